@@ -22,6 +22,12 @@ fg_gather_tables over the ranks' tables): `gather_ms`.
 
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run, one per GPU, RCCL for the
 barrier / max-over-ranks) when no launcher has set WORLD_SIZE; under torchrun it uses the env as given.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, the roofline of the timed
+kernel).  Everything else -- the replica and oracle checks, `cpu_baseline`, the calibration, `e2e`, the bounded legs of the other
+BASELINE configurations (`configs2/3/4`, `small_batch`), cfg5mix's gather, the framing timings, the stamped PMC figures -- runs
+with `--full` only.  `--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of its tables) as
+float64 .npy files, so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -86,6 +92,13 @@ def parse_args():
                     help="cfg2 only: uniform line-length range instead of 192..320 (tuning experiments)")
     ap.add_argument("--invalid-frac", type=float, default=0.01, help="share of invalid lines in the tile (SURVEY 8d: 1 %%)")
     ap.add_argument("--launch-opts", default="", help="fg_set_launch_opts overrides, e.g. lines_per_group=32,waves_per_cu=6 (tuning)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: replica and oracle checks, CPU baseline, calibration, PCIe legs, the "
+                         "bounded legs of the other BASELINE configurations, cfg5mix's gather, framing timings, stamped PMC figures (the "
+                         "--no-* options above trim this set)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; a fixed, seeded sample "
+                         "of rows -- see dump_outputs)")
     a = ap.parse_args()
     if a.tile_lines is None:
         a.tile_lines = 400_000 if a.workload == "cfg5mix" else 1_000_000
@@ -525,21 +538,23 @@ class Resident:
     def decode(self, stream):
         self.dec.decode_device(self.d_bytes, self.d_offsets, self.tables, stream)
 
-    def check_replicas(self):
+    def check_replicas(self, compare=True):
         """every replica of the tile produced the SAME rows -- all fixed columns, not only the status (ent_first is the one
-        column that legitimately differs: entry slices are placed by wave-level allocation); -> (Ok rows of one tile, entries)"""
+        column that legitimately differs: entry slices are placed by wave-level allocation); -> (Ok rows of one tile, entries).
+        compare=False: the two counts only (a plain bench run: the roofline needs the entries, the check is --full's)."""
         import torch
 
         t, reps, n_tile, n = self.tables, self.reps, self.n_tile, self.n
         meta = t.column("meta").view(torch.int32).view(reps, n_tile)
         n_ok_tile = int(((meta[0] & 0xFF) == 0).sum().item())
-        if not os.environ.get("FG_ABLATE"):
+        if compare and not os.environ.get("FG_ABLATE"):
             for col, width in (("meta", 4), ("ts", 8), ("hostname", 8), ("appname", 8), ("procid", 8), ("msgid", 8), ("msg", 8),
                                ("full_msg", 8), ("ent_count", 4)):
                 c = t.column(col)[: n * width].view(torch.int64 if width == 8 else torch.int32).view(reps, n_tile)
                 assert bool((c == c[0:1]).all()), f"replicas disagree in column {col}: work was skipped or corrupted"
-        reserved = int(t.column("ent_used").view(torch.int64)[0].item())
-        assert reserved <= self.ent_cap, "entry table overflow"
+        if compare:
+            reserved = int(t.column("ent_used").view(torch.int64)[0].item())
+            assert reserved <= self.ent_cap, "entry table overflow"
         # entries written (slots are reserved in per-wave chunks; `reserved` is a little more than what the lines own)
         used = int(t.column("ent_count")[: n * 4].view(torch.int32).to(torch.int64).sum().item())
         return n_ok_tile, used
@@ -685,6 +700,74 @@ def calibrate(dec, d_bytes, nbytes, dev, reps=3):
     return out
 
 
+DUMP_ROWS = 1 << 16      # rows sampled per dump (all sub-batches together)
+DUMP_ENTRIES = 1 << 19   # structured-data entries of the sampled rows, at most
+DUMP_ENC_BYTES = 2 << 20  # cfg1: encoded bytes of the first sampled rows, at most
+SPAN_COLUMNS = ("hostname", "appname", "procid", "msgid", "msg", "full_msg")
+
+
+def dump_outputs(out_dir, subs, enc_result=None):
+    """--dump-outputs: what the timed path handed its caller in its LAST step, as float64 (encoded bytes: float32) .npy files in
+    out_dir -- at most ~45 MB.  Per sub-batch (cfg5mix: prefix sub0_ / sub1_) a fixed, seeded sample of DUMP_ROWS rows (rows.npy:
+    their indices) and every fixed column of them: meta, ts, ent_count, and the six spans as (off, len) pairs; the entries those rows
+    own (Ok rows, in row order, up to DUMP_ENTRIES): ent_name (off, len), ent_val (low, high 32 bits), ent_type, ent_flags -- written
+    only when there are any (the headline corpus has no structured data), so no file is empty.  ent_first and ent_used are left out:
+    wave-level allocation places entry slices differently from run to run.  cfg1 adds the encoder's output: enc_len (bytes of each
+    sampled row's message) and enc_bytes (the messages of the first sampled rows, concatenated)."""
+    import torch
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(0x0D0D)
+
+    def u32(x):  # int32 view of uint32 data -> float64, exact
+        return (x.to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64)
+
+    files = {}
+    for k, s in enumerate(subs):
+        pre = f"sub{k}_" if len(subs) > 1 else ""
+        t, n = s.tables, s.n
+        rows = np.unique(rng.integers(0, n, min(n, DUMP_ROWS // len(subs))))
+        idx = torch.from_numpy(rows.astype(np.int64)).to(t.buf.device)
+        files[pre + "rows"] = rows.astype(np.float64)
+        meta = t.column("meta")[: n * 4].view(torch.int32)[idx]
+        files[pre + "meta"] = u32(meta)
+        files[pre + "ts"] = t.column("ts")[: n * 8].view(torch.float64)[idx].cpu().numpy()
+        for col in SPAN_COLUMNS:
+            files[pre + col] = u32(t.column(col)[: n * 8].view(torch.int32).view(n, 2)[idx])
+        count = t.column("ent_count")[: n * 4].view(torch.int32)[idx].to(torch.int64).cpu().numpy()
+        first = t.column("ent_first")[: n * 4].view(torch.int32)[idx].to(torch.int64).cpu().numpy() & 0xFFFFFFFF
+        files[pre + "ent_count"] = count.astype(np.float64)
+        # the entries of the sampled Ok rows, whole rows only, indices checked on the host before the device gathers them
+        count = np.where((files[pre + "meta"].astype(np.int64) & 0xFF) == 0, count, 0)
+        keep = np.cumsum(count) <= DUMP_ENTRIES // len(subs)
+        count, first = count[keep], first[keep]
+        eidx = (np.repeat(first - np.cumsum(count) + count, count) + np.arange(int(count.sum()))).astype(np.int64)
+        used = int(t.column("ent_used").view(torch.int64)[0].item())
+        if eidx.size and not (eidx.min() >= 0 and eidx.max() < min(used, t.ent_cap)):
+            raise RuntimeError(f"dump: entry index outside the {min(used, t.ent_cap)} written entries")
+        if eidx.size:  # (a corpus without structured data has no entries: no empty files)
+            e = torch.from_numpy(eidx).to(t.buf.device)
+            cap = t.ent_cap
+            files[pre + "ent_name"] = u32(t.column("ent_name")[: cap * 8].view(torch.int32).view(cap, 2)[e])
+            files[pre + "ent_val"] = u32(t.column("ent_val")[: cap * 8].view(torch.int32).view(cap, 2)[e])
+            files[pre + "ent_type"] = t.column("ent_type")[:cap][e].cpu().numpy().astype(np.float64)
+            files[pre + "ent_flags"] = t.column("ent_flags")[:cap][e].cpu().numpy().astype(np.float64)
+        if enc_result is not None:
+            e_out, e_off = enc_result
+            lo, hi = e_off[idx].cpu().numpy(), e_off[idx + 1].cpu().numpy()
+            files["enc_len"] = (hi - lo).astype(np.float64)
+            take = np.cumsum(hi - lo) <= DUMP_ENC_BYTES
+            if take.any() and (lo.min() < 0 or hi[take].max() > e_out.numel()):
+                raise RuntimeError("dump: encoder offsets outside its output")
+            parts = [e_out[int(a):int(b)] for a, b in zip(lo[take], hi[take]) if b > a]
+            if parts:
+                files["enc_bytes"] = torch.cat(parts).cpu().numpy().astype(np.float32)
+    for name, arr in files.items():
+        np.save(d / f"{name}.npy", arr)
+    return sorted(files)
+
+
 def dry_run(args):
     """--dry-run-backend gloo: the collectives of main() in main()'s order, on the CPU, with the decode stubbed out (see parse_args).
     Kept beside main() on purpose: a collective added there belongs here too (tests/test_shard_cpu.py::test_bench_dry_run_n_ranks)."""
@@ -705,9 +788,9 @@ def dry_run(args):
     D.barrier()                                    # after it
     elapsed = D.max(time.perf_counter() - t0)      # MAX over ranks
     rank_ms = [r[0] for r in D.all([0.001 * (rank + 1)])]          # every rank's kernel time
-    calib_all = D.all([5000.0 + rank, 6000.0 + rank])              # calibration exchange
+    calib_all = D.all([5000.0 + rank, 6000.0 + rank]) if args.full else []   # calibration exchange
     gather = None
-    if wl == "cfg5mix":
+    if wl == "cfg5mix" and args.full:
         # two synthetic sub-batch tables per rank (one entry per second row), merged by arrival index, then every rank's table to rank 0
         n = 1000 + 10 * rank
         parts, index = [], []
@@ -732,7 +815,7 @@ def dry_run(args):
             assert full.n == sum(1000 + 10 * r for r in range(world))
         gather = {"ranks_gather_ms": g_ms, "all_ranks_gather_ms": [r[0] for r in D.all([g_ms])], "ranks_rows": int(full.n) if rank == 0 else None}
     e2e = None
-    if not args.no_e2e and wl in ("cfg2", "cfg1", "cfg3", "cfg4", "ltsv"):
+    if args.full and not args.no_e2e and wl in ("cfg2", "cfg1", "cfg3", "cfg4", "ltsv"):
         e2e = {"link_peak": D.all([57.0, 57.0, 80.0])}
         for leg in ("decode_batch", "frame_decode_batch", "frame_decode_batch_two_step") + (("transcode_batch",) if wl in ("cfg2", "cfg1") else ()):
             D.barrier()                            # every rank starts a leg together ...
@@ -825,6 +908,7 @@ def main(args=None, thread_rank=None):
 
         raw_stream = d_bytes[:tile_bytes * reps]
         f_off, f_bad, f_n = dec.frame_device(raw_stream, FL.FG_FRAME_LINE, cap_frames=n + 16)  # warm-up + result
+    if wl == "frame" and args.full:
         assert f_n == n and bool((f_off[:n + 1] == d_offsets).all()), "GPU framing disagrees with the generator's offsets"
         evf = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         evf[0].record(stream)
@@ -869,13 +953,14 @@ def main(args=None, thread_rank=None):
         del e_out, e_off
 
     sub_ev = []  # cfg5mix: (start, between, end) per step -> the two kernels' times
+    enc_last = []  # cfg1: what the encoder returned in the last step (--dump-outputs)
 
     def step():
         if wl == "cfg1":
             dec.decode_device(d_bytes, d_offsets, tables, stream)
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(stream)
-            enc.encode_device(dec, d_bytes, d_offsets, n, tables, stream=stream, out=e_buf)
+            enc_last[:] = [enc.encode_device(dec, d_bytes, d_offsets, n, tables, stream=stream, out=e_buf)]
             b.record(stream)
             encode_ms.append((a, b))
         elif wl == "frame":
@@ -904,13 +989,18 @@ def main(args=None, thread_rank=None):
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     rank_ms = [r[0] for r in D.all([kernel_ms])]  # every rank's own kernel time (HIP events on its stream), gathered over RCCL
 
-    # ---- validity --------------------------------------------------------------------------
-    checks = [s.check_replicas() for s in subs]
+    # ---- what the last timed step computed (rank 0's) ---------------------------------------
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, subs, enc_last[0] if enc_last else None)
+
+    # ---- validity (--full; a plain run only counts the Ok rows and entries the roofline needs) ----
+    checks = [s.check_replicas(compare=args.full) for s in subs]
     n_ok_tile, used = sum(c[0] for c in checks), sum(c[1] for c in checks)
 
     # ---- same-process calibration: a float4 copy and a read-only sweep over the decoder's own resident buffer ----
     calib = None
-    if not args.no_calib and wl != "cfg5mix":
+    if args.full and not args.no_calib and wl != "cfg5mix":
         try:
             calib = calibrate(dec, d_bytes, tile_bytes * reps, dev)
         except Exception as e:  # noqa: BLE001 -- never takes the bench line down
@@ -919,7 +1009,7 @@ def main(args=None, thread_rank=None):
 
     # ---- configs[4]: the host-side ordered gather (SURVEY 8d "same + gather time") -----------
     gather = None
-    if wl == "cfg5mix":
+    if wl == "cfg5mix" and args.full:
         from flowgger_amd import shard
 
         side = torch.cuda.Stream(dev)
@@ -985,7 +1075,7 @@ def main(args=None, thread_rank=None):
 
     # ---- PCIe-inclusive legs: every rank, at the same time -----------------------------------
     e2e = None
-    if not args.no_e2e and wl in ("cfg2", "cfg1", "cfg3", "cfg4", "ltsv"):
+    if args.full and not args.no_e2e and wl in ("cfg2", "cfg1", "cfg3", "cfg4", "ltsv"):
         try:
             e2e = e2e_legs(D, dec, fmt, R.data, R.offsets, R.n_tile, R.tile_bytes, want_transcode=wl in ("cfg2", "cfg1"),
                            want_stream=wl in ("cfg2", "cfg1", "cfg3", "cfg4", "ltsv"))
@@ -1035,9 +1125,12 @@ def main(args=None, thread_rank=None):
         if opts:
             out["config"]["launch_opts"] = opts
         out["config"]["parity_checked_by"] = (
-            "in this run: every replica's fixed columns == replica 0's, and the Ok count == the oracle's on the tile (cpu_baseline leg); the "
-            "byte-exact Record comparison with the oracle is the -m gpu test suite's (tiles <= 250 K lines, tests/test_gpu_parity.py), "
+            ("in this run: every replica's fixed columns == replica 0's, and the Ok count == the oracle's on the tile (cpu_baseline leg); "
+             if args.full else "nothing in a plain run (--full compares the replicas and the Ok count with the oracle's); ") +
+            "the byte-exact Record comparison with the oracle is the -m gpu test suite's (tiles <= 250 K lines, tests/test_gpu_parity.py), "
             "not this script's")
+        if dumped:
+            out["outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
         if calib is not None and "copy_GBps" in calib:
             rf = out["roofline"]
             rf["copy_GBps"], rf["read_GBps"] = calib["copy_GBps"], calib["read_GBps"]
@@ -1061,8 +1154,9 @@ def main(args=None, thread_rank=None):
                  "lines_per_s": subs[0].n / (a_ms * 1e-3)},
                 {"format": "ltsv", "lines": subs[1].n, "bytes": subs[1].tile_bytes * reps, "kernel_ms": kernel_ms - a_ms,
                  "lines_per_s": subs[1].n / ((kernel_ms - a_ms) * 1e-3)}]
-            out["gather_ms"] = gather["gather_ms"]
-            out["gather"] = gather
+            if gather is not None:
+                out["gather_ms"] = gather["gather_ms"]
+                out["gather"] = gather
         if wl == "cfg1":
             ems = float(np.mean([a.elapsed_time(b) for a, b in encode_ms[-args.steps:]]))
             out["encode"] = {"ms": ems, "out_bytes": enc_bytes, "lines_per_s": n / (ems * 1e-3),
@@ -1085,7 +1179,7 @@ def main(args=None, thread_rank=None):
                               "fused": fused}
         # HBM traffic from the PMC passes (tools/prof.sh -> profiles/traffic.json): only when it was measured on THESE
         # kernel sources -- a figure from older code is not reported
-        t = stamped(args.workload)
+        t = stamped(args.workload) if args.full else None
         if t:
             out["roofline"]["traffic"] = t["hbm_bytes_per_line"] * n
             out["roofline"]["traffic_profile"] = t.get("profile")
@@ -1093,12 +1187,12 @@ def main(args=None, thread_rank=None):
             if cr:
                 out["roofline"].update({k: cr[k] for k in ("valu_per_line", "salu_per_line", "valu_busy")})
                 out["roofline"]["compute_what"] = cr["what"]
-        elif (ROOT / "profiles" / "traffic.json").exists():
+        elif args.full and (ROOT / "profiles" / "traffic.json").exists():
             out["roofline"]["traffic_note"] = "profiles/traffic.json holds no figure for these kernel sources: not reported"
         if e2e is not None:
             out["e2e"] = e2e
         extra_legs = []
-        if wl == "cfg2" and world == 1 and not args.no_legs:
+        if args.full and wl == "cfg2" and world == 1 and not args.no_legs:
             # BASELINE configs[2] (GELF) and configs[3] (RFC5424 + structured data) on bounded samples, in this process
             for key, lfmt, desc, gen, skey in (
                     ("configs2", 2, WORKLOADS["cfg3"][1], lambda: synth.gelf_lines(250_000, invalid_frac=args.invalid_frac), "cfg3"),
@@ -1111,19 +1205,19 @@ def main(args=None, thread_rank=None):
                     if isinstance(e, AssertionError):
                         raise
                     out[key] = {"error": repr(e)[:200]}
-        if wl == "cfg2" and world == 1 and not args.no_legs:
+        if args.full and wl == "cfg2" and world == 1 and not args.no_legs:
             try:
                 out["small_batch"] = small_batch_leg(dev, local, args.invalid_frac)
             except Exception as e:  # noqa: BLE001 -- an extra leg never takes the bench line down
                 if isinstance(e, AssertionError):
                     raise
                 out["small_batch"] = {"error": repr(e)[:200]}
-        if wl == "cfg2" and world == 1 and "WORLD_SIZE" not in os.environ and not args.no_mix:
+        if args.full and wl == "cfg2" and world == 1 and "WORLD_SIZE" not in os.environ and not args.no_mix:
             # BASELINE configs[4] (mixed RFC5424 + LTSV long-tail stream, host-side ordered gather) on a bounded sample, so that the
             # driver's default run carries its rate and gather time too: this very script, --workload cfg5mix, as a child process
             try:
                 r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--workload", "cfg5mix", "--tile-lines", "200000", "--reps", "5",
-                                    "--steps", "5", "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
+                                    "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=300)
                 m = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
                 out["configs4"] = {"workload": m["config"]["workload"], "value": m["value"], "unit": m["unit"], "ms_per_step": m["ms_per_step"],
                                    "gather_ms": m["gather_ms"], "gather": m["gather"], "sub_batches": m["sub_batches"],
@@ -1133,7 +1227,7 @@ def main(args=None, thread_rank=None):
                                    "what": "python bench.py --workload cfg5mix on a bounded sample (1 M lines resident); full size: that command alone"}
             except Exception as e:  # noqa: BLE001 -- the extra leg never takes the bench line down
                 out["configs4"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:  # (the contract: the CPU leg runs on rank 0 at N = 1 only)
+        if args.full and world == 1 and not args.no_cpu_baseline:  # (the contract: the CPU leg runs on rank 0 at N = 1 only)
             os.sched_setaffinity(0, all_cpus)  # (the CPU leg uses every host core, not only the GPU's NUMA node)
             legs = [(s.fmt, s.data, s.offsets, s.n_tile, synth.LTSV_CONFIG if s.fmt == 1 else None) for s in subs]
             cb, n_ok_cpu = cpu_baseline(legs, pipeline=wl == "cfg1")

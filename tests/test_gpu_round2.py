@@ -89,6 +89,59 @@ def test_bench_launches_its_own_ranks():
     assert out["config"]["lines_per_gpu"] == 200000
 
 
+def _bench_dump(tmp_path, tag, *args):
+    d = tmp_path / tag
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tile-lines", "20000",
+                        "--reps", "2", "--dump-outputs", str(d), *args], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    return line, {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+
+
+@pytest.mark.parametrize("workload", ["cfg4", "cfg1"])
+def test_bench_dump_outputs_are_the_last_steps_tables(tmp_path, workload):
+    """`bench.py --dump-outputs DIR`: a plain run (none of --full's legs in its line) writes the sampled rows of what its timed path
+    computed as float64 / float32 .npy files within 64 MB, the same files on a second run, and the rows are the decoder's rows for
+    those lines (the tile, decoded on its own)."""
+    line, got = _bench_dump(tmp_path, "a", "--workload", workload)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"cpu_baseline", "e2e", "configs2", "configs3", "configs4", "small_batch"} & set(line)
+    assert "copy_GBps" not in line["roofline"] and sorted(line["outputs"]["files"]) == sorted(got)
+    assert all(a.dtype in (np.float32, np.float64) and a.size > 0 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    _, again = _bench_dump(tmp_path, "b", "--workload", workload)
+    assert sorted(again) == sorted(got) and all(np.array_equal(got[k], again[k], equal_nan=True) for k in got)
+    # the sampled rows == the same lines decoded as one tile (a replica's rows equal the tile's)
+    lines = synth.rfc5424_lines(20_000, cfg=4, sd=True) if workload == "cfg4" else synth.rfc5424_lines(20_000, cfg=2)
+    data, offsets = synth.pack(lines)
+    tab = RFC5424Decoder().decode_packed(data, offsets)
+    rows = got["rows"].astype(np.int64) % len(lines)
+    assert np.array_equal(got["meta"], tab.a["meta"][rows].astype(np.float64))
+    assert np.array_equal(got["ts"], tab.a["ts"][rows], equal_nan=True)
+    for col in ("hostname", "appname", "procid", "msgid", "msg", "full_msg"):
+        assert np.array_equal(got[col], tab.span(col)[rows].astype(np.float64)), col
+    assert np.array_equal(got["ent_count"], tab.a["ent_count"][rows].astype(np.float64))
+    ok = (tab.a["meta"][rows] & 0xFF) == 0
+    eidx = np.concatenate([np.arange(f, f + c) for f, c in zip(tab.a["ent_first"][rows][ok].astype(np.int64),
+                                                               tab.a["ent_count"][rows][ok].astype(np.int64))] + [np.zeros(0, np.int64)])
+    m = len(got.get("ent_type", ()))
+    assert (workload == "cfg4") == (m > 0) == ("ent_name" in got) and m <= eidx.size
+    if m:
+        eidx = eidx[:m]
+        assert np.array_equal(got["ent_name"], tab.a["ent_name"].reshape(-1, 2)[eidx].astype(np.float64))
+        assert np.array_equal(got["ent_val"], tab.a["ent_val"].view(np.uint32).reshape(-1, 2)[eidx].astype(np.float64))
+        assert np.array_equal(got["ent_type"], tab.a["ent_type"][eidx].astype(np.float64))
+        assert np.array_equal(got["ent_flags"], tab.a["ent_flags"][eidx].astype(np.float64))
+    if workload == "cfg1":  # decode -> GELF encoder -> line merger: the messages of the sampled rows, the first of them byte for byte
+        from flowgger_amd import GelfEncoder, Pipeline
+
+        want = Pipeline(RFC5424Decoder(), GelfEncoder(None, merger="line")).run_packed(data, offsets)
+        lo, hi = want.out_offsets[rows].astype(np.int64), want.out_offsets[rows + 1].astype(np.int64)
+        assert np.array_equal(got["enc_len"], (hi - lo).astype(np.float64))
+        k = int((np.cumsum(hi - lo) <= 2 << 20).sum())
+        assert k > 0 and np.array_equal(got["enc_bytes"], np.concatenate([want.out[a:b] for a, b in zip(lo[:k], hi[:k])]).astype(np.float32))
+
+
 @pytest.mark.parametrize("src,enc,merger", [("rfc5424", "gelf", "line"), ("sd", "rfc5424", "syslen"), ("gelf", "gelf", "nul")])
 def test_transcode_large_batch_is_sliced_over_two_streams(oracle, src, enc, merger):
     """fg_transcode_batch on a large batch: upload -> decode -> encode -> download in slices (rounds 2-5: ~32 MiB slices on two lanes;

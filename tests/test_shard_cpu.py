@@ -106,7 +106,7 @@ def test_bench_dry_run_n_ranks(workload, world):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--dry-run-backend", "gloo", "--workload", workload,
-                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+                        "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["dry_run"] is True and line["n_gpus"] == world and line["ranks"]["n"] == world and line["calibration_ranks"] == world
