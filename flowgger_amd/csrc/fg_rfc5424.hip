@@ -1113,6 +1113,12 @@ extern "C" uint64_t fg_stash_bytes(uint32_t blocks) {
     return (uint64_t)blocks * fg::kStashEntries * fg::kStashWords * fg::kWave * sizeof(uint64_t);
 }
 
+// The default tile of the short-line whole-line launch: the largest multiple of 1 KiB whose LDS (tile + 64 + one bitmap) leaves eight
+// waves per CU -- what the kernel's registers allow -- room in the CU's 160 KiB.
+constexpr uint32_t kShortLineTile = 17408;
+static_assert(kShortLineTile + 64u + (kShortLineTile / 16u + 16u) * 2u <= 160u * 1024u / 8u, "eight waves per CU");
+static_assert(kShortLineTile + 1024u + 64u + ((kShortLineTile + 1024u) / 16u + 16u) * 2u > 160u * 1024u / 8u, "the largest such tile");
+
 // host-side launcher (called from fg_capi.cpp).  stash: device scratch of fg_stash_bytes(stash_blocks)
 // bytes (or NULL: SD lines are then parsed twice); the persistent grid is capped at stash_blocks.
 extern "C" int fg_launch_rfc5424(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t,
@@ -1146,8 +1152,13 @@ extern "C" int fg_launch_rfc5424(const uint8_t* d_bytes, const uint64_t* d_offse
                                      fg::PlanFormat().classes(2u).lds_tile(fg::sd2::extra_bytes).tile(12288u).chunk(128u).tickets_from(4u));
     else
         // (tickets from 20 chunks per wave on: the HBM-bound kernel pays for the first round's burst, fg_pipeline.hpp plan_launch)
+        // (short lines: a tile of at most kShortLineTile -- the whole-line kernel takes 209 VGPRs, two waves per SIMD, and with the
+        //  18 KiB tile that 64 lines of 254 B ask for, LDS -- 20.8 KiB per wave -- cut that to SEVEN waves per CU; 17 KiB is 19.7 KiB
+        //  of LDS, eight.  cfg2, one box, alternated: 15.13-15.73 G lines/s at 18 KiB, 15.89-16.91 at 17 KiB, 14.76-15.11 at 16 KiB,
+        //  where groups are cut short by bytes)
         prc = head ? fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false, true>, n, plan_len, 0u, 57344u, sb, &p, *lo)
-                   : fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false>, n, plan_len, 0u, 57344u, sb, &p, *lo, fg::PlanFormat().tickets_from(20u).taper_levels(0u));
+                   : fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false>, n, plan_len, 0u, 57344u, sb, &p, *lo,
+                                     fg::PlanFormat().tickets_from(20u).taper_levels(0u).tile(avg_len < 320u ? kShortLineTile : 0u));
     if (prc) return -1;
     if (stash_blocks == 0) stash = nullptr;
     dim3 grid(p.blocks), block(fg::kWave);
