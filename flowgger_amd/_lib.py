@@ -63,7 +63,7 @@ class fg_gelf_extra(C.Structure):
     _fields_ = [("n", C.c_uint32), ("keys", C.POINTER(C.c_char_p)), ("values", C.POINTER(C.c_char_p))]
 
 
-FG_ENC_GELF, FG_ENC_LTSV, FG_ENC_RFC5424, FG_ENC_RFC3164, FG_ENC_PASSTHROUGH = range(5)
+FG_ENC_GELF, FG_ENC_LTSV, FG_ENC_RFC5424, FG_ENC_RFC3164, FG_ENC_PASSTHROUGH, FG_ENC_CAPNP = range(6)
 FG_MERGE_NONE, FG_MERGE_LINE, FG_MERGE_NUL, FG_MERGE_SYSLEN = range(4)
 
 

@@ -193,7 +193,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             continue
         units.append((name, objdir / (name + ".o"), []))
         if name == "fg_encode.hip":
-            for enc in range(5):  # fg_encoder values; GELF (0) has two ranking-scratch sizes
+            for enc in range(6):  # fg_encoder values; GELF (0) has three ranking-scratch sizes
                 for wr in (0, 1):
                     for slots in ((1, 8, 32) if enc == 0 else (0,)):
                         units.append((name, objdir / f"fg_encode.e{enc}w{wr}s{slots}.o",

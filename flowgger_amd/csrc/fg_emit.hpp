@@ -1,4 +1,4 @@
-// fg_emit.hpp -- the five Encoder::encode implementations + the three Merger::frame implementations, as
+// fg_emit.hpp -- the six Encoder::encode implementations + the three Merger::frame implementations, as
 // per-record emitters that read a decode-table row (spans into the packed line bytes + the entry slice)
 // and push the output bytes into a sink -- the Record is never materialised.
 //
@@ -7,6 +7,7 @@
 //   Rfc5424Emitter      encoder/rfc5424_encoder.rs:28-93  (+ impl Display for StructuredData, record.rs:42-67)
 //   Rfc3164Emitter      encoder/rfc3164_encoder.rs:28-101
 //   PassthroughEmitter  encoder/passthrough_encoder.rs:24-50
+//   CapnpEmitter        encoder/capnp_encoder.rs:36-109 (+ capnp 0.14 serialize::write_message)
 //   frame               merger/{line,nul,syslen}_merger.rs
 //
 // A Record field is a DECODED view of a span: raw bytes (RFC5424 / LTSV sources), unescape_sd_value
@@ -64,7 +65,8 @@ struct EncCfg {
     uint32_t src_fmt;          // which decoder produced the tables (fg_format)
     uint32_t enc;              // fg_encoder
     uint32_t merger;           // fg_merger
-    uint32_t ltsv_extra_off, ltsv_extra_len;  // "k1:v1\tk2:v2" (already escaped, '_' stripped); len 0 = none
+    uint32_t ltsv_extra_off, ltsv_extra_len;  // "k1:v1\tk2:v2" (already escaped, '_' stripped); len 0 = none.  Capnp: the
+                                              // output.capnp_extra list's byte image (8-byte aligned; CapnpEmitter)
     uint32_t prepend_off, prepend_len;        // syslog_prepend_timestamp header; len 0xFFFFFFFF = not configured
     double now_ts;             // Record.ts of rows flagged FG_F_TS_NOW
     uint32_t sort_slots;       // GELF: entries of the per-lane ranking scratch (<= kSortSlots)
@@ -1342,6 +1344,485 @@ struct PassthroughEmitter : Base<S, R> {
     }
 };
 
+// =================================================================================================
+// Cap'n Proto (encoder/capnp_encoder.rs: build_record + capnp::serialize::write_message, schema record.capnp)
+// =================================================================================================
+// A message is the segment table, then the segments.  Segment 0 starts with the root pointer and the Record struct (2 data words,
+// 9 pointers: words 0 .. 11); every text / list the builder allocates follows in allocation order.  Texts are the DECODED bytes, a
+// NUL and zero padding to a whole word.  Pointers are relative, so the output.capnp_extra list -- tag, pair structs, texts -- is
+// the same byte image for every row: fg_enc_cfg.hpp builds it once (cfg.ltsv_extra_off / _len carry it for this encoder).
+// A row whose objects exceed the first segment's 1024 words takes capnp_multi (out of line): the allocator of capnp 0.14, far
+// pointers and landing pads included (the rules are not pinned by a reference vector).
+constexpr uint32_t kCapnpSeg0Words = 1024;  // capnp::message::SUGGESTED_FIRST_SEGMENT_WORDS
+constexpr uint32_t kCapnpMaxSegs = 32;      // segment k > 0 holds >= 1024 * 2^k words (GrowHeuristically): never reached
+constexpr uint32_t kCapnpNone = 0xFFFFFFFFu;
+
+// where an object landed: its first word (far: its landing pad is the word before it)
+struct CapnpPlace {
+    uint32_t seg, pos, far;
+};
+// message::HeapAllocator + private/arena.rs BuilderArenaImpl: an object is tried in the segment that holds its pointer (`home`),
+// else it takes one more word (the landing pad) in the first segment with room, else in a new segment of max(that, next_size)
+struct CapnpArena {
+    uint32_t cap[kCapnpMaxSegs], used[kCapnpMaxSegs];
+    uint32_t nseg;
+    uint64_t next;
+    FGE_HD void init() {  // segment 0 (allocate_segment: next_size 1024 -> 2048), the root pointer and the Record struct
+        nseg = 1;
+        cap[0] = kCapnpSeg0Words;
+        used[0] = 12u;
+        next = 2u * kCapnpSeg0Words;
+    }
+    FGE_HD CapnpPlace alloc(uint32_t home, uint32_t a) {
+        if (cap[home] - used[home] >= a) {
+            const CapnpPlace p{home, used[home], 0u};
+            used[home] += a;
+            return p;
+        }
+        for (uint32_t s = 0; s < nseg; ++s) {
+            if (cap[s] - used[s] >= a + 1u) {
+                const CapnpPlace p{s, used[s] + 1u, 1u};
+                used[s] += a + 1u;
+                return p;
+            }
+        }
+        const uint32_t s = nseg < kCapnpMaxSegs ? nseg++ : kCapnpMaxSegs - 1u;
+        const uint64_t c = (uint64_t)a + 1u > next ? (uint64_t)a + 1u : next;
+        next += c;
+        cap[s] = (uint32_t)c;
+        used[s] = a + 1u;
+        return CapnpPlace{s, 1u, 1u};
+    }
+};
+
+template <class S, class R>
+struct CapnpEmitter;
+// the multi-segment form: its own function, everything by value (as encode_lane_global in fg_encode.hip) -- the arena is a
+// dynamically indexed array, i.e. scratch memory, and must not reach the single-segment path
+template <class S, class R>
+#if defined(__HIPCC__)
+__host__ __device__ __attribute__((noinline))
+#else
+inline
+#endif
+S capnp_multi(S sink, EncCfg cfg, R rd, DevTables t, uint64_t li, uint32_t meta, RowRegs row) {
+    CapnpEmitter<S, R> em(sink, cfg, rd, t, li, meta, &row);
+    em.run_multi();
+    return sink;
+}
+
+template <class S, class R>
+struct CapnpEmitter : Base<S, R> {
+    using B = Base<S, R>;
+    using typename B::Dyn;
+    using B::cfg;
+    using B::li;
+    using B::meta;
+    using B::out;
+    using B::rd;
+    using B::t;
+    uint32_t plo = 0, phi = 0;  // a word waiting for its partner: pointer and struct words go out two at a time
+    bool pend = false;
+    FGE_HD CapnpEmitter(S& o, const EncCfg& c, R r, const DevTables& tb, uint64_t l, uint32_t m, const RowRegs* pre) : B{o, c, r, tb, l, m} { this->load_row(pre); }
+
+    static FGE_HD uint32_t tw(uint32_t len) { return (len + 8u) >> 3; }                 // words of a text: bytes + NUL, padded
+    static FGE_HD uint32_t text_hi(uint32_t len) { return 2u | (len + 1u) << 3; }       // list pointer, element size byte
+    static FGE_HD uint32_t list_hi(uint32_t n) { return 7u | (4u * n) << 3; }           // list pointer, inline composite: 4 words a pair
+    static FGE_HD uint32_t near_lo(uint32_t ptr_word, uint32_t target) { return 1u | (target - ptr_word - 1u) << 2; }
+
+    FGE_HD void word(uint32_t lo, uint32_t hi) {
+        if (pend) {
+            out.put16(plo, phi, lo, hi);
+            pend = false;
+        } else {
+            plo = lo;
+            phi = hi;
+            pend = true;
+        }
+    }
+    FGE_HD void flush() {
+        if (pend) out.put_part(plo, phi, 0u, 0u, 8u);
+        pend = false;
+    }
+    // ---- the record's texts and their decoded lengths ----
+    FGE_HD uint32_t dec_len(uint32_t off, uint32_t len, uint32_t mode) {
+        if (mode == M_RAW) return len;
+        uint32_t n = 0;
+        for_each_decoded(rd, off, len, mode, [&](uint32_t) { ++n; });
+        return n;
+    }
+    FGE_HD bool field_on(int col) const { return col == S_HOST || this->some(col); }  // Record.hostname is a String: always set
+    FGE_HD uint32_t field_len(int col) {
+        const fg_span s = this->span(col);
+        return s.len == FG_NONE ? 0u : dec_len(s.off, s.len, this->field_mode(col));
+    }
+    FGE_HD uint32_t key_len(uint32_t e) {  // '_' + name [+ LTSV suffix]
+        const Dyn d = this->dyn_of(e);
+        return 1u + d.dlen + d.sl;
+    }
+    FGE_HD uint32_t val_len(uint32_t e) {
+        const uint64_t v = t.ent_val[e];
+        return dec_len((uint32_t)v, (uint32_t)(v >> 32), this->value_mode(e));
+    }
+    FGE_HD bool is_str(uint32_t e) const { return t.ent_type[e] == FG_T_STRING; }
+    // only sd[0] is encoded (capnp_encoder.rs:79-81): its sd_id entry (kCapnpNone: None) and its pairs [lo, hi)
+    FGE_HD void sd0(uint32_t& sdid, uint32_t& lo, uint32_t& hi) const {
+        const uint32_t end = this->row_ef + this->row_ec;
+        uint32_t e = this->row_ef;
+        sdid = kCapnpNone;
+        if (cfg.src_fmt == FG_RFC5424 && e < end && t.ent_type[e] == FG_T_SDID) sdid = e++;  // (other sources: one element, sd_id None)
+        lo = e;
+        while (e < end && t.ent_type[e] != FG_T_SDID) ++e;
+        hi = e;
+    }
+    // output.capnp_extra, prebuilt: dword k of its image
+    FGE_HD uint32_t xd(uint32_t k) const { return reinterpret_cast<const uint32_t*>(cfg.blob + cfg.ltsv_extra_off)[k]; }
+    FGE_HD uint32_t extra_n() const { return cfg.ltsv_extra_len ? xd(0) >> 2 : 0u; }
+
+    FGE_HD void pad(uint32_t len) { out.put_part(0u, 0u, 0u, 0u, 8u * tw(len) - len); }  // the NUL and the padding: one piece
+    FGE_HD void raw_bytes(uint32_t off, uint32_t len) {
+        uint32_t i = 0;
+        for (; i + 16u <= len; i += 16u) {
+            uint32_t q[4];
+            rd.load16(off + i, q);
+            out.put16(q[0], q[1], q[2], q[3]);
+        }
+        const uint32_t nb = len - i;
+        if (nb) {
+            uint32_t q[4];
+            rd.load16p(off + i, nb, q);
+            B::keep_low(q, nb);
+            out.put_part(q[0], q[1], q[2], q[3], nb);
+        }
+    }
+    // a text from the line (dlen: its decoded length): sixteen bytes per piece, the last 0 .. 15 bytes together with the NUL and
+    // the padding as ONE piece of 8 or 16 bytes
+    FGE_HD void text(uint32_t off, uint32_t len, uint32_t mode, uint32_t dlen) {
+        if (mode != M_RAW) {
+            for_each_decoded(rd, off, len, mode, [&](uint32_t c) { out.put(c); });
+            pad(dlen);
+            return;
+        }
+        uint32_t i = 0;
+        for (; i + 16u <= len; i += 16u) {
+            uint32_t q[4];
+            rd.load16(off + i, q);
+            out.put16(q[0], q[1], q[2], q[3]);
+        }
+        const uint32_t nb = len - i;
+        uint32_t q[4] = {0u, 0u, 0u, 0u};
+        if (nb) {
+            rd.load16p(off + i, nb, q);
+            B::keep_low(q, nb);
+        }
+        out.put_part(q[0], q[1], q[2], q[3], nb < 8u ? 8u : 16u);
+    }
+    FGE_HD void field_text(int col, uint32_t dlen) {
+        const fg_span s = this->span(col);
+        if (s.len == FG_NONE) {  // hostname None in the table: "" in the Record
+            out.put_part(0u, 0u, 0u, 0u, 8u);
+            return;
+        }
+        text(s.off, s.len, this->field_mode(col), dlen);
+    }
+    FGE_HD void sdid_text(uint32_t e) {
+        const fg_span id = t.ent_name[e];
+        text(id.off, id.len, M_RAW, id.len);
+    }
+    FGE_HD void key_text(uint32_t e) {
+        const Dyn d = this->dyn_of(e);
+        out.put('_');
+        if (d.mode == M_RAW) {
+            raw_bytes(d.off + d.skip, d.dlen);
+            for (uint32_t i = 0; i < d.sl; ++i) out.put((uint32_t)cfg.blob[d.so + i]);
+        } else {
+            this->dyn_stream(d, [&](uint32_t c) { out.put(c); });
+        }
+        pad(1u + d.dlen + d.sl);
+    }
+    FGE_HD void val_text(uint32_t e) {
+        const uint64_t v = t.ent_val[e];
+        const uint32_t mode = this->value_mode(e);
+        text((uint32_t)v, (uint32_t)(v >> 32), mode, mode == M_RAW ? 0u : val_len(e));
+    }
+    // a Pair struct: data word 0 = the union's discriminant (SDValue order = FG_T_*) [+ the bool at bit 16], data word 1 = the
+    // number's bits, pointer 0 = the key, pointer 1 = the string
+    FGE_HD void pair_struct(uint32_t e, uint32_t klo, uint32_t khi, uint32_t vlo, uint32_t vhi) {
+        const uint32_t ty = t.ent_type[e];
+        const uint64_t v = t.ent_val[e];
+        const bool num = ty == FG_T_F64 || ty == FG_T_I64 || ty == FG_T_U64;
+        word(ty | ((ty == FG_T_BOOL && v != 0u) ? 1u << 16 : 0u), 0u);
+        word(num ? (uint32_t)v : 0u, num ? (uint32_t)(v >> 32) : 0u);
+        word(klo, khi);
+        word(ty == FG_T_STRING ? vlo : 0u, ty == FG_T_STRING ? vhi : 0u);
+    }
+    FGE_HD void data_words() {
+        const double ts = this->record_ts();
+        uint64_t b;
+        memcpy(&b, &ts, 8);
+        word((uint32_t)b, (uint32_t)(b >> 32));
+        word((uint32_t)FG_META_FACILITY(meta) | (uint32_t)FG_META_SEVERITY(meta) << 8, 0u);
+    }
+
+    FGE_HD uint32_t run() {
+        uint32_t sdid, elo, ehi;
+        sd0(sdid, elo, ehi);
+        const bool sd = this->row_ec != 0u;
+        const uint32_t lh = field_len(S_HOST), la = field_len(S_APP), lp = field_len(S_PROC), lm = field_len(S_MSGID), lg = field_len(S_MSG),
+                       lf = field_len(S_FULL);
+        const uint32_t ls = sdid != kCapnpNone ? t.ent_name[sdid].len : 0u;
+        const uint32_t np = ehi - elo;
+        uint32_t wt = 0;  // the pairs' texts
+        if (sd) {
+            for (uint32_t e = elo; e < ehi; ++e) wt += tw(key_len(e)) + (is_str(e) ? tw(val_len(e)) : 0u);
+        }
+        const uint32_t xn = extra_n();
+        // the objects in allocation order, one segment
+        uint32_t p = 12u;
+        const uint32_t ph = p;
+        p += tw(lh);
+        const uint32_t pa = p;
+        p += this->some(S_APP) ? tw(la) : 0u;
+        const uint32_t pp = p;
+        p += this->some(S_PROC) ? tw(lp) : 0u;
+        const uint32_t pm = p;
+        p += this->some(S_MSGID) ? tw(lm) : 0u;
+        const uint32_t pg = p;
+        p += this->some(S_MSG) ? tw(lg) : 0u;
+        const uint32_t pf = p;
+        p += this->some(S_FULL) ? tw(lf) : 0u;
+        const uint32_t ps = p;
+        p += sdid != kCapnpNone ? tw(ls) : 0u;
+        const uint32_t pl = p;
+        p += sd ? 1u + 4u * np + wt : 0u;
+        const uint32_t px = p;
+        p += cfg.ltsv_extra_len >> 3;
+        if (p > kCapnpSeg0Words) {
+            RowRegs rr;
+            rr.s0 = this->s0;
+            rr.s1 = this->s1;
+            rr.s2 = this->s2;
+            rr.s3 = this->s3;
+            rr.s4 = this->s4;
+            rr.s5 = this->s5;
+            rr.ts = this->row_ts;
+            rr.ef = this->row_ef;
+            rr.ec = this->row_ec;
+            R r2 = rd;
+#if defined(__HIP_DEVICE_COMPILE__)
+            // (the reader's pointer made opaque: otherwise the compiler carries "this is the LDS tile" into the out-of-line function
+            //  and emits an address-space compare gfx950 cannot encode -- "Illegal instruction detected", V_CMP with src_shared_base)
+            uint64_t w = (uint64_t)(uintptr_t)r2.words;
+            asm volatile("" : "+v"(w));
+            r2.words = reinterpret_cast<const uint32_t*>((uintptr_t)w);
+#endif
+            out = capnp_multi<S, R>(out, cfg, r2, t, li, meta, rr);
+            return ES_OK;
+        }
+        if (S::kCount) {
+            out.add(8u + 8u * p);
+            return ES_OK;
+        }
+        out.put16(0u, p, 0u, 0x00090002u);  // segment table (one segment of p words), root pointer: struct, 2 data words, 9 pointers
+        data_words();
+        word(near_lo(3u, ph), text_hi(lh));
+        if (this->some(S_APP)) word(near_lo(4u, pa), text_hi(la));
+        else word(0u, 0u);
+        if (this->some(S_PROC)) word(near_lo(5u, pp), text_hi(lp));
+        else word(0u, 0u);
+        if (this->some(S_MSGID)) word(near_lo(6u, pm), text_hi(lm));
+        else word(0u, 0u);
+        if (this->some(S_MSG)) word(near_lo(7u, pg), text_hi(lg));
+        else word(0u, 0u);
+        if (this->some(S_FULL)) word(near_lo(8u, pf), text_hi(lf));
+        else word(0u, 0u);
+        if (sdid != kCapnpNone) word(near_lo(9u, ps), text_hi(ls));
+        else word(0u, 0u);
+        if (sd) word(near_lo(10u, pl), list_hi(np));
+        else word(0u, 0u);
+        if (xn) word(near_lo(11u, px), list_hi(xn));
+        else word(0u, 0u);
+        flush();
+        field_text(S_HOST, lh);
+        if (this->some(S_APP)) field_text(S_APP, la);
+        if (this->some(S_PROC)) field_text(S_PROC, lp);
+        if (this->some(S_MSGID)) field_text(S_MSGID, lm);
+        if (this->some(S_MSG)) field_text(S_MSG, lg);
+        if (this->some(S_FULL)) field_text(S_FULL, lf);
+        if (sdid != kCapnpNone) sdid_text(sdid);
+        if (sd) {
+            word(np << 2, 2u | 2u << 16);  // the tag: n elements of 2 data words + 2 pointers
+            uint32_t q = pl + 1u + 4u * np;  // where the next key / value goes
+            for (uint32_t e = elo; e < ehi; ++e) {
+                const uint32_t sw = pl + 1u + 4u * (e - elo);
+                const uint32_t kl = key_len(e);
+                const uint32_t klo = near_lo(sw + 2u, q);
+                q += tw(kl);
+                uint32_t vlo = 0u, vhi = 0u;
+                if (is_str(e)) {
+                    const uint32_t vl = val_len(e);
+                    vlo = near_lo(sw + 3u, q);
+                    vhi = text_hi(vl);
+                    q += tw(vl);
+                }
+                pair_struct(e, klo, text_hi(kl), vlo, vhi);
+            }
+            flush();
+            for (uint32_t e = elo; e < ehi; ++e) {
+                key_text(e);
+                if (is_str(e)) val_text(e);
+            }
+        }
+        if (xn) this->blob(cfg.ltsv_extra_off, cfg.ltsv_extra_len);
+        return ES_OK;
+    }
+
+    // ---- the multi-segment form ----
+    enum : uint32_t { K_ROOT = 0, K_FIELD = 1, K_SDID = 2, K_PAIRS = 3, K_KEY = 4, K_VAL = 5, K_EXTRA = 6, K_XKEY = 7, K_XVAL = 8 };
+    // extra pair i's key (v = 0) or value (v = 1) in the image: its length and its first word there
+    FGE_HD uint32_t xtext_len(uint32_t i, uint32_t v) const { return (xd(2u * (3u + 4u * i + v) + 1u) >> 3) - 1u; }
+    FGE_HD uint32_t xtext_word(uint32_t i, uint32_t v) const { return 3u + 4u * i + v + 1u + (xd(2u * (3u + 4u * i + v)) >> 2); }
+    // the pairs' texts in allocation order (each pair: key, then its string value), from the state right after their list
+    template <class F>
+    FGE_HD void pair_objs(CapnpArena& ar, uint32_t seg, uint32_t elo, uint32_t ehi, F&& f) {
+        for (uint32_t e = elo; e < ehi; ++e) {
+            const uint32_t kl = key_len(e);
+            const CapnpPlace kp = ar.alloc(seg, tw(kl));
+            CapnpPlace vp{0u, 0u, 0u};
+            uint32_t vl = 0u;
+            if (is_str(e)) {
+                vl = val_len(e);
+                vp = ar.alloc(seg, tw(vl));
+            }
+            f(e - elo, e, kp, kl, vp, vl);
+        }
+    }
+    template <class F>
+    FGE_HD void extra_objs(CapnpArena& ar, uint32_t seg, uint32_t xn, F&& f) {
+        for (uint32_t i = 0; i < xn; ++i) {
+            const uint32_t kl = xtext_len(i, 0u), vl = xtext_len(i, 1u);
+            const CapnpPlace kp = ar.alloc(seg, tw(kl));
+            const CapnpPlace vp = ar.alloc(seg, tw(vl));
+            f(i, i, kp, kl, vp, vl);
+        }
+    }
+    // every object of the message in allocation order: f(kind, index, place, length or count, arena after the allocation)
+    template <class F>
+    FGE_HD void walk(CapnpArena& ar, uint32_t sdid, uint32_t elo, uint32_t ehi, uint32_t xn, F&& f) {
+        ar.init();
+        f(K_ROOT, 0u, CapnpPlace{0u, 0u, 0u}, 0u, ar);
+        for (int col = S_HOST; col <= S_FULL; ++col) {
+            if (!field_on(col)) continue;
+            const uint32_t l = field_len(col);
+            f(K_FIELD, (uint32_t)col, ar.alloc(0u, tw(l)), l, ar);
+        }
+        if (sdid != kCapnpNone) {
+            const uint32_t l = t.ent_name[sdid].len;
+            f(K_SDID, sdid, ar.alloc(0u, tw(l)), l, ar);
+        }
+        if (this->row_ec != 0u) {
+            const CapnpPlace lp = ar.alloc(0u, 1u + 4u * (ehi - elo));
+            f(K_PAIRS, 0u, lp, ehi - elo, ar);
+            pair_objs(ar, lp.seg, elo, ehi, [&](uint32_t, uint32_t e, const CapnpPlace& kp, uint32_t kl, const CapnpPlace& vp, uint32_t vl) {
+                f(K_KEY, e, kp, kl, ar);
+                if (is_str(e)) f(K_VAL, e, vp, vl, ar);
+            });
+        }
+        if (xn) {
+            const CapnpPlace lp = ar.alloc(0u, 1u + 4u * xn);
+            f(K_EXTRA, 0u, lp, xn, ar);
+            extra_objs(ar, lp.seg, xn, [&](uint32_t, uint32_t i, const CapnpPlace& kp, uint32_t kl, const CapnpPlace& vp, uint32_t vl) {
+                f(K_XKEY, i, kp, kl, ar);
+                f(K_XVAL, i, vp, vl, ar);
+            });
+        }
+    }
+    // the pointer at word `pw` of its segment to the object at p: near, or far to p's landing pad
+    FGE_HD void ptr(const CapnpPlace& p, uint32_t pw, uint32_t hi) {
+        if (p.far) word(2u | (p.pos - 1u) << 3, p.seg);
+        else word(near_lo(pw, p.pos), hi);
+    }
+    FGE_HD void list_words(const CapnpPlace& lp, uint32_t n, bool extra, uint32_t elo, uint32_t ehi, const CapnpArena& after) {
+        word(n << 2, 2u | 2u << 16);
+        CapnpArena sub = after;
+        auto st = [&](uint32_t i, uint32_t e, const CapnpPlace& kp, uint32_t kl, const CapnpPlace& vp, uint32_t vl) {
+            const uint32_t sw = lp.pos + 1u + 4u * i;
+            if (extra) {
+                word(0u, 0u);
+                word(0u, 0u);
+                ptr(kp, sw + 2u, text_hi(kl));
+                ptr(vp, sw + 3u, text_hi(vl));
+                return;
+            }
+            const uint32_t ty = t.ent_type[e];
+            const uint64_t v = t.ent_val[e];
+            const bool num = ty == FG_T_F64 || ty == FG_T_I64 || ty == FG_T_U64;
+            word(ty | ((ty == FG_T_BOOL && v != 0u) ? 1u << 16 : 0u), 0u);
+            word(num ? (uint32_t)v : 0u, num ? (uint32_t)(v >> 32) : 0u);
+            ptr(kp, sw + 2u, text_hi(kl));
+            if (ty == FG_T_STRING) ptr(vp, sw + 3u, text_hi(vl));
+            else word(0u, 0u);
+        };
+        if (extra) extra_objs(sub, lp.seg, n, st);
+        else pair_objs(sub, lp.seg, elo, ehi, st);
+        flush();
+    }
+    FGE_HD void run_multi() {
+        uint32_t sdid, elo, ehi;
+        sd0(sdid, elo, ehi);
+        const uint32_t xn = extra_n();
+        // pass 1: the segments, and where the root's nine pointers go
+        CapnpArena ar;
+        CapnpPlace rp[9];
+        uint32_t rhi[9], ron[9];
+        for (uint32_t j = 0; j < 9u; ++j) ron[j] = 0u;
+        walk(ar, sdid, elo, ehi, xn, [&](uint32_t kind, uint32_t idx, const CapnpPlace& p, uint32_t n, const CapnpArena&) {
+            const uint32_t j = kind == K_FIELD ? idx : kind == K_SDID ? 6u : kind == K_PAIRS ? 7u : kind == K_EXTRA ? 8u : 9u;
+            if (j == 9u) return;
+            rp[j] = p;
+            rhi[j] = (kind == K_PAIRS || kind == K_EXTRA) ? list_hi(n) : text_hi(n);
+            ron[j] = 1u;
+        });
+        const uint32_t nseg = ar.nseg;
+        uint32_t words = (nseg + 2u) >> 1;  // the segment table: count - 1, one size per segment, padded to a whole word
+        for (uint32_t s = 0; s < nseg; ++s) words += ar.used[s];
+        if (S::kCount) {
+            out.add(8u * words);
+            return;
+        }
+        for (uint32_t k = 0; k < nseg + 1u; k += 2u) word(k == 0u ? nseg - 1u : ar.used[k - 1u], k < nseg ? ar.used[k] : 0u);
+        flush();
+        // pass 2 per segment: its objects in allocation order are its words in order
+        for (uint32_t s = 0; s < nseg; ++s) {
+            CapnpArena cur;
+            walk(cur, sdid, elo, ehi, xn, [&](uint32_t kind, uint32_t idx, const CapnpPlace& p, uint32_t n, const CapnpArena& after) {
+                if (p.seg != s) return;
+                if (kind == K_ROOT) {
+                    word(0u, 0x00090002u);
+                    data_words();
+                    for (uint32_t j = 0; j < 9u; ++j) {
+                        if (ron[j]) ptr(rp[j], 3u + j, rhi[j]);
+                        else word(0u, 0u);
+                    }
+                    flush();
+                    return;
+                }
+                const bool list = kind == K_PAIRS || kind == K_EXTRA;
+                if (p.far) {  // the landing pad: the object's own pointer, offset 0
+                    word(1u, list ? list_hi(n) : text_hi(n));
+                    flush();
+                }
+                if (list) list_words(p, n, kind == K_EXTRA, elo, ehi, after);
+                else if (kind == K_FIELD) field_text((int)idx, n);
+                else if (kind == K_SDID) sdid_text(idx);
+                else if (kind == K_KEY) key_text(idx);
+                else if (kind == K_VAL) val_text(idx);
+                else this->blob(cfg.ltsv_extra_off + 8u * xtext_word(idx, kind == K_XVAL ? 1u : 0u), 8u * tw(n));
+            });
+        }
+    }
+};
+
 // ---- mergers ------------------------------------------------------------------------------------
 FGE_HD uint32_t dec_digits(uint64_t v) {
     uint32_t n = 1;
@@ -1387,6 +1868,9 @@ FGE_HD uint32_t encode_row(S& sink, const EncCfg& cfg, R rd, const DevTables& t,
         return em.run();
     } else if (ENC == FG_ENC_RFC3164) {
         Rfc3164Emitter<S, R> em(sink, cfg, rd, t, li, meta, pre);
+        return em.run();
+    } else if (ENC == FG_ENC_CAPNP) {
+        CapnpEmitter<S, R> em(sink, cfg, rd, t, li, meta, pre);
         return em.run();
     } else {
         PassthroughEmitter<S, R> em(sink, cfg, rd, t, li, meta, pre);

@@ -1,7 +1,9 @@
 // fg_enc_cfg.hpp -- host-side construction of the encoder kernels' configuration (EncCfg + its blob) from the
 // C ABI's fg_encode_cfg: what XEncoder::new(&Config) prepares once (encoder/gelf_encoder.rs:16-38,
-// ltsv_encoder.rs:11-30, mod.rs:58-79).  Header-only so that the CPU tests build the very same configuration.
+// ltsv_encoder.rs:11-30, capnp_encoder.rs:13-31, mod.rs:58-79).  Header-only so that the CPU tests build the very same configuration.
 #pragma once
+#include <string.h>
+
 #include <map>
 #include <string>
 #include <vector>
@@ -22,7 +24,7 @@ struct EncCfgHost {
 // suffix[k] / has_suffix[k]: the LTSV decoder's type suffixes (bool, f64, i64, u64).  Returns false on bad arguments.
 inline bool build_enc_cfg(fg_format src_fmt, const fg_encode_cfg* ec, const std::string suffix[4], const bool has_suffix[4],
                           EncCfgHost* out) {
-    if (!ec || (int)ec->encoder < 0 || (int)ec->encoder > (int)FG_ENC_PASSTHROUGH) return false;
+    if (!ec || (int)ec->encoder < 0 || (int)ec->encoder > (int)FG_ENC_CAPNP) return false;
     if ((int)ec->merger < 0 || (int)ec->merger > (int)FG_MERGE_SYSLEN) return false;
     if (ec->n_extra && (!ec->extra_keys || !ec->extra_values)) return false;
     for (uint32_t i = 0; i < ec->n_extra; ++i)
@@ -108,6 +110,31 @@ inline bool build_enc_cfg(fg_format src_fmt, const fg_encode_cfg* ec, const std:
             blob.push_back(':');
             for (const char* v = ec->extra_values[i]; *v; ++v) blob.push_back((uint8_t)(*v == '\n' || *v == '\t' ? ' ' : *v));
         }
+    }
+    if (ec->encoder == FG_ENC_CAPNP && ec->n_extra) {
+        // output.capnp_extra as the Record's `extra` list lands in every message: the tag word, n Pair structs (a string:
+        // discriminant 0, pointer 0 the key, pointer 1 the value), then key / value texts pair by pair (capnp_encoder.rs:98-106).
+        // Its pointers are relative, so the image is the same wherever the list goes (CapnpEmitter copies it as one piece).
+        while (blob.size() & 7u) blob.push_back(0);
+        cfg.ltsv_extra_off = (uint32_t)blob.size();
+        const uint32_t n = ec->n_extra;
+        std::vector<uint64_t> w(1u + 4u * n, 0u);
+        w[0] = (uint64_t)n << 2 | (uint64_t)(2u | 2u << 16) << 32;
+        std::vector<uint8_t> texts;
+        auto text = [&](const char* x, uint32_t ptr_word) {
+            const uint64_t len = strlen(x);
+            const uint64_t at = w.size() + texts.size() / 8u;  // the text's first word in the image
+            w[ptr_word] = 1u | (at - ptr_word - 1u) << 2 | (uint64_t)(2u | (len + 1u) << 3) << 32;
+            texts.insert(texts.end(), x, x + len);
+            texts.resize(texts.size() + 8u - len % 8u, 0);  // NUL + padding to a whole word
+        };
+        for (uint32_t i = 0; i < n; ++i) {
+            text(ec->extra_keys[i], 3u + 4u * i);
+            text(ec->extra_values[i], 4u + 4u * i);
+        }
+        for (uint64_t x : w)
+            for (int b = 0; b < 8; ++b) blob.push_back((uint8_t)(x >> (8 * b)));
+        blob.insert(blob.end(), texts.begin(), texts.end());
     }
     cfg.ltsv_extra_len = (uint32_t)blob.size() - cfg.ltsv_extra_off;
     align4(&blob);

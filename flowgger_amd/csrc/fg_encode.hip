@@ -1,5 +1,5 @@
 // fg_encode.hip -- gfx950 kernels for Encoder::encode + Merger::frame FROM THE DECODE TABLES:
-// GELF, LTSV, RFC5424, RFC3164 and passthrough encoders, line / nul / syslen mergers, for records decoded by any of
+// GELF, LTSV, RFC5424, RFC3164, passthrough and Cap'n Proto encoders, line / nul / syslen mergers, for records decoded by any of
 // the three decoders.  The per-record logic is fg_emit.hpp (host-tested against the oracle); this file is the launch
 // geometry around it.
 //
@@ -25,7 +25,7 @@
 #include "fg_emit.hpp"
 
 // Build: the emitters are large force-inlined templates, so this file is compiled once per kernel with
-// -DFG_ENC_TU=<FG_ENC_*> -DFG_ENC_TU_WRITE=<0|1> -DFG_ENC_TU_SLOTS=<n> (twelve objects, in parallel:
+// -DFG_ENC_TU=<FG_ENC_*> -DFG_ENC_TU_WRITE=<0|1> -DFG_ENC_TU_SLOTS=<n> (sixteen objects, in parallel:
 // flowgger_amd/build.py) and once without FG_ENC_TU for the scan kernels, the dispatcher and the C entry points.
 namespace fg {
 
@@ -232,6 +232,7 @@ static int launch_encode(FG_ENC_ARGS) {
         case FG_ENC_RFC5424: FG_CALL(FG_ENC_RFC5424, 0u);
         case FG_ENC_RFC3164: FG_CALL(FG_ENC_RFC3164, 0u);
         case FG_ENC_PASSTHROUGH: FG_CALL(FG_ENC_PASSTHROUGH, 0u);
+        case FG_ENC_CAPNP: FG_CALL(FG_ENC_CAPNP, 0u);
         default: return -1;
     }
 #undef FG_CALL

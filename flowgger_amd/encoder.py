@@ -2,10 +2,10 @@
 
 Reference: ``trait Encoder { fn encode(&self, record: Record) -> Result<Vec<u8>, &'static str> }``
 (src/flowgger/encoder/mod.rs:54-56) with GelfEncoder / LTSVEncoder / RFC5424Encoder / RFC3164Encoder /
-PassthroughEncoder, and ``trait Merger { fn frame(&self, bytes: &mut Vec<u8>) }`` (merger/mod.rs:30-32) with
+PassthroughEncoder / CapnpEncoder, and ``trait Merger { fn frame(&self, bytes: &mut Vec<u8>) }`` (merger/mod.rs:30-32) with
 LineMerger / NulMerger / SyslenMerger.  Here one call encodes AND frames a whole decoded batch on the GPU straight
 from the decode tables (fg_encode_device): the result is one contiguous byte stream in input order, which is what
-the outputs write.  Configuration keys are the reference's (output.gelf_extra, output.ltsv_extra,
+the outputs write.  Configuration keys are the reference's (output.gelf_extra, output.ltsv_extra, output.capnp_extra,
 output.syslog_prepend_timestamp -- the latter as the already formatted header, since it is the wall clock).
 There is no CPU fallback.
 """
@@ -17,7 +17,9 @@ from typing import Optional
 from . import _lib as L
 from .tables import DeviceTables
 
-MERGERS = {None: L.FG_MERGE_NONE, "none": L.FG_MERGE_NONE, "line": L.FG_MERGE_LINE, "nul": L.FG_MERGE_NUL, "syslen": L.FG_MERGE_SYSLEN}
+# output.framing (merger/mod.rs:447-456): "noop" / "nop" / "capnp" are NopMerger, i.e. no framing
+MERGERS = {None: L.FG_MERGE_NONE, "none": L.FG_MERGE_NONE, "noop": L.FG_MERGE_NONE, "nop": L.FG_MERGE_NONE, "capnp": L.FG_MERGE_NONE,
+           "line": L.FG_MERGE_LINE, "nul": L.FG_MERGE_NUL, "syslen": L.FG_MERGE_SYSLEN}
 
 
 class Encoder:
@@ -31,7 +33,7 @@ class Encoder:
         # the reference iterates a toml Table = BTreeMap: sorted by key
         self.extra = sorted((extra or {}).items())
         for k, v in self.extra:
-            if not isinstance(v, str):  # gelf_encoder.rs:27-29 / ltsv_encoder.rs:21-23
+            if not isinstance(v, str):  # gelf_encoder.rs:27-29 / ltsv_encoder.rs:21-23 / capnp_encoder.rs:23-25
                 raise TypeError(f"output.{self.extra_key} values must be strings")
         self.merger = MERGERS[merger if merger is not None else out.get("framing")]
         self.prepend = prepend
@@ -116,6 +118,10 @@ class RFC3164Encoder(Encoder):  # encoder/rfc3164_encoder.rs
 
 class PassthroughEncoder(Encoder):  # encoder/passthrough_encoder.rs
     enc = L.FG_ENC_PASSTHROUGH
+
+
+class CapnpEncoder(Encoder):  # encoder/capnp_encoder.rs: one Cap'n Proto message (record.capnp) per line
+    enc, extra_key = L.FG_ENC_CAPNP, "capnp_extra"
 
 
 class Transcoded:

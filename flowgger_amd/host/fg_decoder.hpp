@@ -829,7 +829,7 @@ class GpuFramingSplitter {
 struct EncoderConfig {
     fg_encoder encoder = FG_ENC_GELF;
     fg_merger merger = FG_MERGE_LINE;
-    std::map<std::string, std::string> extra;  // output.gelf_extra / output.ltsv_extra (a sorted table, like toml's)
+    std::map<std::string, std::string> extra;  // output.gelf_extra / ltsv_extra / capnp_extra (a sorted table, like toml's)
     std::optional<std::string> prepend;        // the formatted output.syslog_prepend_timestamp header
     double now_ts = 0.0;                       // ts of GELF records decoded without "timestamp" (gelf_decoder.rs:109)
 };

@@ -370,11 +370,15 @@ int fg_encode_gelf_device(fg_ctx* ctx, fg_format src_fmt, const uint8_t* d_bytes
  * apply to every message.  The encoded + framed bytes of line i are written to d_out[out_offsets[i] ..
  * out_offsets[i+1]); a line whose decode failed or whose encode returns Err produces nothing (the reference prints
  * the error and drops the line).  Records from all three decoders are accepted (GELF-sourced spans are JSON-unescaped
- * on the fly).  The capnp encoder is not provided.
- *   cfg->extra_*    output.gelf_extra (GELF) / output.ltsv_extra (LTSV) in the configuration table's iteration order
- *                   (a BTreeMap: sorted by key)
+ * on the fly).  FG_ENC_CAPNP (encoder/capnp_encoder.rs) writes one Cap'n Proto message per line, byte for byte what
+ * capnp::serialize::write_message writes for the Record the reference builds (schema record.capnp: segment table,
+ * root struct, texts in allocation order; records beyond the first segment's 1024 words span several segments).
+ * FG_ENC_CAPNP is an additive value under the same FG_ABI_VERSION: a library without it rejects it with FG_ERR_ARG.
+ *   cfg->extra_*    output.gelf_extra (GELF) / output.ltsv_extra (LTSV) / output.capnp_extra (capnp) in the
+ *                   configuration table's iteration order (a BTreeMap: sorted by key)
  *   cfg->prepend    RFC3164 / passthrough: the already formatted output.syslog_prepend_timestamp header (the
- *                   reference formats the wall clock per message, encoder/mod.rs:81-93); NULL = not configured
+ *                   reference formats the wall clock per message, encoder/mod.rs:81-93); NULL = not configured;
+ *                   ignored by the other encoders
  *   cfg->now_ts     Record.ts of GELF records decoded without "timestamp" (rows flagged FG_F_TS_NOW; the reference
  *                   reads the wall clock at decode time, gelf_decoder.rs:109)
  *   d_out_offsets   out, n + 1 entries (device)
@@ -383,7 +387,7 @@ int fg_encode_gelf_device(fg_ctx* ctx, fg_format src_fmt, const uint8_t* d_bytes
  *   total           out (host): bytes needed; the call synchronises the stream to read it
  *   d_out == NULL   sizing call (only d_out_offsets / d_enc_status / *total are produced);
  *   *total > out_cap -> FG_ERR_ENT_OVERFLOW, nothing written. */
-typedef enum fg_encoder { FG_ENC_GELF = 0, FG_ENC_LTSV = 1, FG_ENC_RFC5424 = 2, FG_ENC_RFC3164 = 3, FG_ENC_PASSTHROUGH = 4 } fg_encoder;
+typedef enum fg_encoder { FG_ENC_GELF = 0, FG_ENC_LTSV = 1, FG_ENC_RFC5424 = 2, FG_ENC_RFC3164 = 3, FG_ENC_PASSTHROUGH = 4, FG_ENC_CAPNP = 5 } fg_encoder;
 typedef enum fg_merger { FG_MERGE_NONE = 0, FG_MERGE_LINE = 1, FG_MERGE_NUL = 2, FG_MERGE_SYSLEN = 3 } fg_merger;
 typedef struct fg_encode_cfg {
     fg_encoder encoder;

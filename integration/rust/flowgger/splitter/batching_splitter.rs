@@ -5,7 +5,7 @@
 //!   * `run_decode`    raw chunk -> `fg_frame_decode_batch` (GPU framing + UTF-8 validation + decode); `Record`s are
 //!                     materialised on the host and go through the unchanged `Encoder` trait object (what `run` uses);
 //!   * `run_transcode` raw chunk -> `fg_transcode_batch` (framing + decode + encode + merger on the GPU): only the
-//!                     encoded, already framed bytes come back -- for the encoders libfg_hip provides (all but capnp).
+//!                     encoded, already framed bytes come back -- for all six encoders ("capnp" is FG_ENC_CAPNP).
 //! WHEN a batch goes to the GPU (the reference handles every line the moment `lines()` yields it, `line_splitter.rs:17`): when
 //! `max_bytes` have accumulated, or -- the usual case on a live connection -- when a read returns LESS than it could hold: the
 //! peer has nothing more in flight right now, so what has arrived is decoded now instead of waiting for a full chunk.  A read
