@@ -20,7 +20,8 @@ if _ALT and (Path(_ALT).name != _ALT or not _ALT.startswith("libfg_hip") or not 
 LIB_PATH = _HERE / (_ALT or ("libfg_hip_prof.so" if os.environ.get("FLOWGGER_AMD_PROF_LIB") else "libfg_hip.so"))
 
 FG_ABI_VERSION = 4  # include/fg_hip.h
-FG_RFC5424, FG_LTSV, FG_GELF, FG_RFC3164 = 0, 1, 2, 3
+FG_RFC5424, FG_LTSV, FG_GELF, FG_RFC3164, FG_CAPNP = 0, 1, 2, 3, 4
+FG_EF_VAL_ESC, FG_EF_NAME_ESC, FG_EF_SUFFIX, FG_EF_NAME_VERBATIM = 1, 2, 4, 8  # entry flags (include/fg_hip.h)
 FG_FRAME_NONE, FG_FRAME_LINE, FG_FRAME_NUL = 0, 1, 2
 FG_ST_OVERFLOW, FG_ST_BAD_UTF8 = 0xFE, 0xFD
 FG_F_LTSV_NOVALUE = 128  # meta flags bit (include/fg_hip.h)

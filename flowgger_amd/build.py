@@ -28,7 +28,7 @@ VARIANT_DEFS = os.environ.get("FG_BUILD_DEFS", "").split()
 LIB = ROOT / (f"libfg_hip_{VARIANT}.so" if VARIANT else "libfg_hip_prof.so" if PROF else "libfg_hip.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip"]
+HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip", "fg_capnp.hip"]
 HIP_HOST_SOURCES = ["fg_capi.cpp", "fg_host_pipeline.cpp"]  # host code that needs the HIP headers / launch syntax
 CXX_SOURCES = ["fg_materialize.cpp", "fg_gather.cpp"]
 
@@ -89,6 +89,7 @@ WORKLOAD_UNITS = {
     "cfg1": ["fg_rfc5424.hip", "fg_encode.hip", "fg_tile_cap.hpp"], "frame": ["fg_rfc5424.hip", "fg_frame.hip"],
     "cfg3": ["fg_gelf.hip"], "ltsv": ["fg_ltsv.hip"], "ltsv5": ["fg_ltsv.hip"],
     "rfc3164": ["fg_rfc3164.hip", "fg_tile_cap.hpp"],
+    "capnp": ["fg_capnp.hip"],
 }
 
 
@@ -234,6 +235,12 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         if verbose:
             print(" ".join(cmd))
         _run(cmd)
+        # fg_launch_capnp is a WEAK reference in fg_capi.cpp (csrc/fg_ctx.hpp says why): --no-undefined does not see a link that
+        # lost fg_capnp.hip.o, so the library is checked for the kernel's launcher here
+        syms = subprocess.run(["nm", "-D", "--defined-only", str(LIB)], capture_output=True, text=True).stdout
+        if " fg_launch_capnp" not in syms:
+            LIB.unlink()
+            raise RuntimeError("libfg_hip was linked without fg_launch_capnp (fg_capnp.hip)")
     if not PROF and not VARIANT:
         _write_deps_manifest()
     return LIB

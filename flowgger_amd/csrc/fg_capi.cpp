@@ -413,6 +413,7 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
                               const uint64_t* d_offsets, uint64_t n, const uint8_t* d_bad_utf8, const fg_tables* tables,
                               void* stream, bool reset_counter, uint64_t span_bytes, uint32_t lane) {
     if ((int)framing < 0 || (int)framing > 2) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP && framing != FG_FRAME_NONE) return FG_ERR_ARG;  // (a chain of length prefixes: framed on the host)
     if (!ctx || !tables || (n && (!d_offsets || !tables->meta))) return FG_ERR_ARG;
     if (nbytes && !d_bytes) return FG_ERR_ARG;
     if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;
@@ -500,6 +501,10 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
                                        d_bad_utf8, scratch, regroup);
             }
             break;
+        case FG_CAPNP:
+            if (!fg_launch_capnp) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernel: fg_ctx.hpp)
+            rc = fg_launch_capnp(d_bytes, d_offsets, n, &dt, avg_len, s, &lo_call, tk);
+            break;
         default:
             return FG_ERR_UNSUPPORTED;
     }
@@ -530,6 +535,7 @@ int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const u
                          uint64_t cap, const fg_tables* tables, uint64_t avg_line, void* stream, unsigned long long** d_total) {
     if (!ctx || !tables || !d_offsets || !d_total || (nbytes && !d_bytes)) return FG_ERR_ARG;
     if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP) return FG_ERR_ARG;
     if (((uintptr_t)d_bytes & 15u) != 0 || tables->n < cap || (cap && !tables->meta) || tables->ent_cap > 0xFFFFFFFFull) return FG_ERR_ARG;
     if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF) return FG_ERR_UNSUPPORTED;
     if (nbytes == 0 || cap == 0) return FG_ERR_UNSUPPORTED;
@@ -647,7 +653,7 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
     const bool async = total == nullptr;
     if (!ctx || !ecfg || !tables || !d_out_offsets || (n && (!d_offsets || !tables->meta))) return FG_ERR_ARG;
     if (async && !d_out) return FG_ERR_ARG;
-    if ((int)src_fmt < 0 || (int)src_fmt > (int)FG_RFC3164) return FG_ERR_ARG;
+    if ((int)src_fmt < 0 || (int)src_fmt > (int)FG_CAPNP) return FG_ERR_ARG;
     if (tables->n < n) return FG_ERR_ARG;
     if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;  // (the emitters' global reader loads aligned 16-byte chunks: as the decoders require)
     DeviceGuard g(ctx->device);
@@ -825,6 +831,9 @@ int fg_set_rfc3164(fg_ctx* ctx, const fg_rfc3164_cfg* cfg) {
     return upload_tz(ctx);
 }
 
+// capnp_splitter.rs:135,140; [3] has no counterpart: the reference unwrap()s get_root() (:47) and the connection thread panics
+const char* const kErrCapnp[] = {"", "Missing timestamp", "Missing host name", "Capnp decoding error: the root pointer cannot be read"};
+
 const char* fg_error_string(fg_format fmt, uint8_t status) {
     if (status == FG_ST_BAD_UTF8) return "Invalid UTF-8 input";  // line_splitter.rs:23, nul_splitter.rs:36
     switch (fmt) {
@@ -836,6 +845,8 @@ const char* fg_error_string(fg_format fmt, uint8_t status) {
             return status < sizeof(kErrGelf) / sizeof(*kErrGelf) ? kErrGelf[status] : nullptr;
         case FG_RFC3164:
             return status < sizeof(kErr3164) / sizeof(*kErr3164) ? kErr3164[status] : nullptr;
+        case FG_CAPNP:
+            return status < sizeof(kErrCapnp) / sizeof(*kErrCapnp) ? kErrCapnp[status] : nullptr;
     }
     return nullptr;
 }

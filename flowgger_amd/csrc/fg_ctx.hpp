@@ -41,6 +41,10 @@ extern "C" uint64_t fg_stash_bytes(uint32_t blocks);
 extern "C" int fg_launch_rfc3164(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t,
                                  const fg::r3164::Cfg* cfg, uint32_t tile_cap, hipStream_t stream, uint32_t strip,
                                  const uint8_t* line_bad, uint8_t* scratch, int regroup);
+// (a WEAK reference: the CPU suite links the host side of the C ABI against fake launchers -- tests/native/host_pipeline_fake.cpp --
+//  which have none for this format; FG_CAPNP then answers FG_ERR_UNSUPPORTED.  The product library always has the kernel.)
+extern "C" int fg_launch_capnp(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, uint64_t avg_len,
+                               hipStream_t stream, const fg_launch_opts* lo, fg::TicketSlot* tk) __attribute__((weak));
 extern "C" uint64_t fg_rfc3164_scratch_bytes(uint64_t n);
 extern "C" uint64_t fg_rfc3164_regroup_from(void);   // lines from which the library regroups by itself  // the regrouped form's scratch: shape keys, block counts, the line permutation
 extern "C" int fg_launch_encode_sizes(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t,

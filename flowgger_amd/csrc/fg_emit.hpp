@@ -692,10 +692,12 @@ struct Base {
         uint32_t skip;      // decoded bytes to skip: 1 when a GELF key already starts with '_'
         uint32_t dlen;      // decoded length after the skip
         uint32_t so, sl;    // suffix in the blob (sl = 0: none)
+        uint32_t pfx;       // 1: the Record key is '_' + these bytes; 0: the bytes alone -- an FG_CAPNP `extra` whose key starts
+                            //    with no '_' (FG_EF_NAME_VERBATIM, capnp_splitter.rs:104-108)
     };
     FGE_HD Dyn dyn_of(uint32_t e) {
         const fg_span nm = t.ent_name[e];
-        Dyn d{nm.off, nm.len, M_RAW, 0u, nm.len, 0u, 0u};
+        Dyn d{nm.off, nm.len, M_RAW, 0u, nm.len, 0u, 0u, 1u};
         const uint32_t ty = t.ent_type[e];
         const uint32_t ef = t.ent_flags[e];
         if (cfg.src_fmt == FG_GELF) {
@@ -711,6 +713,13 @@ struct Base {
             } else if (nm.len && rd.byte(nm.off) == '_') {
                 d.skip = 1;
                 d.dlen = nm.len - 1u;
+            }
+        } else if (cfg.src_fmt == FG_CAPNP) {  // the same rule (capnp_splitter.rs:80-87); spans are never escaped
+            if (nm.len && rd.byte(nm.off) == '_') {
+                d.skip = 1;
+                d.dlen = nm.len - 1u;
+            } else if (ef & FG_EF_NAME_VERBATIM) {
+                d.pfx = 0u;
             }
         }
         const uint32_t si = ty - FG_T_BOOL;
@@ -779,7 +788,8 @@ struct Base {
                 out.put('[');
                 open = true;
                 const fg_span id = t.ent_name[e];
-                for (uint32_t i = 0; i < id.len; ++i) out.put(rd.byte(id.off + i));
+                if (id.len != FG_NONE)  // (FG_CAPNP: sd_id None prints as "")
+                    for (uint32_t i = 0; i < id.len; ++i) out.put(rd.byte(id.off + i));
                 continue;
             }
             if (!open) {  // LTSV / GELF records: one element, sd_id None
@@ -874,7 +884,19 @@ struct GelfEmitter : Base<S, R> {
         }
         dtoa::write_pieces(d, out);  // digits in registers, as one piece or two where the shape allows (no char buffer: that would be scratch memory)
     }
+    // the FULL key (with its '_' where it has one): only FG_CAPNP rows hold keys without
+    FGE_HD uint32_t fk_len(const Dyn& d) const { return d.pfx + d.dlen + d.sl; }
+    FGE_HD uint32_t fk_byte(const Dyn& d, uint32_t k) { return (d.pfx && k == 0u) ? (uint32_t)'_' : this->dyn_byte(d, k - d.pfx); }
+    FGE_HD int cmp_full(const Dyn& a, const Dyn& b) {
+        const uint32_t la = fk_len(a), lb = fk_len(b), n = la < lb ? la : lb;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t x = fk_byte(a, k), y = fk_byte(b, k);
+            if (x != y) return x < y ? -1 : 1;
+        }
+        return la == lb ? 0 : (la < lb ? -1 : 1);
+    }
     FGE_HD int cmp_dyn(const Dyn& a, const Dyn& b) {
+        if (!(a.pfx & b.pfx)) return cmp_full(a, b);
         const uint32_t la = a.dlen + a.sl, lb = b.dlen + b.sl, n = la < lb ? la : lb;
         for (uint32_t k = 0; k < n; ++k) {
             const uint32_t x = this->dyn_byte(a, k), y = this->dyn_byte(b, k);
@@ -885,6 +907,14 @@ struct GelfEmitter : Base<S, R> {
     // full key ('_' + ...) against a static key
     FGE_HD int cmp_dyn_static(const Dyn& a, const StaticKey& s) {
         if (s.key_len == 0) return 1;
+        if (!a.pfx) {  // a key without '_': byte by byte
+            const uint32_t la = fk_len(a), lb = s.key_len, n = la < lb ? la : lb;
+            for (uint32_t k = 0; k < n; ++k) {
+                const uint32_t x = this->dyn_byte(a, k), y = cfg.blob[s.key_off + k];
+                if (x != y) return x < y ? -1 : 1;
+            }
+            return la == lb ? 0 : (la < lb ? -1 : 1);
+        }
         const uint32_t s0 = cfg.blob[s.key_off];
         if (s0 != '_') return '_' < s0 ? -1 : 1;
         const uint32_t la = a.dlen + a.sl, lb = s.key_len - 1u, n = la < lb ? la : lb;
@@ -898,7 +928,7 @@ struct GelfEmitter : Base<S, R> {
         const Dyn d = this->dyn_of(e);
         member_start();
         out.put('"');
-        out.put('_');
+        if (d.pfx) out.put('_');
         this->dyn_stream(d, [&](uint32_t c) { esc_byte(c); });
         out.put('"');
         out.put(':');
@@ -927,7 +957,7 @@ struct GelfEmitter : Base<S, R> {
             case SK_FULL: if (!this->some(S_FULL)) return; break;
             case SK_PROC: if (!this->some(S_PROC)) return; break;
             case SK_LEVEL: if (FG_META_SEVERITY(meta) == 0xFFu) return; break;
-            case SK_SDID: if (sdid_entry == 0xFFFFFFFFu) return; break;
+            case SK_SDID: if (sdid_entry == 0xFFFFFFFFu || t.ent_name[sdid_entry].len == FG_NONE) return; break;
             default: break;
         }
         key_static(k);
@@ -981,7 +1011,11 @@ struct GelfEmitter : Base<S, R> {
             if (np < cfg.sort_slots && ranked) {
                 const Dyn d = this->dyn_of(e);
                 uint64_t pre = 0;
-                for (uint32_t k = 0; k < 7u; ++k) pre = (pre << 8) | (k < d.dlen + d.sl ? this->dyn_byte(d, k) : 0u);
+                if (cfg.src_fmt == FG_CAPNP) {  // (keys with and without '_' in one row: the prefix of the FULL key)
+                    for (uint32_t k = 0; k < 7u; ++k) pre = (pre << 8) | (k < fk_len(d) ? fk_byte(d, k) : 0u);
+                } else {
+                    for (uint32_t k = 0; k < 7u; ++k) pre = (pre << 8) | (k < d.dlen + d.sl ? this->dyn_byte(d, k) : 0u);
+                }
                 keys64[np] = (pre << 8) | np;  // 7 key bytes big-endian, then the slot: equal keys keep insertion order
                 slot_ent[np] = (uint8_t)(e - first);
             } else {
@@ -1038,7 +1072,16 @@ struct GelfEmitter : Base<S, R> {
                 if (e != kNone) {
                     const int c = cmp_dyn_static(d, cfg.keys[sk]);
                     if (c < 0) break;
-                    if (c == 0) shadowed = true;
+                    if (c == 0) {
+                        // gelf_extra is inserted last and replaces the pair; a fixed member ("host", "sd_id" ...) is inserted FIRST, so a
+                        // pair of that name -- only an FG_CAPNP extra can have one -- replaces IT (gelf_encoder.rs:60-110)
+                        if (cfg.keys[sk].kind == SK_EXTRA) {
+                            shadowed = true;
+                        } else {
+                            ++sk;
+                            continue;
+                        }
+                    }
                 }
                 emit_static(cfg.keys[sk], sdid_entry);
                 ++sk;
@@ -1458,7 +1501,7 @@ struct CapnpEmitter : Base<S, R> {
     }
     FGE_HD uint32_t key_len(uint32_t e) {  // '_' + name [+ LTSV suffix]
         const Dyn d = this->dyn_of(e);
-        return 1u + d.dlen + d.sl;
+        return d.pfx + d.dlen + d.sl;
     }
     FGE_HD uint32_t val_len(uint32_t e) {
         const uint64_t v = t.ent_val[e];
@@ -1470,7 +1513,10 @@ struct CapnpEmitter : Base<S, R> {
         const uint32_t end = this->row_ef + this->row_ec;
         uint32_t e = this->row_ef;
         sdid = kCapnpNone;
-        if (cfg.src_fmt == FG_RFC5424 && e < end && t.ent_type[e] == FG_T_SDID) sdid = e++;  // (other sources: one element, sd_id None)
+        if ((cfg.src_fmt == FG_RFC5424 || cfg.src_fmt == FG_CAPNP) && e < end && t.ent_type[e] == FG_T_SDID) {  // (other sources: one element, sd_id None)
+            sdid = e++;
+            if (t.ent_name[sdid].len == FG_NONE) sdid = kCapnpNone;  // (FG_CAPNP: the element of a message whose sd_id getter failed)
+        }
         lo = e;
         while (e < end && t.ent_type[e] != FG_T_SDID) ++e;
         hi = e;
@@ -1531,14 +1577,14 @@ struct CapnpEmitter : Base<S, R> {
     }
     FGE_HD void key_text(uint32_t e) {
         const Dyn d = this->dyn_of(e);
-        out.put('_');
+        if (d.pfx) out.put('_');
         if (d.mode == M_RAW) {
             raw_bytes(d.off + d.skip, d.dlen);
             for (uint32_t i = 0; i < d.sl; ++i) out.put((uint32_t)cfg.blob[d.so + i]);
         } else {
             this->dyn_stream(d, [&](uint32_t c) { out.put(c); });
         }
-        pad(1u + d.dlen + d.sl);
+        pad(d.pfx + d.dlen + d.sl);
     }
     FGE_HD void val_text(uint32_t e) {
         const uint64_t v = t.ent_val[e];

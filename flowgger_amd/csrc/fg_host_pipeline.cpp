@@ -353,6 +353,9 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
                     uint64_t n, fg_tables* out) {
     if (!ctx || !out || (n && !offsets) || (nbytes && !bytes)) return FG_ERR_ARG;
     if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP)  // a message is an array of 8-byte words (include/fg_hip.h)
+        for (uint64_t i = 0; i <= n && n; ++i)
+            if (offsets[i] & 7u) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
     int rc;
     if ((rc = decode_batch_zero_copy(ctx, fmt, bytes, nbytes, offsets, n, out)) != FG_ERR_UNSUPPORTED) return rc;
@@ -516,6 +519,7 @@ static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int fin
 static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
                                   fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
     if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_UNSUPPORTED;
     *n_frames = 0;
     *consumed = 0;
@@ -1207,9 +1211,13 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
                        uint64_t nbytes, const uint64_t* offsets, uint64_t n, int final, fg_transcoded* out) {
     if (!ctx || !ecfg || !out || (nbytes && !bytes)) return FG_ERR_ARG;
     if ((int)framing < 0 || (int)framing > 2) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP && framing != FG_FRAME_NONE) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
     if (framing == FG_FRAME_NONE) {
         if (n && !offsets) return FG_ERR_ARG;
         if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
+        if (fmt == FG_CAPNP)  // a message is an array of 8-byte words (include/fg_hip.h)
+            for (uint64_t i = 0; i <= n && n; ++i)
+                if (offsets[i] & 7u) return FG_ERR_ARG;
     } else if (offsets) {
         return FG_ERR_ARG;  // a raw stream chunk is framed here; it does not come with offsets
     }

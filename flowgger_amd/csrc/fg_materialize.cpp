@@ -153,7 +153,7 @@ extern "C" int64_t fg_tables_serialize(fg_format fmt, const fg_cfg* cfg, const u
                                        const fg_tables* t, uint64_t i0, uint64_t i1, uint8_t* out, uint64_t cap,
                                        uint64_t* out_offsets) {
     if (!t || !offsets || i1 < i0 || i1 > t->n) return FG_ERR_ARG;
-    if ((int)fmt < 0 || (int)fmt > (int)FG_RFC3164) return FG_ERR_ARG;
+    if ((int)fmt < 0 || (int)fmt > (int)FG_CAPNP) return FG_ERR_ARG;
     Sink k{out, cap};
     std::string tmp;
     const char* suffix[6] = {nullptr, cfg ? cfg->suffix_bool : nullptr, cfg ? cfg->suffix_f64 : nullptr,
@@ -211,7 +211,7 @@ extern "C" int64_t fg_tables_serialize(fg_format fmt, const fg_cfg* cfg, const u
         k.u32(0);
         uint32_t n_sd = 0, n_pairs = 0;
         uint64_t n_pairs_at = 0;
-        if (fmt != FG_RFC5424) {  // one element, sd_id None (ltsv_decoder.rs:88,215; gelf_decoder.rs:35,119)
+        if (fmt != FG_RFC5424 && fmt != FG_CAPNP) {  // one element, sd_id None (ltsv_decoder.rs:88,215; gelf_decoder.rs:35,119)
             n_sd = 1;
             k.u8(0);
             n_pairs_at = k.n;
@@ -224,9 +224,13 @@ extern "C" int64_t fg_tables_serialize(fg_format fmt, const fg_cfg* cfg, const u
                 if (n_sd) k.patch32(n_pairs_at, n_pairs);
                 ++n_sd;
                 n_pairs = 0;
-                k.u8(1);
-                k.u32(nm.len);
-                k.put(line + nm.off, nm.len);
+                if (nm.len == FG_NONE) {  // FG_CAPNP: the element of a message whose sd_id getter failed (capnp_splitter.rs:118)
+                    k.u8(0);
+                } else {
+                    k.u8(1);
+                    k.u32(nm.len);
+                    k.put(line + nm.off, nm.len);
+                }
                 n_pairs_at = k.n;
                 k.u32(0);
                 continue;
@@ -242,7 +246,8 @@ extern "C" int64_t fg_tables_serialize(fg_format fmt, const fg_cfg* cfg, const u
             } else {
                 key.assign((const char*)np, nl);
             }
-            if (fmt != FG_GELF || key.empty() || key[0] != '_') key.insert(key.begin(), '_');
+            // (FG_CAPNP: the GELF rule for the pairs, capnp_splitter.rs:80-87; the extras' keys as they are, :104-108)
+            if (!(ef & FG_EF_NAME_VERBATIM) && ((fmt != FG_GELF && fmt != FG_CAPNP) || key.empty() || key[0] != '_')) key.insert(key.begin(), '_');
             if ((ef & FG_EF_SUFFIX) && ty <= FG_T_U64 && suffix[ty]) key += suffix[ty];
             k.u32((uint32_t)key.size());
             k.put(key.data(), key.size());

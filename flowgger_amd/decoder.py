@@ -254,6 +254,147 @@ class GelfDecoder(Decoder):
     fmt = L.FG_GELF
 
 
+def pack_messages(messages: Iterable[bytes]) -> Tuple[np.ndarray, np.ndarray]:
+    """The container of an FG_CAPNP batch: whole Cap'n Proto messages (segment table included) -> (packed bytes, offsets[n+1]).
+    A message is an array of 8-byte words and starts on one (include/fg_hip.h): a message whose length is no whole number of words
+    is refused (ValueError), as the C ABI refuses offsets that are no multiples of 8."""
+    bl = [bytes(m) for m in messages]
+    for i, b in enumerate(bl):
+        if len(b) & 7:
+            raise ValueError(f"message {i}: {len(b)} bytes is not a whole number of 8-byte words")
+    offsets = np.zeros(len(bl) + 1, np.uint64)
+    if bl:
+        offsets[1:] = np.cumsum([len(b) for b in bl], dtype=np.uint64)
+    data = np.frombuffer(b"".join(bl), np.uint8).copy() if bl else np.zeros(0, np.uint8)
+    return data, offsets
+
+
+class CapnpStreamError(Exception):
+    """capnp::serialize::read_message failed: the reference prints "Capnp decoding error: ..." and ends the connection
+    (splitter/capnp_splitter.rs:26-31).  `offsets` / `consumed`: the whole messages in front of the bad table, which the reference
+    has handled by then."""
+
+    def __init__(self, text: str, offsets=None, consumed: int = 0):
+        super().__init__(text)
+        self.offsets = np.zeros(1, np.uint64) if offsets is None else offsets
+        self.consumed = consumed
+
+
+class CapnpFramer:
+    """The framing half of CapnpSplitter::run (splitter/capnp_splitter.rs:24-46): a Cap'n Proto stream is a chain of length
+    prefixes -- message k + 1 starts where the segment table of message k says -- so the walk stays on the host and reads one
+    table per message.  ``feed(chunk)`` returns the whole messages now available as (packed bytes, offsets) for
+    :meth:`CapnpDecoder.decode_packed`; an incomplete last message is carried over to the next call.  The two conditions under
+    which capnp 0.14's ``read_message`` (default ``ReaderOptions``) ends the connection raise :class:`CapnpStreamError`:
+    512 or more segments, more than 8 Mi words in total."""
+
+    MAX_SEGMENTS = 512
+    MAX_WORDS = 8 << 20
+
+    def __init__(self):
+        self._carry = b""
+        self._ended = None  # the CapnpStreamError that ended the connection
+
+    @classmethod
+    def frame(cls, buf: Union[bytes, memoryview]) -> Tuple[np.ndarray, int]:
+        """(offsets of the whole messages at the front of `buf`, bytes they cover)"""
+        import struct
+
+        mv = memoryview(buf)
+        offs, p, n_buf = [0], 0, len(mv)
+        while n_buf - p >= 8:
+            n = struct.unpack_from("<I", mv, p)[0] + 1
+            if n >= cls.MAX_SEGMENTS:
+                raise CapnpStreamError(f"Too many segments: {n}", np.array(offs, np.uint64), p)
+            table = (4 + 4 * n + 7) // 8 * 8
+            if n_buf - p < table:
+                break
+            words = sum(struct.unpack_from(f"<{n}I", mv, p + 4))
+            if words > cls.MAX_WORDS:
+                raise CapnpStreamError(f"Message has {words} words, which is too large", np.array(offs, np.uint64), p)
+            if n_buf - p < table + 8 * words:
+                break
+            p += table + 8 * words
+            offs.append(p)
+        return np.array(offs, np.uint64), p
+
+    def feed(self, chunk: bytes) -> Tuple[np.ndarray, np.ndarray]:
+        if self._ended is not None:
+            raise self._ended
+        buf = self._carry + bytes(chunk)
+        try:
+            offsets, consumed = self.frame(buf)
+        except CapnpStreamError as e:
+            # the whole messages in front of the bad table are handled first (capnp_splitter.rs:24-60): they are returned now and
+            # the error is raised by the next call -- at once when there are none
+            self._ended = e
+            if len(e.offsets) < 2:
+                raise
+            offsets, consumed = e.offsets, e.consumed
+        self._carry = buf[consumed:]
+        return np.frombuffer(buf[:consumed], np.uint8).copy(), offsets
+
+    @property
+    def pending(self) -> int:
+        """bytes of an incomplete message carried over"""
+        return len(self._carry)
+
+
+class CapnpDecoder(Decoder):
+    """handle_message of src/flowgger/splitter/capnp_splitter.rs:65-167 (input.format = "capnp"; the reference has no Decoder for
+    it: the splitter reads Records off the wire itself).  A "line" is one whole message, segment table included."""
+    fmt = L.FG_CAPNP
+
+    def decode_batch(self, lines: Sequence[bytes]) -> List[Union[Record, DecodeError]]:
+        data, offsets = pack_messages(lines)
+        tab = self.decode_packed(data, offsets)
+        blob, offs = tab.serialize(self.fmt, data, offsets)
+        raw = blob.tobytes()
+        return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(len(lines))]
+
+
+class CapnpSplitter:
+    """CapnpSplitter::run (splitter/capnp_splitter.rs:15-63) without the encoder: chunks of the stream in, Records (or the
+    DecodeError the reference prints) out, in stream order."""
+
+    def __init__(self, decoder: Optional[CapnpDecoder] = None, device: int = 0):
+        self.decoder = decoder or CapnpDecoder(device=device)
+        self.framer = CapnpFramer()
+
+    def feed(self, chunk: bytes) -> List[Union[Record, DecodeError]]:
+        data, offsets = self.framer.feed(chunk)
+        n = len(offsets) - 1
+        if n == 0:
+            return []
+        tab = self.decoder.decode_packed(data, offsets)
+        blob, offs = tab.serialize(L.FG_CAPNP, data, offsets)
+        raw = blob.tobytes()
+        return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
+
+
+class CapnpTranscodingSplitter:
+    """CapnpSplitter::run (splitter/capnp_splitter.rs:15-63) WITH the encoder: chunks of the stream in, the re-encoded + framed
+    messages out.  handle_message + encoder.encode + the merger for every whole message of a chunk is one fg_transcode_batch
+    (FG_CAPNP, FG_FRAME_NONE); the tables never leave the device.  ``feed`` returns a :class:`~flowgger_amd.encoder.Transcoded`
+    (``.out`` the bytes for the output, ``.dec_status`` / ``.enc_status`` what the reference prints per dropped message)."""
+
+    def __init__(self, encoder, decoder: Optional[CapnpDecoder] = None, device: int = 0, now_ts: float = 0.0):
+        from .encoder import Pipeline
+
+        self.decoder = decoder or CapnpDecoder(device=device)
+        self.pipeline = Pipeline(self.decoder, encoder)
+        self.framer = CapnpFramer()
+        self.now_ts = now_ts
+
+    def feed(self, chunk: bytes):
+        from .encoder import Transcoded
+
+        data, offsets = self.framer.feed(chunk)
+        if len(offsets) < 2:  # no whole message yet
+            return Transcoded(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), None, 0)
+        return self.pipeline.run_packed(data, offsets, now_ts=self.now_ts)
+
+
 class RFC3164Decoder(Decoder):
     """src/flowgger/decoder/rfc3164_decoder.rs:10-213.  The reference's config is ignored (:13-15); two things it takes
     from its environment are explicit here: ``current_year`` (it reads the clock per parse, :179; default

@@ -282,6 +282,71 @@ class RFC3164Decoder : public Decoder {  // decoder/rfc3164_decoder.rs:14-213
     RFC3164Decoder(const RFC3164Decoder& o, int) : Decoder(o, 0) {}
 };
 
+class CapnpDecoder : public Decoder {  // handle_message of splitter/capnp_splitter.rs:65-167: a "line" is one whole message
+  public:
+    explicit CapnpDecoder(int device = 0) : Decoder(FG_CAPNP, device, nullptr) {}
+    std::unique_ptr<Decoder> clone_boxed() const override { return std::unique_ptr<Decoder>(new CapnpDecoder(*this, 0)); }
+  private:
+    CapnpDecoder(const CapnpDecoder& o, int) : Decoder(o, 0) {}
+};
+
+// The framing half of CapnpSplitter::run (splitter/capnp_splitter.rs:24-46, capnp::serialize::read_message): a Cap'n Proto stream is
+// a chain of length prefixes -- message k + 1 starts where the segment table of message k says -- so the walk stays on the host, like
+// syslen, and reads one table per message.  frame(): the whole messages at the front of buf[0 .. n) -> their offsets (offsets.size()
+// - 1 messages, all multiples of 8 from a buffer that starts at a message) and the bytes they cover; the caller carries the rest
+// over.  The two conditions under which capnp 0.14's read_message (default ReaderOptions) ends the connection are reported as such.
+struct CapnpFramer {
+    enum Status { Ok = 0, TooManySegments = 1, TooLarge = 2 };  // "Capnp decoding error: ..." + return (:28-31)
+    static constexpr uint64_t kMaxSegments = 512, kMaxWords = 8ull << 20;
+    static Status frame(const uint8_t* buf, uint64_t n, std::vector<uint64_t>* offsets, uint64_t* consumed) {
+        uint64_t p = 0;
+        offsets->assign(1, 0);
+        *consumed = 0;
+        while (n - p >= 8) {
+            uint32_t n1;
+            memcpy(&n1, buf + p, 4);
+            const uint64_t segs = (uint64_t)n1 + 1;
+            if (segs >= kMaxSegments) return TooManySegments;
+            const uint64_t table = (4 + 4 * segs + 7) / 8 * 8;
+            if (n - p < table) break;
+            uint64_t words = 0;
+            for (uint64_t k = 0; k < segs; ++k) {
+                uint32_t w;
+                memcpy(&w, buf + p + 4 + 4 * k, 4);
+                words += w;
+            }
+            if (words > kMaxWords) return TooLarge;
+            if (n - p < table + 8 * words) break;
+            p += table + 8 * words;
+            offsets->push_back(p);
+            *consumed = p;
+        }
+        return Ok;
+    }
+    // The carry-over form: feed() appends a chunk of the stream and frames what is whole; bytes() / offsets() are the batch for
+    // fg_decode_batch / fg_transcode_batch (FG_CAPNP, FG_FRAME_NONE); consume() drops the batch and keeps the incomplete tail.  A
+    // status other than Ok is returned TOGETHER with the whole messages in front of the bad table: the reference handles those
+    // first and ends the connection afterwards (capnp_splitter.rs:24-60).
+    Status feed(const uint8_t* chunk, uint64_t n) {
+        buf_.insert(buf_.end(), chunk, chunk + n);
+        return frame(buf_.data(), buf_.size(), &offs_, &consumed_);
+    }
+    const uint8_t* bytes() const { return buf_.data(); }
+    uint64_t nbytes() const { return consumed_; }
+    const std::vector<uint64_t>& offsets() const { return offs_; }
+    uint64_t messages() const { return offs_.size() - 1; }
+    uint64_t pending() const { return buf_.size() - consumed_; }
+    void consume() {
+        buf_.erase(buf_.begin(), buf_.begin() + (std::ptrdiff_t)consumed_);
+        offs_.assign(1, 0);
+        consumed_ = 0;
+    }
+  private:
+    std::vector<uint8_t> buf_;
+    std::vector<uint64_t> offs_{0};
+    uint64_t consumed_ = 0;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Batching framers: same framing and error reporting as the reference splitters, one
 // decode_batch per `max_lines` / `max_bytes` instead of one decode per line.
@@ -978,6 +1043,62 @@ class TranscodingSplitter {
         }
     }
     Framing f_;
+    EncoderConfig enc_;
+    size_t chunk_;
+};
+
+// CapnpSplitter::run (splitter/capnp_splitter.rs:15-63) beside the splitters above: the stream is framed on the host (CapnpFramer), and
+// handle_message + encoder.encode + the merger for every whole message of a chunk is ONE fg_transcode_batch(FG_CAPNP, FG_FRAME_NONE).
+// `out` receives the re-encoded messages in stream order; `err` what the reference prints: the handle_message / encoder error of a
+// dropped message (:48-58) and "Capnp decoding error: ..." when read_message ends the connection (:28-31; the text behind the colon
+// is capnp 0.14's and unpinned) -- after the messages in front of it have been handled.
+class CapnpTranscodingSplitter {
+  public:
+    explicit CapnpTranscodingSplitter(EncoderConfig enc, size_t chunk_bytes = 8u << 20) : enc_(std::move(enc)), chunk_(chunk_bytes) {}
+    void run(std::istream& in, const Decoder& d, std::ostream& out, std::ostream& err) {
+        std::vector<const char*> ks, vs;
+        for (auto& kv : enc_.extra) { ks.push_back(kv.first.c_str()); vs.push_back(kv.second.c_str()); }
+        fg_encode_cfg ec{};
+        ec.encoder = enc_.encoder;
+        ec.merger = enc_.merger;
+        ec.n_extra = (uint32_t)ks.size();
+        ec.extra_keys = ks.data();
+        ec.extra_values = vs.data();
+        ec.prepend = enc_.prepend ? enc_.prepend->c_str() : nullptr;
+        ec.now_ts = enc_.now_ts;
+        CapnpFramer fr;
+        std::vector<uint8_t> chunk(chunk_), batch;
+        for (;;) {
+            in.read((char*)chunk.data(), (std::streamsize)chunk.size());
+            const uint64_t got = (uint64_t)in.gcount();
+            const CapnpFramer::Status st = fr.feed(chunk.data(), got);
+            if (fr.messages()) {
+                batch.assign(fr.bytes(), fr.bytes() + fr.nbytes());
+                batch.resize(fr.nbytes() + 16);  // readable slack
+                fg_transcoded r{};
+                const int rc = fg_transcode_batch(d.ctx(), FG_CAPNP, FG_FRAME_NONE, &ec, batch.data(), fr.nbytes(), fr.offsets().data(), fr.messages(), 1, &r);
+                if (rc != FG_OK) throw std::runtime_error("fg_transcode_batch failed: " + std::to_string(rc));
+                if (r.out_bytes) {
+                    out.write((const char*)r.out, (std::streamsize)r.out_bytes);
+                    out.flush();
+                }
+                for (uint64_t i = 0; i < r.n; ++i) {
+                    const uint8_t ds = FG_META_STATUS(r.meta[i]), es = r.enc_status[i];
+                    if (ds == 0 && es == 0) continue;
+                    const char* msg = ds ? fg_error_string(FG_CAPNP, ds) : fg_encode_error_string(es);
+                    err << (msg ? msg : "?") << "\n";  // :50, :57
+                }
+            }
+            fr.consume();
+            if (st == CapnpFramer::TooManySegments) { err << "Capnp decoding error: Too many segments\n"; return; }
+            if (st == CapnpFramer::TooLarge) { err << "Capnp decoding error: Message is too large\n"; return; }
+            if (got == 0 || !in) {  // read_message at the end of the stream (whole messages or not): Failed, the loop ends (:28-31)
+                err << "Capnp decoding error: Premature end of file\n";
+                return;
+            }
+        }
+    }
+  private:
     EncoderConfig enc_;
     size_t chunk_;
 };

@@ -33,7 +33,16 @@ extern "C" {
 
 #define FG_ABI_VERSION 4 /* 4 (round 6): fg_frame_decode_device (framing inside the decode kernels), FG_LO_NO_FUSED_FRAMING, fg_launch_opts.fused_look / fused_ext (the struct grew), fg_last_host_path; 3 (round 5): fg_launch_opts.ent_chunk (the struct grew), FG_LO_STATIC_CHUNKS / _FRAME_SELFTEST_STALL, fg_ticket_ring_check; 2 (round 4): FG_YEAR_NOW = INT32_MIN, FG_F_LTSV_NOVALUE and the failed-LTSV-row count, ent_used = RESERVED slots, fg_calibrate_device */
 
-typedef enum fg_format { FG_RFC5424 = 0, FG_LTSV = 1, FG_GELF = 2, FG_RFC3164 = 3 } fg_format;
+/* FG_CAPNP (input.format = "capnp", splitter/capnp_splitter.rs:65-167): a "line" of the batch is ONE WHOLE Cap'n Proto message
+ * INCLUDING its segment table; offsets[i] must be multiples of 8 (a message is an array of 8-byte words; the host-buffer entry
+ * points answer FG_ERR_ARG otherwise, fg_decode_batch_device -- whose offsets live on the device -- gives such a row status 3);
+ * spans are relative to offsets[i] as for every other format.  Only FG_FRAME_NONE is valid with it: a capnp stream is a chain
+ * of length prefixes and is framed on the host (flowgger_amd/host/fg_decoder.hpp CapnpFramer).  FG_CAPNP is an additive value
+ * under the same FG_ABI_VERSION: a library without it rejects it with FG_ERR_ARG / FG_ERR_UNSUPPORTED.  All six encoders and the
+ * mergers take FG_CAPNP tables (fg_encode_device, fg_encode_device_async, fg_transcode_batch with FG_FRAME_NONE): the relay's
+ * handle_message + encoder.encode (capnp_splitter.rs:47-60) is one fg_transcode_batch.  The passthrough encoder emits the
+ * message's full_msg text, not the message. */
+typedef enum fg_format { FG_RFC5424 = 0, FG_LTSV = 1, FG_GELF = 2, FG_RFC3164 = 3, FG_CAPNP = 4 } fg_format;
 
 /* return codes */
 enum {
@@ -97,7 +106,10 @@ typedef enum fg_framing {
 enum {
     FG_EF_VAL_ESC = 1,   /* value span needs unescaping: RFC5424 \" \\ \] (rfc5424_decoder.rs:105-125) or JSON escapes (GELF) */
     FG_EF_NAME_ESC = 2,  /* GELF: key span holds JSON escapes */
-    FG_EF_SUFFIX = 4     /* LTSV: append the configured type suffix to the name (ltsv_decoder.rs:131-136) */
+    FG_EF_SUFFIX = 4,    /* LTSV: append the configured type suffix to the name (ltsv_decoder.rs:131-136) */
+    FG_EF_NAME_VERBATIM = 8 /* FG_CAPNP: the Record key is the name span as it is -- the `extra` pairs (capnp_splitter.rs:104-108);
+                               every other FG_CAPNP name gets a leading '_' unless the span starts with one (:80-87), the rule of
+                               the GELF rows */
 };
 
 /* One entry = one (name, SDValue) pair or one SD-element header, 18 bytes as SoA:
@@ -105,6 +117,11 @@ enum {
  *   ent_val[k]   String: span packed as off | (uint64)len<<32 ; Bool: 0/1 ; F64: IEEE bits ;
  *                I64: two's complement ; U64: value ; Null/SDID: 0
  *   ent_type[k]  FG_T_*      ent_flags[k]  FG_EF_*
+ * LTSV / GELF rows have ONE element without an id and no FG_T_SDID entry: their entries are its pairs.  An FG_CAPNP row whose
+ * Record.sd is Some opens with ONE FG_T_SDID entry -- its name span has len == FG_NONE when sd_id is None (malformed messages
+ * only; a null pointer is Some("") = a span of length 0) -- followed by the kept pairs, then the kept extras; ent_count == 0 is
+ * sd == None.  (The element needs its entry even without an id: Some([{None, []}]) and None are different Records.)  An optional
+ * text of an FG_CAPNP row that is None (its getter failed) is a span with len == FG_NONE.
  * Line i owns entries [ent_first[i], ent_first[i]+ent_count[i]) in decoder order.  Slices of
  * different lines may appear in any order inside the entry table (wave-level allocation). */
 typedef struct fg_tables {
@@ -478,7 +495,11 @@ enum { FG_CALIB_COPY = 0, FG_CALIB_READ = 1,
        FG_CALIB_COPY_FLAT = 3 /* the copy as one 16-byte element per thread (no grid-stride loop) */ };
 int fg_calibrate_device(fg_ctx* ctx, int mode, const uint8_t* d_src, uint8_t* d_dst, uint64_t nbytes, void* stream);
 
-/* The reference's exact &'static str for a status code of a format (0 -> "", unknown -> NULL). */
+/* The reference's exact &'static str for a status code of a format (0 -> "", unknown -> NULL).
+ * FG_CAPNP: 1 "Missing timestamp", 2 "Missing host name" (capnp_splitter.rs:135,140); 3 = the root pointer cannot be read (no
+ * segment 0, a root that is not a struct pointer or points outside its segment, 512 or more segments, a message of 4 GiB or
+ * more): the reference unwrap()s get_root() (:47), panics and loses the connection thread -- there is no &'static str, the text
+ * is this library's own. */
 const char* fg_error_string(fg_format fmt, uint8_t status);
 
 /* Materialise rows [i0, i1) of HOST-visible tables into the canonical Record serialisation
