@@ -94,6 +94,7 @@ extern "C" {
 
 int fg_abi_version(void) { return FG_ABI_VERSION; }
 int fg_last_host_path(const fg_ctx* ctx) { return ctx ? ctx->last_host_path : 0; }
+int fg_last_syslen_stop(const fg_ctx* ctx) { return ctx ? ctx->last_syslen_stop : 0; }
 
 int fg_tables_layout(uint64_t n, uint64_t ent_cap, uint64_t sizes[FG_TABLE_ARRAYS]) {
     if (!sizes) return FG_ERR_ARG;
@@ -244,6 +245,8 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_fused) (void)hipFree(ctx->d_fused);
     if (ctx->d_r3164) (void)hipFree(ctx->d_r3164);
     if (ctx->d_bad) (void)hipFree(ctx->d_bad);
+    if (ctx->d_sl_packed) (void)hipFree(ctx->d_sl_packed);
+    if (ctx->d_sl_starts) (void)hipFree(ctx->d_sl_starts);
     if (ctx->d_enc) (void)hipFree(ctx->d_enc);
     if (ctx->h_enc_ring) (void)hipHostFree(ctx->h_enc_ring);
     for (hipEvent_t e : ctx->ev_enc)
@@ -396,6 +399,41 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     FG_HIP(ctx, hipMemcpyAsync(&last_end, d_offsets + total, 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
     *n_frames = last_end == nbytes ? total : total + 1;
+    return FG_OK;
+}
+
+// replaces read_msglen + read_exact + String::from_utf8 of SyslenSplitter::run (splitter/syslen_splitter.rs:17-57) for a chunk
+int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint8_t* d_packed, uint64_t* d_offsets,
+                           uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames, uint64_t* consumed,
+                           int* stop_reason, void* stream) {
+    (void)final;  // (a frame needs its whole payload either way; what a TAIL means at the end of the stream is the caller's business)
+    if (!ctx || !d_packed || !d_offsets || !d_frame_starts || !d_bad_utf8 || !n_frames || !consumed || !stop_reason || (nbytes && !d_bytes))
+        return FG_ERR_ARG;
+    if (((uintptr_t)d_bytes & 15u) != 0 || ((uintptr_t)d_packed & 15u) != 0) return FG_ERR_ARG;
+    *n_frames = 0;
+    *consumed = 0;
+    *stop_reason = FG_SYSLEN_CLEAN;
+    if (!fg_launch_syslen || !fg_syslen_max_bytes || !fg_syslen_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    if (nbytes > fg_syslen_max_bytes()) return FG_ERR_UNSUPPORTED;  // (the scratch keeps positions as 32-bit words)
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_syslen_scratch_bytes(nbytes))) != FG_OK) return rc;
+    uint32_t* d_hdr = nullptr;
+    const int lrc = fg_launch_syslen(d_bytes, nbytes, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8, cap_frames, &d_hdr, s);
+    if (lrc != 0) {
+        ctx->last_hip = lrc;
+        return FG_ERR_HIP;
+    }
+    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (hdr[0] != 0 || hdr[5] != 1) return FG_ERR_UNSUPPORTED;  // declined: more speculative chains than the kernels track
+    *n_frames = hdr[2];
+    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
+    *consumed = hdr[3];
+    *stop_reason = (int)hdr[1];
+    ctx->last_syslen_payload = hdr[4];
     return FG_OK;
 }
 

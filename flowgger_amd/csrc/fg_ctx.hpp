@@ -62,6 +62,13 @@ extern "C" uint64_t fg_frame_scratch_bytes(uint64_t nbytes);
 extern "C" int fg_launch_frame(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
                                uint8_t* d_bad, uint64_t cap, uint64_t** d_total_out, hipStream_t stream, int classic);
 constexpr uint64_t FG_FRAME_ABORTED = ~0ull;  // *d_total_out after a one-pass launch whose look-back gave up: launch again, classic
+// the octet-counted framer (fg_syslen.hip): *d_hdr_out = its result words in device memory (fg::syslen H_*).  (WEAK references, as
+// fg_launch_capnp above: the fake launchers of the CPU suite have none, fg_frame_syslen_device then answers FG_ERR_UNSUPPORTED and the
+// host-buffer entry points take their host hop.  The product library always has the kernels: build.py checks the link.)
+extern "C" uint64_t fg_syslen_scratch_bytes(uint64_t nbytes) __attribute__((weak));
+extern "C" uint64_t fg_syslen_max_bytes(void) __attribute__((weak));
+extern "C" int fg_launch_syslen(const uint8_t* d_bytes, uint64_t nbytes, uint8_t* scratch, uint8_t* d_packed, uint64_t* d_offsets,
+                                uint64_t* d_starts, uint8_t* d_bad, uint64_t cap, uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
@@ -140,6 +147,12 @@ struct fg_ctx {
     uint64_t d_r3164_cap = 0;
     uint8_t* d_fused = nullptr;  // fg_frame_decode_device: the fused launch's scratch (ticket counters, tile counts, block prefixes)
     uint64_t d_fused_cap = 0;
+    uint8_t* d_sl_packed = nullptr;  // FG_FRAME_SYSLEN host-buffer calls: the payloads packed back to back
+    uint64_t d_sl_packed_cap = 0;
+    uint64_t* d_sl_starts = nullptr; // ... the frame starts in the caller's chunk
+    uint64_t d_sl_starts_cap = 0;
+    int last_syslen_stop = 0;        // fg_last_syslen_stop
+    uint64_t last_syslen_payload = 0; // fg_frame_syslen_device: the payload bytes its last call packed (the host-buffer calls size the decode with it)
     uint8_t* d_bad = nullptr;    // fg_frame_decode_batch: per-frame UTF-8 verdicts
     uint64_t d_bad_cap = 0;
     uint64_t* h_off = nullptr;   // fg_frame_decode_batch: pinned host copy of the frame offsets

@@ -7,7 +7,7 @@
 //       a final unterminated piece is a line if it is non-empty; invalid UTF-8 -> InvalidData ->
 //       stderr "Invalid UTF-8 input", the line is dropped.
 //   NulSplitter   `for line in buf_reader.split(0)` + str::from_utf8   nul_splitter.rs:18-40
-//   (SyslenSplitter's "<len> " prefix chain is sequential per connection and stays on the host.)
+//   (SyslenSplitter's "<len> " prefix chain has its own kernels: fg_syslen.hip.)
 //
 // Output: frame i = bytes[offsets[i] .. offsets[i+1]) INCLUDING its terminator (the decode
 // kernels strip "\n" / "\r\n" / "\0" themselves, fg_decode_frames_device), bad_utf8[i] = 1 when

@@ -7,6 +7,7 @@
 #include <cstddef>
 
 #include "fg_ctx.hpp"
+#include "fg_syslen_parse.hpp"
 
 extern "C" {
 
@@ -516,27 +517,116 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
 
 static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int final, uint64_t* n_frames, uint64_t* consumed);
 
-static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
-                                  fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
-    if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (fmt == FG_CAPNP) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
-    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_UNSUPPORTED;
-    *n_frames = 0;
-    *consumed = 0;
-    *out_offsets = nullptr;
-    if (nbytes == 0) return FG_OK;
-    DeviceGuard g(ctx->device);
+// FG_FRAME_SYSLEN stage shared by fg_frame_decode_batch and fg_transcode_batch (the read_msglen / read_exact loop of
+// SyslenSplitter::run, syslen_splitter.rs:42-57, for a chunk): the chunk goes up as it is (one copy; from a pinned
+// chunk the copy engine reads it in place at link speed and no payload byte is touched by the host's cores) and is framed + packed in HBM.  When the device
+// framer declines (fg_frame_syslen_device: FG_ERR_UNSUPPORTED) or meets a prefix beyond its bound, the prefixes are hopped on the host
+// over the caller's bytes and the packed batch is uploaded: the same results either way.  Leaves the payloads in ctx->d_sl_packed,
+// their offsets in ctx->d_offsets, the verdicts in ctx->d_bad, the frame starts in ctx->h_off (host, n + 1 entries).
+static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int final, uint64_t* n_frames, uint64_t* consumed, uint64_t* payload) {
     hipStream_t s = ctx->stream;
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
     FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
     FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
-    // 1. frame: offsets + UTF-8 verdicts
-    uint64_t n = 0;
-    if ((rc = frame_stage(ctx, framing, nbytes, final, &n, consumed)) != FG_OK) return rc;
+    const uint8_t* const d_src = ctx->d_bytes;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    auto ensure = [&](uint64_t cap) -> int {
+        int r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_sl_starts, &ctx->d_sl_starts_cap, (cap + 2) * 8)) != FG_OK) return r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return r;
+        if ((cap + 2) * 8 > ctx->h_off_cap) {
+            if (ctx->h_off) FG_HIP(ctx, hipHostFree(ctx->h_off));
+            ctx->h_off = nullptr;
+            ctx->h_off_cap = 0;
+            const uint64_t want = up((cap + 2) * 10, 1 << 16);
+            FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_off, want, hipHostMallocDefault));
+            ctx->h_off_cap = want;
+        }
+        return FG_OK;
+    };
+    uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 1024, n = 0;
+    int stop = FG_SYSLEN_CLEAN;
+    // (two deliberate simplifications: a cap_frames that turns out too small runs the whole framer again with the count it reported --
+    //  the next chunk is sized from this one's frames per byte --, and a prefix beyond the device parser's bound sends the WHOLE chunk
+    //  through the host hop below, not just that one frame: leading zeros by the dozen are legal and never seen)
+    for (;;) {
+        if ((rc = ensure(cap)) != FG_OK) return rc;
+        rc = fg_frame_syslen_device(ctx, d_src, nbytes, final, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts, ctx->d_bad, cap, &n, consumed, &stop,
+                                    FG_STREAM_OWN);
+        if (rc != FG_ERR_ENT_OVERFLOW) break;
+        cap = n + 16;
+    }
+    if (rc == FG_OK && stop != FG_SYSLEN_LONG_PREFIX) {
+        ctx->last_host_path = FG_PATH_FRAME_SYSLEN_DEVICE;
+        *payload = ctx->last_syslen_payload;
+        // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + *payload, 0, up(*payload, 16) + 16 - *payload, s));
+        FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_sl_starts, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+    } else if (rc == FG_OK || rc == FG_ERR_UNSUPPORTED) {
+        // the host hop (what fg::BatchingSplitter's Syslen branch does, over a chunk): prefixes of any length
+        namespace sl = fg::syslen;
+        std::vector<uint64_t> starts, offs{0};
+        std::vector<uint8_t> packed, bad;
+        stop = (int)sl::host_walk(bytes, nbytes, ~0ull, consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
+            const uint8_t* b = bytes + pos + plen;
+            bool err = false;
+            for (uint64_t i = 0; i <= len && !err; ++i)
+                err = sl::utf8_err_at(i < len ? b[i] : 0u, i >= 1 ? b[i - 1] : 0u, i >= 2 ? b[i - 2] : 0u, i >= 3 ? b[i - 3] : 0u);
+            starts.push_back(pos);
+            packed.insert(packed.end(), b, b + len);
+            offs.push_back(packed.size());
+            bad.push_back(err ? 1 : 0);
+        });
+        starts.push_back(*consumed);
+        n = starts.size() - 1;
+        if ((rc = ensure(n)) != FG_OK) return rc;
+        memcpy(ctx->h_off, starts.data(), (n + 1) * 8);
+        if (!packed.empty()) FG_HIP(ctx, hipMemcpyAsync(ctx->d_sl_packed, packed.data(), packed.size(), hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + packed.size(), 0, up(packed.size(), 16) + 16 - packed.size(), s));
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, bad.data(), n, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));  // (the vectors go out of scope)
+        *payload = packed.size();
+        ctx->last_host_path = FG_PATH_FRAME_SYSLEN_HOST;
+    } else {
+        return rc;
+    }
+    ctx->last_syslen_stop = stop;
+    *n_frames = n;
+    return FG_OK;
+}
+
+static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
+                                  fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
+    if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN) return FG_ERR_UNSUPPORTED;
+    const bool syslen = framing == FG_FRAME_SYSLEN;
+    *n_frames = 0;
+    *consumed = 0;
+    *out_offsets = nullptr;
+    if (syslen) ctx->last_syslen_stop = FG_SYSLEN_CLEAN;
+    if (nbytes == 0) return FG_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    uint64_t n = 0, payload = 0;
+    if (syslen) {
+        // 1. frame + pack where the chunk lies; what is decoded is the packed batch (FG_FRAME_NONE), what goes back are the frame starts
+        if ((rc = syslen_stage(ctx, bytes, nbytes, final, &n, consumed, &payload)) != FG_OK) return rc;
+    } else {
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+        // 1. frame: offsets + UTF-8 verdicts
+        if ((rc = frame_stage(ctx, framing, nbytes, final, &n, consumed)) != FG_OK) return rc;
+    }
     *n_frames = n;
     if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
-    if ((n + 1) * 8 > ctx->h_off_cap) {
+    if (!syslen && (n + 1) * 8 > ctx->h_off_cap) {
         if (ctx->h_off) FG_HIP(ctx, hipHostFree(ctx->h_off));
         ctx->h_off = nullptr;
         ctx->h_off_cap = 0;
@@ -544,7 +634,7 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
         FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_off, want, hipHostMallocDefault));
         ctx->h_off_cap = want;
     }
-    FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (!syslen) FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     *out_offsets = ctx->h_off;
     if (n == 0) {
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -553,7 +643,9 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
         return FG_OK;
     }
     // 2. decode the frames in place (terminators stripped in-kernel, invalid UTF-8 -> FG_ST_BAD_UTF8)
-    const uint64_t used_bytes = *consumed;
+    const uint64_t used_bytes = syslen ? payload : *consumed;
+    const uint8_t* const dec_bytes = syslen ? ctx->d_sl_packed : ctx->d_bytes;
+    const fg_framing dec_framing = syslen ? FG_FRAME_NONE : framing;
     uint64_t ent_cap = fmt == FG_RFC5424 ? used_bytes / 16 + 1024 : used_bytes / 8 + 1024;
     for (;;) {
         if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
@@ -571,7 +663,7 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
         fg_tables dt, ht;
         carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
         carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
-        rc = fg_decode_frames_device(ctx, fmt, framing, ctx->d_bytes, used_bytes, ctx->d_offsets, n, ctx->d_bad, &dt, FG_STREAM_OWN);
+        rc = fg_decode_frames_device(ctx, fmt, dec_framing, dec_bytes, used_bytes, ctx->d_offsets, n, ctx->d_bad, &dt, FG_STREAM_OWN);
         if (rc != FG_OK) return rc;
         uint64_t used = 0;
         FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
@@ -897,7 +989,12 @@ static int frame_decode_fused(fg_ctx* ctx, fg_format fmt, fg_framing framing, co
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
                           fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_UNSUPPORTED;
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN) return FG_ERR_UNSUPPORTED;
+    if (framing == FG_FRAME_SYSLEN) {  // (one piece: framed + packed where the chunk lies, then the packed batch is decoded)
+        const int rc = frame_decode_one_piece(ctx, fmt, framing, bytes, nbytes, final, out, out_offsets, n_frames, consumed);
+        if (rc != FG_OK) ctx->last_host_path = 0;
+        return rc;
+    }
     {
         DeviceGuard g(ctx->device);
         *n_frames = 0;
@@ -956,7 +1053,8 @@ static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int fin
 
 // Decode ctx->d_bytes / ctx->d_offsets into tables carved from ctx->d_tab, growing the entry table until it fits.
 static int decode_stage(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t nbytes, uint64_t n, const uint8_t* d_bad,
-                        fg_tables* dt, uint64_t* ent_used) {
+                        fg_tables* dt, uint64_t* ent_used, const uint8_t* d_src = nullptr) {
+    if (!d_src) d_src = ctx->d_bytes;
     hipStream_t s = ctx->stream;
     int rc;
     uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
@@ -967,7 +1065,7 @@ static int decode_stage(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t
         carve(nullptr, n, ent_cap, nullptr, &bytes_total);
         if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, bytes_total)) != FG_OK) return rc;
         carve(ctx->d_tab, n, ent_cap, dt, nullptr);
-        rc = fg_decode_frames_device(ctx, fmt, framing, ctx->d_bytes, nbytes, ctx->d_offsets, n, d_bad, dt, FG_STREAM_OWN);
+        rc = fg_decode_frames_device(ctx, fmt, framing, d_src, nbytes, ctx->d_offsets, n, d_bad, dt, FG_STREAM_OWN);
         if (rc != FG_OK) return rc;
         uint64_t used = 0;
         FG_HIP(ctx, hipMemcpyAsync(&used, dt->ent_used, 8, hipMemcpyDeviceToHost, s));
@@ -1210,8 +1308,10 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
 int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* ecfg, const uint8_t* bytes,
                        uint64_t nbytes, const uint64_t* offsets, uint64_t n, int final, fg_transcoded* out) {
     if (!ctx || !ecfg || !out || (nbytes && !bytes)) return FG_ERR_ARG;
-    if ((int)framing < 0 || (int)framing > 2) return FG_ERR_ARG;
+    if ((int)framing < 0 || (int)framing > (int)FG_FRAME_SYSLEN) return FG_ERR_ARG;
     if (fmt == FG_CAPNP && framing != FG_FRAME_NONE) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
+    const bool syslen = framing == FG_FRAME_SYSLEN;
+    if (syslen) ctx->last_syslen_stop = FG_SYSLEN_CLEAN;
     if (framing == FG_FRAME_NONE) {
         if (n && !offsets) return FG_ERR_ARG;
         if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
@@ -1234,12 +1334,23 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
         *out = fg_transcoded{};
     }
     // 1. the chunk (and, for framed input, its offsets) to HBM
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
-    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
-    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    if (!syslen) {
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+        if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    }
     uint64_t consumed = nbytes;
     const uint8_t* d_bad = nullptr;
-    if (framing == FG_FRAME_NONE) {
+    // (FG_FRAME_SYSLEN: what is decoded and encoded is the PACKED batch -- payloads back to back, FG_FRAME_NONE offsets)
+    const uint8_t* d_src = nullptr;
+    uint64_t src_bytes = 0;
+    fg_framing dec_framing = framing;
+    if (syslen) {
+        if ((rc = syslen_stage(ctx, bytes, nbytes, final, &n, &consumed, &src_bytes)) != FG_OK) return rc;
+        d_bad = ctx->d_bad;
+        d_src = ctx->d_sl_packed;
+        dec_framing = FG_FRAME_NONE;
+    } else if (framing == FG_FRAME_NONE) {
         if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 1) * 8)) != FG_OK) return rc;
         if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
     } else {
@@ -1255,7 +1366,11 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     // 2. decode (tables stay in HBM)
     fg_tables dt{};
     uint64_t ent_used = 0;
-    if ((rc = decode_stage(ctx, fmt, framing, consumed, n, d_bad, &dt, &ent_used)) != FG_OK) return rc;
+    if (!syslen) {
+        d_src = ctx->d_bytes;
+        src_bytes = consumed;
+    }
+    if ((rc = decode_stage(ctx, fmt, dec_framing, src_bytes, n, d_bad, &dt, &ent_used, d_src)) != FG_OK) return rc;
     // 3. encode + frame from the tables; the output buffer grows to the batch (steady state: one count + one write)
     const uint64_t offs_bytes = up((n + 1) * 8, 256);
     if ((rc = grow_dev(ctx, (void**)&ctx->d_tmeta, &ctx->d_tmeta_cap, offs_bytes + up(n, 256))) != FG_OK) return rc;
@@ -1263,11 +1378,11 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     uint8_t* d_enc_status = ctx->d_tmeta + offs_bytes;
     if (!ctx->d_tout && (rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, consumed + consumed / 2 + 4096)) != FG_OK) return rc;
     uint64_t total = 0;
-    rc = fg_encode_device(ctx, fmt, ecfg, ctx->d_bytes, consumed, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
+    rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
                           d_enc_status, &total, FG_STREAM_OWN);
     if (rc == FG_ERR_ENT_OVERFLOW) {
         if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, total + 4096)) != FG_OK) return rc;
-        rc = fg_encode_device(ctx, fmt, ecfg, ctx->d_bytes, consumed, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
+        rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
                               d_enc_status, &total, FG_STREAM_OWN);
     }
     if (rc != FG_OK) return rc;
@@ -1280,7 +1395,8 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     FG_HIP(ctx, hipMemcpyAsync(h + o_offs, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync(h + o_meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync(h + o_st, d_enc_status, n, hipMemcpyDeviceToHost, s));
-    if (framing != FG_FRAME_NONE) FG_HIP(ctx, hipMemcpyAsync(h + o_frames, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (syslen) memcpy(h + o_frames, ctx->h_off, (n + 1) * 8);  // (the frame starts in the caller's chunk, prefix included)
+    else if (framing != FG_FRAME_NONE) FG_HIP(ctx, hipMemcpyAsync(h + o_frames, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
     out->out = h + o_msgs;
     out->out_bytes = total;

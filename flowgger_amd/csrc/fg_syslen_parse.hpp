@@ -1,0 +1,89 @@
+// fg_syslen_parse.hpp -- the length prefix of an octet-counted frame (read_msglen, src/flowgger/splitter/syslen_splitter.rs:17-25), the
+// position-based UTF-8 rule and the sequential walk over a chunk: what the device framer (fg_syslen.hpp), the host hop of the
+// host-buffer entry points (fg_host_pipeline.cpp) and the CPU suite share.  No HIP, no wave primitives.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define FG_SLH __host__ __device__ inline
+#else
+#define FG_SLH inline
+#endif
+
+
+namespace fg {
+namespace syslen {
+
+constexpr uint32_t kMaxPrefix = 24;  // FG_SYSLEN_MAX_PREFIX: bytes of "<len> " the device parser reads, the ' ' included
+// fg_syslen_stop + "a well-formed prefix whose payload fits"
+enum { ST_CLEAN = 0, ST_TAIL = 1, ST_BAD_LEN = 2, ST_LONG_PREFIX = 3, ST_VALID = 4 };
+
+struct Prefix {
+    uint32_t st, plen;
+    uint64_t len;
+};
+// read_msglen at position p of a chunk of nbytes: the bytes up to and including the first ' ', the text before it as
+// usize::from_str (an optional '+', at least one digit, leading zeros, nothing else, the value fits 64 bits).  bound = the bytes
+// looked at (kMaxPrefix on the device; the host hop passes ~0).
+template <class Get>
+FG_SLH Prefix parse_prefix(Get get, uint64_t p, uint64_t nbytes, uint64_t bound = kMaxPrefix) {
+    Prefix r{ST_CLEAN, 0u, 0ull};
+    if (p >= nbytes) return r;
+    uint64_t v = 0;
+    bool digits = false, ovf = false;
+    for (uint64_t k = 0; k < bound; ++k) {
+        if (p + k >= nbytes) { r.st = ST_TAIL; return r; }
+        const uint32_t c = get(p + k);
+        if (c == ' ') {
+            r.plen = (uint32_t)k + 1u;
+            r.len = v;
+            if (!digits || ovf) r.st = ST_BAD_LEN;
+            else r.st = v > nbytes - (p + k + 1u) ? ST_TAIL : ST_VALID;
+            return r;
+        }
+        if (c == '+' && k == 0) continue;
+        if (c < '0' || c > '9') { r.st = ST_BAD_LEN; return r; }
+        const uint64_t d = c - '0';
+        if (v > (~0ull - d) / 10ull) ovf = true;
+        else v = v * 10ull + d;
+        digits = true;
+    }
+    r.st = ST_LONG_PREFIX;
+    return r;
+}
+
+// UTF-8 well-formedness judged AT one byte from it and its three predecessors (0 before the payload): the rule of fg_frame.hip.
+// A sequence cut off by the end of a payload shows at the position behind it (b = 0): under this framing that byte is the next
+// prefix's or the chunk's end, so the caller asks for position `len` itself and flags the frame that ends there.
+FG_SLH bool utf8_err_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3) {
+    const bool c1 = (p1 & 0xC0u) == 0x80u, c2 = (p2 & 0xC0u) == 0x80u;
+    const bool must = p1 >= 0xC0u || (p2 >= 0xE0u && c1) || (p3 >= 0xF0u && c2 && c1);
+    bool err = ((b & 0xC0u) == 0x80u) != must;
+    err |= b == 0xC0u || b == 0xC1u || b >= 0xF5u;
+    err |= p1 == 0xE0u && !(b & 0x20u);
+    err |= p1 == 0xEDu && (b & 0x20u);
+    err |= p1 == 0xF0u && !(b & 0x30u);
+    err |= p1 == 0xF4u && (b & 0x30u);
+    return err;
+}
+
+// The sequential walk (what the device logic must reproduce, and the host hop of the entry points that take host buffers): frames
+// into `starts` / `plens` while they fit `cap`; returns the stop reason.  bound as parse_prefix.
+template <class Push>
+inline uint32_t host_walk(const uint8_t* bytes, uint64_t nbytes, uint64_t bound, uint64_t* consumed, Push push) {
+    uint64_t pos = 0;
+    auto get = [&](uint64_t p) { return (uint32_t)bytes[p]; };
+    for (;;) {
+        const Prefix pr = parse_prefix(get, pos, nbytes, bound);
+        if (pr.st != ST_VALID) {
+            *consumed = pos;
+            return pr.st;
+        }
+        push(pos, pr.plen, pr.len);
+        pos += pr.plen + pr.len;
+    }
+}
+
+}  // namespace syslen
+}  // namespace fg

@@ -158,6 +158,41 @@ class Decoder:
             L.check(rc, "fg_frame_device")
             return d_offsets, d_bad, int(n.value)
 
+    def frame_syslen_device(self, d_bytes, final: bool = True, cap_frames: Optional[int] = None, stream=None):
+        """Frame an octet-counted stream ("<len> " + len bytes, input.framing = "syslen") resident in HBM: read_msglen + read_exact +
+        the per-message String::from_utf8 of SyslenSplitter::run (splitter/syslen_splitter.rs:17-57), FRAMED AND PACKED.  Returns
+        (d_packed uint8, d_offsets int64[n + 1] into d_packed -- the FG_FRAME_NONE convention: decode_frames_device / the encoders take
+        the two as they are --, d_frame_starts int64[n + 1] into d_bytes with the prefixes, d_bad uint8[n], n, consumed, stop_reason
+        (an FG_SYSLEN_*)).  Every payload that is not valid UTF-8 is flagged; the reference panics at the first one, and stopping
+        there is the caller's job.  FgError(FG_ERR_UNSUPPORTED) when the device path declines the chunk: frame it on the host.
+        d_bytes must start at a 16-byte aligned address (FG_ERR_ARG otherwise: a slice of a tensor from an odd offset does not) and
+        its memory must be readable up to numel() rounded up to 16 -- view it into an allocation with that pad."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        nbytes = d_bytes.numel()
+        cap = cap_frames if cap_frames is not None else nbytes // 32 + 16
+        d_packed = torch.empty((nbytes + 15) // 16 * 16 + 16, dtype=torch.uint8, device=d_bytes.device)
+        while True:
+            d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=d_bytes.device)
+            d_starts = torch.empty(cap + 1, dtype=torch.int64, device=d_bytes.device)
+            d_bad = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_bytes.device)
+            n, consumed, stop = C.c_uint64(), C.c_uint64(), C.c_int()
+            rc = L.lib().fg_frame_syslen_device(self._ctx, d_bytes.data_ptr(), nbytes, int(final), d_packed.data_ptr(), d_offsets.data_ptr(),
+                                                d_starts.data_ptr(), d_bad.data_ptr(), cap, C.byref(n), C.byref(consumed), C.byref(stop),
+                                                C.c_void_p(stream.cuda_stream))
+            if rc == L.FG_ERR_ENT_OVERFLOW:
+                cap = int(n.value) + 16
+                continue
+            L.check(rc, "fg_frame_syslen_device")
+            k = int(n.value)
+            return d_packed, d_offsets[:k + 1], d_starts[:k + 1], d_bad[:k], k, int(consumed.value), int(stop.value)
+
+    def last_syslen_stop(self) -> int:
+        """how the prefix chain of the last FG_FRAME_SYSLEN frame_decode_batch / Pipeline.run_stream on this decoder ended (FG_SYSLEN_*)"""
+        return int(L.lib().fg_last_syslen_stop(self._ctx))
+
     def decode_frames_device(self, d_bytes, d_offsets, n: int, tables: DeviceTables, framing: int, d_bad=None,
                              stream=None) -> None:
         """Decode frames produced by frame_device (terminators are stripped inside the kernels; frames
@@ -192,7 +227,9 @@ class Decoder:
         """Raw chunk of the byte stream in, tables out: GPU framing + UTF-8 validation + decode in one
         call (fg_frame_decode_batch; the body of LineSplitter::run / NulSplitter::run).  Returns
         (HostTables, offsets uint64[n+1], consumed): frame i = raw[offsets[i]:offsets[i+1]] including
-        its terminator; raw[consumed:] is an unterminated tail to carry over (empty when `final`)."""
+        its terminator; raw[consumed:] is an unterminated tail to carry over (empty when `final`).
+        framing = FG_FRAME_SYSLEN (the loop of SyslenSplitter::run): frame i starts with its "<len> " prefix and the tables' spans are
+        relative to its payload; last_syslen_stop() says how the chain ended at `consumed`."""
         buf = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, np.uint8)
         padded = np.zeros(buf.size + 16, np.uint8)
         padded[:buf.size] = buf

@@ -181,7 +181,9 @@ class Pipeline:
         return self._call(L.FG_FRAME_NONE, data, int(offsets[-1]) if n else 0, offsets, n, True, now_ts)
 
     def run_stream(self, raw, framing: int, final: bool = True, now_ts: float = 0.0) -> Transcoded:
-        """a raw stream chunk, framed on the GPU ("\\n" / NUL); bytes past `.consumed` belong to the next chunk"""
+        """a raw stream chunk, framed on the GPU ("\\n" / NUL / FG_FRAME_SYSLEN: "<len> " prefixes -- `.frame_offsets` are then the frame
+        starts, prefixes included, and decoder.last_syslen_stop() says how the chain ended); bytes past `.consumed` belong to the
+        next chunk"""
         import numpy as np
 
         data = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)

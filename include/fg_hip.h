@@ -99,8 +99,36 @@ enum {
 typedef enum fg_framing {
     FG_FRAME_NONE = 0, /* offsets delimit bare lines (framing bytes already stripped by the caller) */
     FG_FRAME_LINE = 1, /* BufRead::lines(): "\n" terminated, the "\n" and one preceding "\r" are not part of the line */
-    FG_FRAME_NUL = 2   /* BufRead::split(0): "\0" terminated */
+    FG_FRAME_NUL = 2,  /* BufRead::split(0): "\0" terminated */
+    FG_FRAME_SYSLEN = 3 /* RFC 6587 octet counting (splitter/syslen_splitter.rs:17-57): "<len> " followed by exactly len bytes, untrimmed
+                           (a trailing "\n" belongs to the message); framed by fg_frame_syslen_device and by the host-buffer entry points
+                           fg_frame_decode_batch / fg_transcode_batch.  An additive value under the same FG_ABI_VERSION: a library without
+                           it rejects it with FG_ERR_ARG / FG_ERR_UNSUPPORTED */
 } fg_framing;
+
+/* How the "<len> " chain of an FG_FRAME_SYSLEN chunk ended (fg_frame_syslen_device, fg_last_syslen_stop): what the caller does next
+ * to reproduce SyslenSplitter::run (syslen_splitter.rs:42-57). */
+typedef enum fg_syslen_stop {
+    FG_SYSLEN_CLEAN = 0,      /* consumed == nbytes: the chunk ended on a frame boundary.  At the end of the stream read_until returns
+                                 Ok(0): "Can't read message's length" */
+    FG_SYSLEN_TAIL = 1,       /* the prefix or the payload at `consumed` runs past nbytes.  Not final: carry bytes[consumed ..) over.
+                                 Final: EOF inside the length (the reference drops the last byte it read, parses the rest, and
+                                 read_exact fails) or inside the payload ("failed to fill whole buffer") -- the host code
+                                 (flowgger_amd/host/fg_decoder.hpp) tells the two apart on the few bytes of the tail */
+    FG_SYSLEN_BAD_LEN = 2,    /* the bytes at `consumed` are no length (a lone ' ', a non-digit, '+' alone, a value beyond 64 bits):
+                                 "Can't read message's length", the connection is over */
+    FG_SYSLEN_LONG_PREFIX = 3 /* the prefix at `consumed` is longer than FG_SYSLEN_MAX_PREFIX bytes (leading zeros: legal, never seen):
+                                 the caller hops that one frame on the host and resubmits the rest */
+} fg_syslen_stop;
+#define FG_SYSLEN_MAX_PREFIX 24u /* bytes of a "<len> " prefix, the ' ' included, the device parser reads */
+
+/* Bytes of the "<len> " prefix of an FG_FRAME_SYSLEN frame as fg_frame_decode_batch / fg_transcode_batch return it (`frame` = its
+ * first byte, frame_len = off[i + 1] - off[i]): the payload -- what the table's spans are relative to -- starts that many bytes in. */
+static inline uint32_t FG_SYSLEN_PREFIX_LEN(const uint8_t* frame, uint64_t frame_len) {
+    uint32_t k = 0;
+    while (k < frame_len && frame[k] != (uint8_t)' ') ++k;
+    return k < frame_len ? k + 1u : (uint32_t)frame_len;
+}
 
 /* entry flags */
 enum {
@@ -288,15 +316,16 @@ int fg_decode_batch_device(fg_ctx* ctx, fg_format fmt, const uint8_t* d_bytes, u
  *   d_bad_utf8  out, cap_frames + 1 bytes: 1 = the frame is not valid UTF-8
  *   n_frames    out (host): number of frames; the call synchronises the stream to read it
  * Returns FG_ERR_ENT_OVERFLOW when cap_frames is too small (*n_frames then holds the need).
- * framing must be FG_FRAME_LINE or FG_FRAME_NUL.  (syslen framing is a sequential prefix chain
- * per connection and stays on the host: flowgger_amd/host/fg_decoder.hpp.) */
+ * framing must be FG_FRAME_LINE or FG_FRAME_NUL (FG_ERR_UNSUPPORTED otherwise: FG_FRAME_SYSLEN has its own entry point,
+ * fg_frame_syslen_device, because its frames carry a prefix and come out packed). */
 int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
                     uint64_t* d_offsets, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames,
                     void* stream);
 
 /* Decode frames as produced by fg_frame_device: the kernels strip the terminators themselves, and
  * frames flagged in d_bad_utf8 (may be NULL) get status FG_ST_BAD_UTF8 instead of a decode.
- * fg_decode_batch_device(...) == fg_decode_frames_device(..., FG_FRAME_NONE, ..., NULL, ...). */
+ * fg_decode_batch_device(...) == fg_decode_frames_device(..., FG_FRAME_NONE, ..., NULL, ...).
+ * FG_FRAME_SYSLEN is rejected (FG_ERR_ARG): decode what fg_frame_syslen_device packed with FG_FRAME_NONE. */
 int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes,
                             uint64_t nbytes, const uint64_t* d_offsets, uint64_t n,
                             const uint8_t* d_bad_utf8, const fg_tables* tables, void* stream);
@@ -316,7 +345,32 @@ int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, cons
  *                written: run again with more; [1] nonzero: the kernel's look-back gave up (never seen; bounded spin) -- nothing is
  *                valid, use fg_frame_device + fg_decode_frames_device
  * Asynchronous on `stream`.  FG_ERR_UNSUPPORTED (nothing launched): FG_RFC3164, or lines so long (average >= 768 bytes) that the
- * decoders stage heads only -- those keep the separate framing pass. */
+ * decoders stage heads only -- those keep the separate framing pass.  FG_FRAME_SYSLEN is rejected (FG_ERR_ARG): see
+ * fg_frame_syslen_device. */
+
+/* GPU FRAMING of an OCTET-COUNTED stream (input.framing = "syslen"; replaces read_msglen + read_exact + String::from_utf8 of
+ * SyslenSplitter::run, splitter/syslen_splitter.rs:17-57, for a chunk of the stream that lies in device-addressable memory).
+ * At a frame start the prefix is the bytes up to and including the first ' '; the text before it is usize::from_str (an optional
+ * '+', at least one ASCII digit, leading zeros allowed, nothing else, the value fits 64 bits); the payload is the next len bytes,
+ * untrimmed; the next frame starts right behind it; len == 0 is an empty message.  The frames are written FRAMED AND PACKED:
+ *   d_bytes         raw stream chunk (device-addressable), 16-byte aligned, readable up to nbytes rounded up to 16
+ *   final           nonzero: the stream ends with this chunk.  (The frames found are the same either way -- a frame needs its whole
+ *                   payload; what differs is what the caller does with a TAIL.)
+ *   d_packed        out: the payloads back to back, capacity nbytes rounded up to 16, plus 16
+ *   d_offsets       out, cap_frames + 1 entries INTO d_packed, the FG_FRAME_NONE convention: everything downstream
+ *                   (fg_decode_frames_device(..., FG_FRAME_NONE, ...), fg_encode_device*, the mergers) takes the two unchanged
+ *   d_frame_starts  out, cap_frames + 1 entries INTO d_bytes, prefix included: the frames tile [0, consumed)
+ *   d_bad_utf8      out, cap_frames bytes: 1 = the payload is not valid UTF-8 (rows decoded with it get FG_ST_BAD_UTF8).  The
+ *                   reference unwrap()-panics at the FIRST such payload (syslen_splitter.rs:32): every such frame is flagged here,
+ *                   stopping at the first one is the CALLER's job
+ *   n_frames, consumed, stop_reason   out (host): frames, the bytes they cover, an fg_syslen_stop; the call synchronises the stream
+ * Returns FG_ERR_ENT_OVERFLOW when cap_frames is too small (*n_frames holds the need; nbytes / 2 always suffices), and
+ * FG_ERR_UNSUPPORTED when the device path DECLINES the chunk -- payload text that looks like prefixes sent more speculative chains
+ * across a tile boundary than the kernels track: nothing is valid, frame the chunk on the host (the host-buffer entry points do).
+ * The chain is resolved exactly: a result that is returned is the sequential walk's. */
+int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint8_t* d_packed, uint64_t* d_offsets,
+                           uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames, uint64_t* consumed,
+                           int* stop_reason, void* stream);
 int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                            uint64_t* d_offsets, uint64_t cap_frames, const fg_tables* tables, uint64_t avg_line_hint,
                            uint64_t* d_result, void* stream);
@@ -344,6 +398,11 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
  *   out_offsets  ctx-owned host array, *n_frames + 1 entries: frame i = bytes[off[i] .. off[i+1])
  *                INCLUDING its terminator; spans in `out` are relative to off[i]
  *   consumed     bytes covered by the returned frames: carry bytes[consumed .. nbytes) over
+ * FG_FRAME_SYSLEN (the whole loop of SyslenSplitter::run, syslen_splitter.rs:42-57, for a chunk): out_offsets are the frame starts
+ * in `bytes`, "<len> " prefix included; the spans in `out` are relative to each frame's PAYLOAD start, off[i] +
+ * FG_SYSLEN_PREFIX_LEN(bytes + off[i], off[i + 1] - off[i]); fg_last_syslen_stop says how the chain ended.  Every payload that is not
+ * valid UTF-8 is flagged FG_ST_BAD_UTF8; the reference panics at the first one, and stopping there is the caller's job.  A chunk the
+ * device framer declines is framed by a host hop over `bytes` instead, with the same results (fg_last_host_path tells).
  * Everything returned stays valid until the next call on this ctx. */
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes,
                           uint64_t nbytes, int final, fg_tables* out, const uint64_t** out_offsets,
@@ -356,9 +415,14 @@ enum {
     FG_PATH_DECODE_SLICED = 2,     /* fg_decode_batch: hipMemcpy slices on three streams */
     FG_PATH_FRAME_FUSED = 3,       /* fg_frame_decode_batch: ONE launch -- the decode kernel frames the pinned chunk itself (round 6) */
     FG_PATH_FRAME_SLICED = 4,      /* fg_frame_decode_batch: upload slices + framing scan + decode per slice (rounds 3-5) */
-    FG_PATH_FRAME_ONE_PIECE = 5    /* fg_frame_decode_batch: upload, frame, count on the host, decode */
+    FG_PATH_FRAME_ONE_PIECE = 5,   /* fg_frame_decode_batch: upload, frame, count on the host, decode */
+    FG_PATH_FRAME_SYSLEN_DEVICE = 6, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_SYSLEN: framed + packed by the device */
+    FG_PATH_FRAME_SYSLEN_HOST = 7  /* ... the device framer declined the chunk: the prefixes were hopped on the host */
 };
 int fg_last_host_path(const fg_ctx* ctx);
+/* How the prefix chain of the last FG_FRAME_SYSLEN call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an
+ * fg_syslen_stop; FG_SYSLEN_CLEAN before the first such call). */
+int fg_last_syslen_stop(const fg_ctx* ctx);
 
 /* GELF ENCODER FROM THE TABLES: replaces GelfEncoder::encode (src/flowgger/encoder/
  * gelf_encoder.rs:59-115, serde_json 0.8 serialisation of the BTreeMap it builds) for a whole
@@ -444,6 +508,8 @@ const char* fg_encode_error_string(uint8_t enc_status);
  *   framing == FG_FRAME_LINE / _NUL: `bytes` is a raw stream chunk, `offsets` must be NULL and `n` is ignored; an
  *     unterminated tail is a frame only when `final` != 0, otherwise out->consumed < nbytes and the caller carries
  *     the rest over to the next call (as for fg_frame_decode_batch).
+ *   framing == FG_FRAME_SYSLEN: the same for an octet-counted chunk; frame_offsets are the frame starts, prefix included
+ *     (FG_SYSLEN_PREFIX_LEN), and fg_last_syslen_stop says how the chain ended.
  * Results (pinned host memory owned by ctx, valid until the next host-buffer call on it):
  *   out / out_bytes / out_offsets[n + 1]   message i = out[out_offsets[i] .. out_offsets[i + 1]) -- empty when the
  *                                          line was dropped
