@@ -212,11 +212,16 @@ __global__ __launch_bounds__(kWave) void k_rfc3164_perm(const uint8_t* __restric
     // (three ds_bpermute each before), and the list of the long rows (lane ids in ballot order)
     __shared__ uint4 s_meta[kWave];
     __shared__ uint8_t s_long[kWave];
-    s_meta[lane] = make_uint4(o0_lo, o0_hi, tb | (st_fit << 16), 0u);
+    // (a row that is NOT staged -- it does not fit, or the lane has no record -- publishes zero for both halves: its prefix sum is not
+    //  bounded by anything (the rows of one workgroup may add up to megabytes; a lane without a record holds the total), and the bits
+    //  of it from 64 KiB up would read as row bytes and send the line's first sixteen bytes over a row staged before it)
+    s_meta[lane] = make_uint4(o0_lo, o0_hi, (in_tile ? tb : 0u) | (st_fit << 16), 0u);
     if (st_fit > 256u) s_long[__popcll(longm & ((1ull << lane) - 1ull))] = (uint8_t)lane;
     __syncthreads();
     uint4 v[16], v2[kLong];
-    uint32_t rpk[16], r2pk[kLong];  // row offset | row bytes << 16 (the tile is below 64 KiB)
+    // row offset | row bytes << 16: both halves are those of a STAGED row (offset + bytes <= tile_cap <= 56 KiB, so each fits sixteen
+    // bits) or zero, and the stores are guarded by the row bytes alone
+    uint32_t rpk[16], r2pk[kLong];
 #pragma unroll
     for (uint32_t i = 0; i < 16u; ++i) {
         const uint4 m = s_meta[i * 4u + sub];  // the line this lane helps to stage in step i
