@@ -25,6 +25,8 @@ FG_EF_VAL_ESC, FG_EF_NAME_ESC, FG_EF_SUFFIX, FG_EF_NAME_VERBATIM = 1, 2, 4, 8  #
 FG_FRAME_NONE, FG_FRAME_LINE, FG_FRAME_NUL, FG_FRAME_SYSLEN = 0, 1, 2, 3
 FG_SYSLEN_CLEAN, FG_SYSLEN_TAIL, FG_SYSLEN_BAD_LEN, FG_SYSLEN_LONG_PREFIX = 0, 1, 2, 3  # fg_syslen_stop
 FG_SYSLEN_MAX_PREFIX = 24
+FG_UDP_RAW, FG_UDP_ZLIB, FG_UDP_GZIP, FG_UDP_BAD_ZLIB, FG_UDP_BAD_GZIP, FG_UDP_BAD_UTF8, FG_UDP_TOO_LARGE = range(7)  # fg_udp_status
+FG_UDP_DEFAULT_MAX_INFLATED = 65_527 * 5
 FG_ST_OVERFLOW, FG_ST_BAD_UTF8 = 0xFE, 0xFD
 FG_F_LTSV_NOVALUE = 128  # meta flags bit (include/fg_hip.h)
 FG_OK, FG_ERR_ARG, FG_ERR_HIP, FG_ERR_NO_DEVICE, FG_ERR_ENT_OVERFLOW, FG_ERR_UNSUPPORTED, FG_ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
@@ -186,6 +188,10 @@ def lib() -> C.CDLL:
     L.fg_last_host_path.argtypes = [vp]
     L.fg_last_syslen_stop.argtypes = [vp]
     L.fg_frame_syslen_device.argtypes = [vp, vp, u64, C.c_int, vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), vp]
+    L.fg_udp_error_string.argtypes = [C.c_uint8]
+    L.fg_udp_error_string.restype = C.c_char_p
+    L.fg_udp_unpack_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
+    L.fg_udp_decode_batch.argtypes = [vp, C.c_int, vp, u64, vp, u64, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.fg_frame_decode_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, vp, u64, C.POINTER(fg_tables), u64, vp, vp]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")

@@ -247,6 +247,10 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_bad) (void)hipFree(ctx->d_bad);
     if (ctx->d_sl_packed) (void)hipFree(ctx->d_sl_packed);
     if (ctx->d_sl_starts) (void)hipFree(ctx->d_sl_starts);
+    if (ctx->d_udp) (void)hipFree(ctx->d_udp);
+    if (ctx->d_udp_off) (void)hipFree(ctx->d_udp_off);
+    if (ctx->d_udp_st) (void)hipFree(ctx->d_udp_st);
+    if (ctx->h_udp) (void)hipHostFree(ctx->h_udp);
     if (ctx->d_enc) (void)hipFree(ctx->d_enc);
     if (ctx->h_enc_ring) (void)hipHostFree(ctx->h_enc_ring);
     for (hipEvent_t e : ctx->ev_enc)
@@ -434,6 +438,61 @@ int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
     *consumed = hdr[3];
     *stop_reason = (int)hdr[1];
     ctx->last_syslen_payload = hdr[4];
+    return FG_OK;
+}
+
+const char* fg_udp_error_string(uint8_t st) {
+    switch (st) {
+        case FG_UDP_RAW:
+        case FG_UDP_ZLIB:
+        case FG_UDP_GZIP: return "";
+        case FG_UDP_BAD_ZLIB: return "Corrupted compressed (zlib) record";  // udp_input.rs:113
+        case FG_UDP_BAD_GZIP: return "Corrupted compressed (gzip) record";  // udp_input.rs:124
+        case FG_UDP_BAD_UTF8: return "Invalid UTF-8 input";                 // udp_input.rs:136
+        case FG_UDP_TOO_LARGE: return "Compressed record inflates beyond max_inflated (not inflated on the GPU)";
+        default: return nullptr;
+    }
+}
+
+// replaces handle_record_maybe_compressed (input/udp_input.rs:100-143) up to decoder.decode, for a batch of datagrams
+int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
+                         uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total,
+                         void* stream) {
+    if (!ctx || !d_offsets || !d_out_offsets || !d_drop || !d_udp_status || !total || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) != 0) return FG_ERR_ARG;
+    if (max_inflated == 0) max_inflated = FG_UDP_DEFAULT_MAX_INFLATED;
+    if (max_inflated > FG_UDP_MAX_MAX_INFLATED) return FG_ERR_ARG;
+    *total = 0;
+    if (!fg_launch_udp_count || !fg_launch_udp_write || !fg_launch_udp_finish) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    if (n == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    const uint64_t nb = (n + 63) / 64, sizes_bytes = up(n * 4, 16);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, sizes_bytes + nb * 8)) != FG_OK) return rc;
+    uint32_t* d_sizes = (uint32_t*)ctx->d_udp;
+    uint64_t* d_sums = (uint64_t*)(ctx->d_udp + sizes_bytes);
+    int lrc = fg_launch_udp_count(d_bytes, d_offsets, n, (uint32_t)max_inflated, d_sizes, d_sums, d_udp_status, d_drop, s);
+    if (lrc == 0) lrc = fg_launch_encode_scan(d_sizes, d_sums, n, d_out_offsets, 0ull, s);
+    if (lrc != 0) {
+        ctx->last_hip = lrc;
+        return FG_ERR_HIP;
+    }
+    FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (!d_out) return FG_OK;  // the sizing call
+    if (*total > out_cap) return FG_ERR_ENT_OVERFLOW;
+    lrc = fg_launch_udp_write(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
+    if (lrc == 0) lrc = fg_launch_udp_finish(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
+    if (lrc != 0) {
+        ctx->last_hip = lrc;
+        return FG_ERR_HIP;
+    }
+    FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
 }
 

@@ -69,6 +69,15 @@ extern "C" uint64_t fg_syslen_scratch_bytes(uint64_t nbytes) __attribute__((weak
 extern "C" uint64_t fg_syslen_max_bytes(void) __attribute__((weak));
 extern "C" int fg_launch_syslen(const uint8_t* d_bytes, uint64_t nbytes, uint8_t* scratch, uint8_t* d_packed, uint64_t* d_offsets,
                                 uint64_t* d_starts, uint8_t* d_bad, uint64_t cap, uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
+// the UDP input's unpacker (fg_udp.hip): count (sizes + per-64 sums; the scan between the two is fg_launch_encode_scan), then write and
+// finish into the slots.  (WEAK references, as fg_launch_syslen above: without the kernels fg_udp_unpack_device answers
+// FG_ERR_UNSUPPORTED.  The product library always has them: build.py checks the link.)
+extern "C" int fg_launch_udp_count(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t max_inflated, uint32_t* d_sizes,
+                                   uint64_t* d_block_sums, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_udp_write(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                                   uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_udp_finish(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                                    uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
@@ -153,6 +162,17 @@ struct fg_ctx {
     uint64_t d_sl_starts_cap = 0;
     int last_syslen_stop = 0;        // fg_last_syslen_stop
     uint64_t last_syslen_payload = 0; // fg_frame_syslen_device: the payload bytes its last call packed (the host-buffer calls size the decode with it)
+    // fg_udp_decode_batch also BORROWS d_bytes (the datagrams), d_sl_packed (the payloads), d_offsets (their offsets), d_bad (the drop
+    // flags) and d_tab / h_tab from the frame / syslen / decode paths: every host-buffer call on a ctx synchronises before it returns,
+    // so no two of them have these buffers in use at once.
+    uint8_t* d_udp = nullptr;        // fg_udp_unpack_device: per-datagram sizes, then the per-64 sums of the scan
+    uint64_t d_udp_cap = 0;
+    uint64_t* d_udp_off = nullptr;   // fg_udp_decode_batch: the datagrams' offsets
+    uint64_t d_udp_off_cap = 0;
+    uint8_t* d_udp_st = nullptr;     // ... their fg_udp_status
+    uint64_t d_udp_st_cap = 0;
+    uint8_t* h_udp = nullptr;        // ... pinned: inflated lines | their offsets | fg_udp_status
+    uint64_t h_udp_cap = 0;
     uint8_t* d_bad = nullptr;    // fg_frame_decode_batch: per-frame UTF-8 verdicts
     uint64_t d_bad_cap = 0;
     uint64_t* h_off = nullptr;   // fg_frame_decode_batch: pinned host copy of the frame offsets

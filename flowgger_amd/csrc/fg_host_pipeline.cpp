@@ -986,6 +986,109 @@ static int frame_decode_fused(fg_ctx* ctx, fg_format fmt, fg_framing framing, co
     return FG_OK;
 }
 
+// The UDP input for a batch of datagrams in host memory (handle_record_maybe_compressed, input/udp_input.rs:100-143): one upload,
+// fg_udp_unpack_device into ctx-owned HBM (counted first, so the buffer is sized by what the batch inflates to), the decode of the
+// packed payloads as FG_FRAME_NONE with the drop flags as its UTF-8 verdicts, and the tables, the payloads, their offsets and the
+// per-datagram status back into pinned memory.  One piece: a datagram batch is small beside the chunks the sliced forms are for.
+int fg_udp_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, uint64_t n,
+                        uint64_t max_inflated, fg_tables* out, const uint8_t** out_lines, const uint64_t** out_line_offsets,
+                        const uint8_t** udp_status) {
+    if (!ctx || !out || !out_lines || !out_line_offsets || !udp_status || !offsets || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP) return FG_ERR_ARG;  // (the reference has no Decoder for it: config.rs picks the capnp splitter, not a decoder)
+    if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF && fmt != FG_RFC3164) return FG_ERR_ARG;
+    if (n && (offsets[0] != 0 || offsets[n] != nbytes)) return FG_ERR_ARG;
+    for (uint64_t i = 0; i < n; ++i)  // (one pass over host memory: an offset that runs backwards would reach the kernels as a huge length)
+        if (offsets[i] > offsets[i + 1]) return FG_ERR_ARG;
+    *out_lines = nullptr;
+    *out_line_offsets = nullptr;
+    *udp_status = nullptr;
+    fg_tables empty{};
+    *out = empty;
+    if (n == 0) return FG_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_off, &ctx->d_udp_off_cap, (n + 2) * 8)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 2) * 8)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, n + 1)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_st, &ctx->d_udp_st_cap, n + 1)) != FG_OK) return rc;
+    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    FG_HIP(ctx, hipMemcpyAsync(ctx->d_udp_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    // 1. unpack: the sizing call first, then into a buffer of that size (the count pass runs twice; it is the cheap half only for
+    //    batches of bare records -- the price of not guessing a compression ratio)
+    uint64_t total = 0;
+    if ((rc = fg_udp_unpack_device(ctx, ctx->d_bytes, nbytes, ctx->d_udp_off, n, max_inflated, nullptr, 0, ctx->d_offsets, ctx->d_bad, ctx->d_udp_st,
+                                   &total, FG_STREAM_OWN)) != FG_OK)
+        return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(total, 16) + 16)) != FG_OK) return rc;
+    if ((rc = fg_udp_unpack_device(ctx, ctx->d_bytes, nbytes, ctx->d_udp_off, n, max_inflated, ctx->d_sl_packed, total, ctx->d_offsets, ctx->d_bad,
+                                   ctx->d_udp_st, &total, FG_STREAM_OWN)) != FG_OK)
+        return rc;
+    // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + total, 0, up(total, 16) + 16 - total, s));
+    // 2. the payloads, their offsets and the status back to the host
+    const uint64_t lines_sz = up(total, 16) + 16, offs_sz = up((n + 1) * 8, 16), need = lines_sz + offs_sz + up(n, 16);
+    if (need > ctx->h_udp_cap) {
+        if (ctx->h_udp) FG_HIP(ctx, hipHostFree(ctx->h_udp));
+        ctx->h_udp = nullptr;
+        ctx->h_udp_cap = 0;
+        const uint64_t want = up(need + need / 4, 1 << 16);
+        FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_udp, want, hipHostMallocDefault));
+        ctx->h_udp_cap = want;
+    }
+    uint8_t* const h_lines = ctx->h_udp;
+    uint64_t* const h_offs = (uint64_t*)(ctx->h_udp + lines_sz);
+    uint8_t* const h_st = ctx->h_udp + lines_sz + offs_sz;
+    if (total) FG_HIP(ctx, hipMemcpyAsync(h_lines, ctx->d_sl_packed, total, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h_offs, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h_st, ctx->d_udp_st, n, hipMemcpyDeviceToHost, s));
+    // 3. decode the payloads where they lie (as the second half of frame_decode_one_piece)
+    uint64_t ent_cap = fmt == FG_RFC5424 ? total / 16 + 1024 : total / 8 + 1024;
+    for (;;) {
+        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
+        uint64_t bytes_total = 0;
+        carve(nullptr, n, ent_cap, nullptr, &bytes_total);
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, bytes_total)) != FG_OK) return rc;
+        if (bytes_total > ctx->h_tab_cap) {
+            if (ctx->h_tab) FG_HIP(ctx, hipHostFree(ctx->h_tab));
+            ctx->h_tab = nullptr;
+            ctx->h_tab_cap = 0;
+            const uint64_t want = up(bytes_total + bytes_total / 4, 1 << 20);
+            FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
+            ctx->h_tab_cap = want;
+        }
+        fg_tables dt, ht;
+        carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
+        carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
+        rc = fg_decode_frames_device(ctx, fmt, FG_FRAME_NONE, ctx->d_sl_packed, total, ctx->d_offsets, n, ctx->d_bad, &dt, FG_STREAM_OWN);
+        if (rc != FG_OK) return rc;
+        uint64_t used = 0;
+        FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        if (used > ent_cap) {
+            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
+            ent_cap = used + used / 8 + 1024;
+            continue;
+        }
+        uint64_t sizes[FG_TABLE_ARRAYS];
+        fg_tables_layout(n, used, sizes);
+        void* dsts[FG_TABLE_ARRAYS] = {ht.meta, ht.ts, ht.hostname, ht.appname, ht.procid, ht.msgid, ht.msg, ht.full_msg,
+                                       ht.ent_first, ht.ent_count, ht.ent_name, ht.ent_val, ht.ent_type, ht.ent_flags, ht.ent_used};
+        void* srcs[FG_TABLE_ARRAYS] = {dt.meta, dt.ts, dt.hostname, dt.appname, dt.procid, dt.msgid, dt.msg, dt.full_msg,
+                                       dt.ent_first, dt.ent_count, dt.ent_name, dt.ent_val, dt.ent_type, dt.ent_flags, dt.ent_used};
+        for (int k = 0; k < FG_TABLE_ARRAYS; ++k)
+            if (sizes[k]) FG_HIP(ctx, hipMemcpyAsync(dsts[k], srcs[k], sizes[k], hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        *out = ht;
+        *out_lines = h_lines;
+        *out_line_offsets = h_offs;
+        *udp_status = h_st;
+        return FG_OK;
+    }
+}
+
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
                           fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;

@@ -244,6 +244,48 @@ class Decoder:
         offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), (nf + 1,)).copy()
         return HostTables.from_struct(st), offsets, int(used.value)
 
+    # -- the UDP input (input/udp_input.rs:100-143) -------------------------------------------------------
+    def udp_decode_packed(self, data: np.ndarray, offsets: np.ndarray, max_inflated: Optional[int] = None):
+        """Datagrams back to back in, tables out (fg_udp_decode_batch: upload, inflate / copy + UTF-8 on the GPU, decode).  Returns
+        (HostTables, lines uint8, line_offsets uint64[n + 1], udp_status uint8[n]): the tables' spans are relative to the INFLATED
+        line i = lines[line_offsets[i]:line_offsets[i + 1]]; a dropped datagram has status FG_ST_BAD_UTF8 and its FG_UDP_* reason in
+        udp_status."""
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        st = L.fg_tables()
+        lines, offs, ust = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(L.lib().fg_udp_decode_batch(self._ctx, self.fmt, data.ctypes.data, data.size, offsets.ctypes.data, n, int(max_inflated or 0),
+                                            C.byref(st), C.byref(lines), C.byref(offs), C.byref(ust)), "fg_udp_decode_batch")
+        if n == 0:
+            return None, np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint8)
+        line_offsets = np.ctypeslib.as_array(C.cast(offs, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+        total = int(line_offsets[n])
+        out = np.zeros(total + 16, np.uint8)  # (the pad the host-side readers of a batch expect)
+        if total:
+            out[:total] = np.ctypeslib.as_array(C.cast(lines, C.POINTER(C.c_uint8)), (total,))
+        status = np.ctypeslib.as_array(C.cast(ust, C.POINTER(C.c_uint8)), (n,)).copy()
+        return HostTables.from_struct(st), out[:total], line_offsets, status
+
+    def decode_datagrams(self, datagrams: Sequence[bytes], max_inflated: Optional[int] = None) -> List[Union[Record, DecodeError]]:
+        """handle_record_maybe_compressed (input/udp_input.rs:100-143) for a list of UDP datagrams: each is a zlib stream, a gzip
+        member or a bare record; a Record or the DecodeError the reference prints per datagram ("Corrupted compressed (zlib) record",
+        "Corrupted compressed (gzip) record", "Invalid UTF-8 input", or the decoder's own).  max_inflated: the most a compressed
+        datagram may inflate to (None = 65 527 * 5); one beyond it is a DecodeError of this library's own -- inflate it on the host."""
+        data, offsets = pack_lines(datagrams)
+        if len(datagrams) == 0:
+            return []
+        tab, lines, line_offsets, ust = self.udp_decode_packed(data, offsets, max_inflated)
+        blob, offs = tab.serialize(self.fmt, lines, line_offsets, cfg=self._cfg)
+        raw = blob.tobytes()
+        out: List[Union[Record, DecodeError]] = []
+        for i in range(len(datagrams)):
+            if ust[i] > L.FG_UDP_GZIP:
+                out.append(DecodeError(L.lib().fg_udp_error_string(int(ust[i])).decode()))
+            else:
+                out.append(parse_canonical(raw[int(offs[i]):int(offs[i + 1])]))
+        return out
+
     # -- GELF encoder from the tables (SURVEY.md 8f-2) ------------------------------------------------
     def encode_gelf_device(self, d_bytes, d_offsets, n: int, tables: DeviceTables, extra: Optional[dict] = None, stream=None):
         """GelfEncoder::encode (encoder/gelf_encoder.rs:59-115) for every decoded line of `tables`, on the
@@ -279,6 +321,36 @@ class Decoder:
     def error_string(self, status: int) -> Optional[str]:
         s = L.lib().fg_error_string(self.fmt, status)
         return None if s is None else s.decode()
+
+
+class UdpUnpacker:
+    """The device-resident form of the UDP input's body (fg_udp_unpack_device): datagrams in HBM in, the payloads -- inflated where
+    they were compressed, UTF-8 checked -- packed in HBM out, ready for Decoder.decode_frames_device(..., FG_FRAME_NONE, d_bad=d_drop)."""
+
+    def __init__(self, decoder: Decoder, max_inflated: Optional[int] = None):
+        self.decoder = decoder
+        self.max_inflated = int(max_inflated or 0)
+
+    def unpack(self, d_bytes, d_offsets, stream=None):
+        """d_bytes uint8, d_offsets int64[n + 1] (torch tensors in HBM) -> (d_out uint8, d_out_offsets int64[n + 1], d_drop uint8[n],
+        d_udp_status uint8[n]).  Synchronises the stream twice (the size, then the result)."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        n = d_offsets.numel() - 1
+        dev = d_bytes.device
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_drop = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        d_st = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        total = C.c_uint64()
+        args = (self.decoder._ctx, d_bytes.data_ptr(), d_bytes.numel(), d_offsets.data_ptr(), n, self.max_inflated)
+        tail = (d_off.data_ptr(), d_drop.data_ptr(), d_st.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
+        L.check(L.lib().fg_udp_unpack_device(*args, None, 0, *tail), "fg_udp_unpack_device (size)")
+        cap = int(total.value)
+        d_out = torch.zeros((cap + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+        L.check(L.lib().fg_udp_unpack_device(*args, d_out.data_ptr(), cap, *tail), "fg_udp_unpack_device")
+        return d_out[:cap], d_off, d_drop[:n], d_st[:n]
 
 
 class RFC5424Decoder(Decoder):

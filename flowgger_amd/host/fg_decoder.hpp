@@ -802,6 +802,106 @@ class MicroBatcher {
 };
 
 
+// ---------------------------------------------------------------------------------------------
+// The UDP input with its body on the GPU: handle_record_maybe_compressed (input/udp_input.rs:100-143) for a batch.  Datagrams are
+// parked as they arrive -- zlib streams, gzip members and bare records alike -- and one fg_udp_decode_batch call inflates, checks
+// UTF-8 and decodes them; no host core touches a payload.  Flushes by FlushPolicy (max_lines datagrams, max_bytes, max_latency_ms
+// for the first one parked).  A dropped datagram is reported as the reference reports it, `writeln!(stderr(), "{}", e)`
+// (udp_input.rs:84-86): "Corrupted compressed (zlib) record", "Corrupted compressed (gzip) record", "Invalid UTF-8 input" or the
+// decoder's own error.  max_inflated: include/fg_hip.h (0 = the default); a datagram beyond it is reported with the library's text
+// for FG_UDP_TOO_LARGE and handed to `too_large`, when given, to be inflated on the host.  The receive loop of udp_input.rs:78-88:
+//     for (;;) { n = recv(sock, buf, timeout = ub.wait_ms()); if (n > 0) ub.push({buf, n}); ub.poll(); }
+// ---------------------------------------------------------------------------------------------
+class UdpBatcher {
+  public:
+    using TooLarge = std::function<void(std::string_view datagram)>;
+    UdpBatcher(const Decoder& d, RecordSink sink, std::ostream& err, const FlushPolicy& pol = FlushPolicy(), uint64_t max_inflated = 0,
+               TooLarge too_large = nullptr)
+        : d_(d), sink_(std::move(sink)), pol_(pol), err_(&err), max_inflated_(max_inflated), too_large_(std::move(too_large)) {
+        offsets_.assign(1, 0);
+    }
+    ~UdpBatcher() {
+        try { flush(); } catch (...) {}
+    }
+    void push(std::string_view datagram) {
+        if (offsets_.size() == 1) t0_ = std::chrono::steady_clock::now();
+        bytes_.insert(bytes_.end(), datagram.begin(), datagram.end());
+        offsets_.push_back(bytes_.size());
+        if (offsets_.size() - 1 >= pol_.max_lines || bytes_.size() >= pol_.max_bytes) flush();
+    }
+    // how long the caller may block in its receive call before poll() is due: -1 = nothing is parked
+    int wait_ms() const {
+        if (offsets_.size() == 1) return -1;
+        const auto waited = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0_).count();
+        return waited >= pol_.max_latency_ms ? 0 : (int)(pol_.max_latency_ms - waited);
+    }
+    void poll() {
+        if (offsets_.size() > 1 && wait_ms() == 0) flush();
+    }
+    void flush() {
+        const uint64_t n = offsets_.size() - 1;
+        if (n == 0) return;
+        const uint64_t nbytes = offsets_.back();
+        bytes_.resize(nbytes + 16);  // readable slack (the data itself is not touched)
+        // (whatever happens below, the slack goes again: a failed flush leaves the datagrams parked as they were, for the caller to
+        //  retry or drop(); one that got as far as the sinks has handed them over)
+        struct Unslack {
+            std::vector<uint8_t>& b;
+            uint64_t n;
+            ~Unslack() { b.resize(n); }
+        } unslack{bytes_, nbytes};
+        fg_tables t{};
+        const uint8_t* lines = nullptr;
+        const uint64_t* loffs = nullptr;
+        const uint8_t* ust = nullptr;
+        const int rc = fg_udp_decode_batch(d_.ctx(), d_.format(), bytes_.data(), nbytes, offsets_.data(), n, max_inflated_, &t, &lines, &loffs, &ust);
+        if (rc != FG_OK) throw std::runtime_error("fg_udp_decode_batch failed: " + std::to_string(rc));
+        Decoder::side_effects(d_.format(), FG_FRAME_NONE, lines, loffs, t);
+        std::vector<uint64_t> offs(n + 1);
+        const int64_t total = fg_tables_serialize(d_.format(), d_.cfg_ptr(), lines, loffs, &t, 0, n, nullptr, 0, offs.data());
+        if (total < 0) throw std::runtime_error("fg_tables_serialize failed");
+        std::vector<uint8_t> blob((size_t)total + 1);
+        fg_tables_serialize(d_.format(), d_.cfg_ptr(), lines, loffs, &t, 0, n, blob.data(), (uint64_t)total, offs.data());
+        // from here on the batch is consumed, whatever a sink throws: take it out of the parked state first
+        std::vector<uint8_t> taken;
+        std::vector<uint64_t> taken_offs(1, 0);
+        taken.swap(bytes_);
+        taken_offs.swap(offsets_);
+        unslack.n = 0;
+        std::ostream& err = *err_;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (ust[i] > FG_UDP_GZIP) {
+                err << fg_udp_error_string(ust[i]) << "\n";
+                if (ust[i] == FG_UDP_TOO_LARGE && too_large_)
+                    too_large_(std::string_view((const char*)taken.data() + taken_offs[i], taken_offs[i + 1] - taken_offs[i]));
+                continue;
+            }
+            DecodeResult r = detail::from_canonical(blob.data() + offs[i], d_.format(), FG_META_STATUS(t.meta[i]));
+            if (r.ok()) sink_(std::move(r.record));
+            else err << r.err << "\n";
+        }
+    }
+    // forget what is parked (after a flush that failed for good)
+    void drop() {
+        bytes_.clear();
+        offsets_.assign(1, 0);
+    }
+    size_t pending_bytes() const { return bytes_.size(); }
+    size_t pending() const { return offsets_.size() - 1; }
+
+  private:
+    const Decoder& d_;
+    RecordSink sink_;
+    FlushPolicy pol_;
+    std::ostream* err_;
+    uint64_t max_inflated_;
+    TooLarge too_large_;
+    std::vector<uint8_t> bytes_;
+    std::vector<uint64_t> offsets_;
+    std::chrono::steady_clock::time_point t0_{};
+};
+
+
 // LineSplitter / NulSplitter with the framing itself on the GPU: raw chunks of the stream go to
 // fg_frame_decode_batch (framing + UTF-8 validation + decode in one call); the host only carries an
 // unterminated tail over to the next chunk and reports like the reference.

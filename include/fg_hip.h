@@ -375,6 +375,54 @@ int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const
                            uint64_t* d_offsets, uint64_t cap_frames, const fg_tables* tables, uint64_t avg_line_hint,
                            uint64_t* d_result, void* stream);
 
+/* THE UDP INPUT'S BODY ON THE GPU (input.type = "udp"; replaces handle_record_maybe_compressed, src/flowgger/input/udp_input.rs:
+ * 100-143, up to decoder.decode, for a batch of datagrams).  A datagram is a zlib stream when it has at least 8 bytes, byte 0 is 0x78
+ * and byte 1 is 0x01, 0x9c or 0xda; a gzip member when it has at least 24 bytes and starts 1f 8b 08; a bare record otherwise.
+ * Compressed payloads are inflated (RFC 1950 / 1951 / 1952 in full, with zlib's notion of what is malformed; the first gzip member
+ * only; bytes behind the trailer ignored), every payload is checked as str::from_utf8 does, and the payloads come out PACKED, the
+ * FG_FRAME_NONE convention everything downstream takes.
+ *
+ * DEPARTURE FROM THE REFERENCE: max_inflated.  The reference inflates without a limit (its Vec::with_capacity(65_527 * 5) is a
+ * reservation); a GPU that others share needs one.  A compressed datagram that inflates to more than max_inflated bytes is
+ * dropped with FG_UDP_TOO_LARGE and is the caller's to inflate on the host; nothing beyond max_inflated + 1 bytes of it is ever
+ * produced.  0 = FG_UDP_DEFAULT_MAX_INFLATED (that same product).  Bare records are not subject to it.
+ * The verdicts are zlib's with max_inflated + 1 bytes of room, in this order: a malformation met within that room is BAD_*, then more
+ * than max_inflated bytes is TOO_LARGE, then a stream that did not end is BAD_*.  One consequence: a stream that ENDS at exactly
+ * max_inflated + 1 bytes is inflated once, because zlib had the room to reach its trailer -- a wrong checksum makes it BAD_*, a right
+ * one leaves it TOO_LARGE, and either way the dropped row occupies max_inflated + 1 bytes of d_out and of *total. */
+typedef enum fg_udp_status {
+    FG_UDP_RAW = 0,       /* kept: a bare record */
+    FG_UDP_ZLIB = 1,      /* kept: inflated from a zlib stream */
+    FG_UDP_GZIP = 2,      /* kept: inflated from a gzip member */
+    FG_UDP_BAD_ZLIB = 3,  /* dropped: "Corrupted compressed (zlib) record" */
+    FG_UDP_BAD_GZIP = 4,  /* dropped: "Corrupted compressed (gzip) record" */
+    FG_UDP_BAD_UTF8 = 5,  /* dropped: "Invalid UTF-8 input" (bare or inflated) */
+    FG_UDP_TOO_LARGE = 6  /* dropped: inflates beyond max_inflated (this library's own; see above) */
+} fg_udp_status;
+#define FG_UDP_DEFAULT_MAX_INFLATED 327635u   /* 65_527 * 5 */
+#define FG_UDP_MAX_MAX_INFLATED 0x7FFFFFF0u
+/* What the reference prints for a dropped datagram (udp_input.rs:84-86 prints the error of :113 / :124 / :136): "" for the three
+ * kept values, a text of this library's own for FG_UDP_TOO_LARGE, NULL for an unknown value. */
+const char* fg_udp_error_string(uint8_t st);
+/*   d_bytes, d_offsets   the datagrams back to back (device-addressable): datagram i = d_bytes[d_offsets[i] .. d_offsets[i + 1])
+ *   max_inflated         see above; at most FG_UDP_MAX_MAX_INFLATED
+ *   d_out                out: the payloads, 16-byte aligned and writable up to out_cap ROUNDED UP TO 16 (what fg_decode_frames_device
+ *                        reads).  NULL = the sizing call, as for fg_encode_device: only *total and d_out_offsets are produced
+ *   d_out_offsets        out, n + 1 entries into d_out: payload i = [off[i], off[i + 1]).  A datagram dropped for its STREAM
+ *                        (FG_UDP_BAD_ZLIB / _BAD_GZIP / _TOO_LARGE) has an empty payload, with two exceptions that show only once
+ *                        the bytes exist: a stream that is whole, trailer included, and whose checksum (or gzip ISIZE) alone
+ *                        disagrees keeps the bytes it produced, flagged BAD_*; and the TOO_LARGE row of exactly max_inflated + 1
+ *                        bytes described above keeps those.  FG_UDP_BAD_UTF8 keeps its bytes
+ *   d_drop               out, n bytes: nonzero = not to be decoded.  Goes straight into the d_bad_utf8 argument of
+ *                        fg_decode_frames_device(..., FG_FRAME_NONE, ...): those rows come back with FG_ST_BAD_UTF8
+ *   d_udp_status         out, n bytes: an fg_udp_status each, the real reason
+ *   total                out (host): the bytes the payloads take.  The call synchronises the stream to read it.  With d_out given and
+ *                        *total > out_cap nothing is written: FG_ERR_ENT_OVERFLOW, the need in *total
+ * One lane walks one datagram, so a batch wants thousands of them; a single large stream is not what this is for. */
+int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n,
+                         uint64_t max_inflated, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets,
+                         uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, void* stream);
+
 /* HOST-BUFFER decode: the batch is decoded into ctx-owned pinned host memory (`out` is filled with host pointers valid until
  * the next call on this ctx or fg_destroy).  Synchronous.  Entry-table capacity grows automatically.
  *   `bytes` AND `offsets` in PINNED memory (fg_alloc_pinned / hipHostRegister: where the batching framer accumulates lines),
@@ -407,6 +455,16 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes,
                           uint64_t nbytes, int final, fg_tables* out, const uint64_t** out_offsets,
                           uint64_t* n_frames, uint64_t* consumed);
+
+/* HOST-BUFFER UDP decode: upload the datagrams, fg_udp_unpack_device, decode -- the whole of handle_record_maybe_compressed for a
+ * batch.  `bytes` / `offsets` pinned or pageable.  `out`: tables in ctx-owned pinned host memory, n rows; a dropped datagram has
+ * status FG_ST_BAD_UTF8 and (*udp_status)[i] says why.  *out_lines / *out_line_offsets (n + 1 entries): the payloads as decoded, in
+ * ctx-owned pinned memory -- the spans in `out` are relative to line i = (*out_lines)[off[i] .. off[i + 1]), NOT to the datagram, so
+ * a caller needs them to materialise Records.  FG_CAPNP is rejected (FG_ERR_ARG): the reference has no Decoder for it.  Everything
+ * returned stays valid until the next call on this ctx.  fg_last_host_path is not touched. */
+int fg_udp_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, uint64_t n,
+                        uint64_t max_inflated, fg_tables* out, const uint8_t** out_lines, const uint64_t** out_line_offsets,
+                        const uint8_t** udp_status);
 
 /* Which form the last fg_decode_batch / fg_frame_decode_batch call on this ctx took (0 = none yet): the library picks by what the
  * caller's buffers allow, silently -- a harness that prices a leg against the link, or a test of one form, asks afterwards. */
