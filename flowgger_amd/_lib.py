@@ -22,7 +22,9 @@ LIB_PATH = _HERE / (_ALT or ("libfg_hip_prof.so" if os.environ.get("FLOWGGER_AMD
 FG_ABI_VERSION = 4  # include/fg_hip.h
 FG_RFC5424, FG_LTSV, FG_GELF, FG_RFC3164, FG_CAPNP = 0, 1, 2, 3, 4
 FG_EF_VAL_ESC, FG_EF_NAME_ESC, FG_EF_SUFFIX, FG_EF_NAME_VERBATIM = 1, 2, 4, 8  # entry flags (include/fg_hip.h)
-FG_FRAME_NONE, FG_FRAME_LINE, FG_FRAME_NUL, FG_FRAME_SYSLEN = 0, 1, 2, 3
+FG_FRAME_NONE, FG_FRAME_LINE, FG_FRAME_NUL, FG_FRAME_SYSLEN, FG_FRAME_CAPNP = 0, 1, 2, 3, 4
+FG_CAPNP_CLEAN, FG_CAPNP_TAIL, FG_CAPNP_TOO_MANY_SEGMENTS, FG_CAPNP_TOO_LARGE = 0, 1, 2, 3  # fg_capnp_stop
+FG_CAPNP_FRAME_MAX_BYTES = 0xFFFF0000
 FG_SYSLEN_CLEAN, FG_SYSLEN_TAIL, FG_SYSLEN_BAD_LEN, FG_SYSLEN_LONG_PREFIX = 0, 1, 2, 3  # fg_syslen_stop
 FG_SYSLEN_MAX_PREFIX = 24
 FG_UDP_RAW, FG_UDP_ZLIB, FG_UDP_GZIP, FG_UDP_BAD_ZLIB, FG_UDP_BAD_GZIP, FG_UDP_BAD_UTF8, FG_UDP_TOO_LARGE = range(7)  # fg_udp_status
@@ -93,6 +95,7 @@ FG_LO_NO_FUSED_FRAMING = 16384
 FG_LO_RFC3164_REGROUP, FG_LO_RFC3164_NO_REGROUP = 32768, 65536
 FG_PATH_DECODE_ZERO_COPY, FG_PATH_DECODE_SLICED, FG_PATH_FRAME_FUSED, FG_PATH_FRAME_SLICED, FG_PATH_FRAME_ONE_PIECE = 1, 2, 3, 4, 5
 FG_PATH_FRAME_SYSLEN_DEVICE, FG_PATH_FRAME_SYSLEN_HOST = 6, 7
+FG_PATH_FRAME_CAPNP_DEVICE, FG_PATH_FRAME_CAPNP_HOST = 8, 9
 FG_LO_RESERVED = 0x40000000  # the library's own (fg_set_launch_opts clears it)
 
 
@@ -187,6 +190,8 @@ def lib() -> C.CDLL:
     L.fg_decode_frames_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, vp, u64, vp, C.POINTER(fg_tables), vp]
     L.fg_last_host_path.argtypes = [vp]
     L.fg_last_syslen_stop.argtypes = [vp]
+    L.fg_last_capnp_stop.argtypes = [vp]
+    L.fg_frame_capnp_device.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), vp]
     L.fg_frame_syslen_device.argtypes = [vp, vp, u64, C.c_int, vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), vp]
     L.fg_udp_error_string.argtypes = [C.c_uint8]
     L.fg_udp_error_string.restype = C.c_char_p

@@ -95,6 +95,7 @@ extern "C" {
 int fg_abi_version(void) { return FG_ABI_VERSION; }
 int fg_last_host_path(const fg_ctx* ctx) { return ctx ? ctx->last_host_path : 0; }
 int fg_last_syslen_stop(const fg_ctx* ctx) { return ctx ? ctx->last_syslen_stop : 0; }
+int fg_last_capnp_stop(const fg_ctx* ctx) { return ctx ? ctx->last_capnp_stop : 0; }
 
 int fg_tables_layout(uint64_t n, uint64_t ent_cap, uint64_t sizes[FG_TABLE_ARRAYS]) {
     if (!sizes) return FG_ERR_ARG;
@@ -438,6 +439,39 @@ int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
     *consumed = hdr[3];
     *stop_reason = (int)hdr[1];
     ctx->last_syslen_payload = hdr[4];
+    return FG_OK;
+}
+
+// replaces the walk of capnp::serialize::read_message over the segment tables in CapnpSplitter::run (splitter/capnp_splitter.rs:24-46)
+int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint64_t* d_offsets, uint64_t cap_frames,
+                          uint64_t* n_frames, uint64_t* consumed, int* stop_reason, void* stream) {
+    (void)final;  // (a message needs its whole body either way; what a TAIL means at the end of the stream is the caller's business)
+    if (!ctx || !d_offsets || !n_frames || !consumed || !stop_reason || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;
+    *n_frames = 0;
+    *consumed = 0;
+    *stop_reason = FG_CAPNP_CLEAN;
+    if (nbytes > FG_CAPNP_FRAME_MAX_BYTES) return FG_ERR_ARG;  // (the scratch keeps word indices in 29 bits)
+    if (!fg_launch_capnp_frame || !fg_capnp_frame_max_bytes || !fg_capnp_frame_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    if (nbytes > fg_capnp_frame_max_bytes()) return FG_ERR_ARG;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_capnp_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
+    uint32_t* d_hdr = nullptr;
+    const int lrc = fg_launch_capnp_frame(d_bytes, nbytes, ctx->d_frame, d_offsets, cap_frames, &d_hdr, s);
+    if (lrc != 0) {
+        ctx->last_hip = lrc;
+        return FG_ERR_HIP;
+    }
+    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (hdr[0] != 0 || hdr[4] != 1) return FG_ERR_UNSUPPORTED;  // declined: more nodes than the store holds
+    *n_frames = hdr[2];
+    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
+    *consumed = (uint64_t)hdr[3] * 8u;
+    *stop_reason = (int)hdr[1];
     return FG_OK;
 }
 

@@ -69,6 +69,13 @@ extern "C" uint64_t fg_syslen_scratch_bytes(uint64_t nbytes) __attribute__((weak
 extern "C" uint64_t fg_syslen_max_bytes(void) __attribute__((weak));
 extern "C" int fg_launch_syslen(const uint8_t* d_bytes, uint64_t nbytes, uint8_t* scratch, uint8_t* d_packed, uint64_t* d_offsets,
                                 uint64_t* d_starts, uint8_t* d_bad, uint64_t cap, uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
+// the Cap'n Proto stream framer (fg_capnp_frame.hip): *d_hdr_out = its result words in device memory (fg::capnpf H_*).  (WEAK references,
+// as fg_launch_syslen above: without the kernels fg_frame_capnp_device answers FG_ERR_UNSUPPORTED and the host-buffer entry points walk
+// the segment tables on the host.  The product library always has them: build.py checks the link.)
+extern "C" uint64_t fg_capnp_frame_scratch_bytes(uint64_t nbytes) __attribute__((weak));
+extern "C" uint64_t fg_capnp_frame_max_bytes(void) __attribute__((weak));
+extern "C" int fg_launch_capnp_frame(const uint8_t* d_bytes, uint64_t nbytes, uint8_t* scratch, uint64_t* d_offsets, uint64_t cap,
+                                     uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
 // the UDP input's unpacker (fg_udp.hip): count (sizes + per-64 sums; the scan between the two is fg_launch_encode_scan), then write and
 // finish into the slots.  (WEAK references, as fg_launch_syslen above: without the kernels fg_udp_unpack_device answers
 // FG_ERR_UNSUPPORTED.  The product library always has them: build.py checks the link.)
@@ -161,6 +168,7 @@ struct fg_ctx {
     uint64_t* d_sl_starts = nullptr; // ... the frame starts in the caller's chunk
     uint64_t d_sl_starts_cap = 0;
     int last_syslen_stop = 0;        // fg_last_syslen_stop
+    int last_capnp_stop = 0;         // fg_last_capnp_stop
     uint64_t last_syslen_payload = 0; // fg_frame_syslen_device: the payload bytes its last call packed (the host-buffer calls size the decode with it)
     // fg_udp_decode_batch also BORROWS d_bytes (the datagrams), d_sl_packed (the payloads), d_offsets (their offsets), d_bad (the drop
     // flags) and d_tab / h_tab from the frame / syslen / decode paths: every host-buffer call on a ctx synchronises before it returns,

@@ -8,6 +8,7 @@
 
 #include "fg_ctx.hpp"
 #include "fg_syslen_parse.hpp"
+#include "fg_capnp_next.hpp"
 
 extern "C" {
 
@@ -599,16 +600,53 @@ static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int 
     return FG_OK;
 }
 
+// FG_FRAME_CAPNP stage shared by fg_frame_decode_batch and fg_transcode_batch (the read_message loop of CapnpSplitter::run,
+// capnp_splitter.rs:24-46, for a chunk): the chunk is already in ctx->d_bytes (zero padded) and is framed where it lies; the decoders
+// then read the messages from the same buffer.  When the device framer declines (fg_frame_capnp_device: FG_ERR_UNSUPPORTED) the segment
+// tables are walked on the host over the caller's bytes and the offsets are uploaded: the same results either way.  Leaves the message
+// offsets in ctx->d_offsets (n + 1 entries).
+static int capnp_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int final, uint64_t* n_frames, uint64_t* consumed) {
+    hipStream_t s = ctx->stream;
+    int rc, stop = FG_CAPNP_CLEAN;
+    // (a message of the record schema is a few hundred bytes; a cap_frames that turns out too small runs the framer again with the
+    //  count it reported, like syslen_stage)
+    uint64_t cap = nbytes / 64 + 1024, n = 0;
+    for (;;) {
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
+        rc = fg_frame_capnp_device(ctx, ctx->d_bytes, nbytes, final, ctx->d_offsets, cap, &n, consumed, &stop, FG_STREAM_OWN);
+        if (rc != FG_ERR_ENT_OVERFLOW) break;
+        cap = n + 16;
+    }
+    if (rc == FG_OK) {
+        ctx->last_host_path = FG_PATH_FRAME_CAPNP_DEVICE;
+    } else if (rc == FG_ERR_UNSUPPORTED) {
+        std::vector<uint64_t> offs;
+        stop = (int)fg::capnpf::host_walk(bytes, nbytes, consumed, [&](uint64_t p) { offs.push_back(p); });
+        offs.push_back(*consumed);
+        n = offs.size() - 1;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 2) * 8)) != FG_OK) return rc;
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));  // (the vector goes out of scope)
+        ctx->last_host_path = FG_PATH_FRAME_CAPNP_HOST;
+    } else {
+        return rc;
+    }
+    ctx->last_capnp_stop = stop;
+    *n_frames = n;
+    return FG_OK;
+}
+
 static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
                                   fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (fmt == FG_CAPNP) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
-    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN) return FG_ERR_UNSUPPORTED;
-    const bool syslen = framing == FG_FRAME_SYSLEN;
+    if ((fmt == FG_CAPNP) != (framing == FG_FRAME_CAPNP)) return FG_ERR_ARG;  // (a capnp stream has its own framing, and nothing else has it)
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN && framing != FG_FRAME_CAPNP) return FG_ERR_UNSUPPORTED;
+    const bool syslen = framing == FG_FRAME_SYSLEN, capnp = framing == FG_FRAME_CAPNP;
     *n_frames = 0;
     *consumed = 0;
     *out_offsets = nullptr;
     if (syslen) ctx->last_syslen_stop = FG_SYSLEN_CLEAN;
+    if (capnp) ctx->last_capnp_stop = FG_CAPNP_CLEAN;
     if (nbytes == 0) return FG_OK;
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
@@ -621,8 +659,10 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
         if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
         FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
         FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
-        // 1. frame: offsets + UTF-8 verdicts
-        if ((rc = frame_stage(ctx, framing, nbytes, final, &n, consumed)) != FG_OK) return rc;
+        // 1. frame: offsets + UTF-8 verdicts (a capnp stream: offsets only, Text is checked by the decoder)
+        if (capnp) rc = capnp_stage(ctx, bytes, nbytes, final, &n, consumed);
+        else rc = frame_stage(ctx, framing, nbytes, final, &n, consumed);
+        if (rc != FG_OK) return rc;
     }
     *n_frames = n;
     if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
@@ -645,7 +685,7 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
     // 2. decode the frames in place (terminators stripped in-kernel, invalid UTF-8 -> FG_ST_BAD_UTF8)
     const uint64_t used_bytes = syslen ? payload : *consumed;
     const uint8_t* const dec_bytes = syslen ? ctx->d_sl_packed : ctx->d_bytes;
-    const fg_framing dec_framing = syslen ? FG_FRAME_NONE : framing;
+    const fg_framing dec_framing = syslen || capnp ? FG_FRAME_NONE : framing;
     uint64_t ent_cap = fmt == FG_RFC5424 ? used_bytes / 16 + 1024 : used_bytes / 8 + 1024;
     for (;;) {
         if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
@@ -663,7 +703,7 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
         fg_tables dt, ht;
         carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
         carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
-        rc = fg_decode_frames_device(ctx, fmt, dec_framing, dec_bytes, used_bytes, ctx->d_offsets, n, ctx->d_bad, &dt, FG_STREAM_OWN);
+        rc = fg_decode_frames_device(ctx, fmt, dec_framing, dec_bytes, used_bytes, ctx->d_offsets, n, capnp ? nullptr : ctx->d_bad, &dt, FG_STREAM_OWN);
         if (rc != FG_OK) return rc;
         uint64_t used = 0;
         FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
@@ -1092,8 +1132,9 @@ int fg_udp_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
                           fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (!ctx || !out || !out_offsets || !n_frames || !consumed || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN) return FG_ERR_UNSUPPORTED;
-    if (framing == FG_FRAME_SYSLEN) {  // (one piece: framed + packed where the chunk lies, then the packed batch is decoded)
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL && framing != FG_FRAME_SYSLEN && framing != FG_FRAME_CAPNP) return FG_ERR_UNSUPPORTED;
+    if (framing == FG_FRAME_CAPNP && fmt != FG_CAPNP) return FG_ERR_ARG;
+    if (framing == FG_FRAME_SYSLEN || framing == FG_FRAME_CAPNP) {  // (one piece: framed where the chunk lies -- syslen: and packed --, then decoded)
         const int rc = frame_decode_one_piece(ctx, fmt, framing, bytes, nbytes, final, out, out_offsets, n_frames, consumed);
         if (rc != FG_OK) ctx->last_host_path = 0;
         return rc;
@@ -1411,10 +1452,12 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
 int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* ecfg, const uint8_t* bytes,
                        uint64_t nbytes, const uint64_t* offsets, uint64_t n, int final, fg_transcoded* out) {
     if (!ctx || !ecfg || !out || (nbytes && !bytes)) return FG_ERR_ARG;
-    if ((int)framing < 0 || (int)framing > (int)FG_FRAME_SYSLEN) return FG_ERR_ARG;
-    if (fmt == FG_CAPNP && framing != FG_FRAME_NONE) return FG_ERR_ARG;  // (a capnp stream is framed on the host: CapnpFramer)
-    const bool syslen = framing == FG_FRAME_SYSLEN;
+    if ((int)framing < 0 || (int)framing > (int)FG_FRAME_CAPNP) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP && framing != FG_FRAME_NONE && framing != FG_FRAME_CAPNP) return FG_ERR_ARG;  // (a capnp stream has its own framing,
+    if (fmt != FG_CAPNP && framing == FG_FRAME_CAPNP) return FG_ERR_ARG;                               //  and nothing else has it)
+    const bool syslen = framing == FG_FRAME_SYSLEN, capnp = framing == FG_FRAME_CAPNP;
     if (syslen) ctx->last_syslen_stop = FG_SYSLEN_CLEAN;
+    if (capnp) ctx->last_capnp_stop = FG_CAPNP_CLEAN;
     if (framing == FG_FRAME_NONE) {
         if (n && !offsets) return FG_ERR_ARG;
         if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
@@ -1456,6 +1499,9 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     } else if (framing == FG_FRAME_NONE) {
         if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 1) * 8)) != FG_OK) return rc;
         if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    } else if (capnp) {  // (framed where the chunk lies; what is decoded are the messages in ctx->d_bytes, FG_FRAME_NONE offsets)
+        if ((rc = capnp_stage(ctx, bytes, nbytes, final, &n, &consumed)) != FG_OK) return rc;
+        dec_framing = FG_FRAME_NONE;
     } else {
         if ((rc = frame_stage(ctx, framing, nbytes, final, &n, &consumed)) != FG_OK) return rc;
         d_bad = ctx->d_bad;

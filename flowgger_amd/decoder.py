@@ -189,6 +189,40 @@ class Decoder:
             k = int(n.value)
             return d_packed, d_offsets[:k + 1], d_starts[:k + 1], d_bad[:k], k, int(consumed.value), int(stop.value)
 
+    def frame_capnp_device(self, d_bytes, final: bool = True, cap_frames: Optional[int] = None, stream=None):
+        """Frame a Cap'n Proto stream resident in HBM (fg_frame_capnp_device): the walk of capnp::serialize::read_message over the
+        segment tables in CapnpSplitter::run (splitter/capnp_splitter.rs:24-46).  Returns (d_offsets int64[n + 1] into d_bytes --
+        message i = d_bytes[off[i]:off[i + 1]], its segment table included: with d_bytes what decode_frames_device(...,
+        FG_FRAME_NONE) takes --, n, consumed, stop_reason (an FG_CAPNP_*)).  Nothing is packed and no UTF-8 pass runs.
+        FgError(FG_ERR_UNSUPPORTED) when the device path declines the chunk: walk it on the host (CapnpFramer.frame).  d_bytes must
+        start at a 16-byte aligned address and its memory must be readable up to numel() rounded up to 16."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        nbytes = d_bytes.numel()
+        cap = cap_frames if cap_frames is not None else nbytes // 64 + 16
+        while True:
+            d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=d_bytes.device)
+            n, consumed, stop = C.c_uint64(), C.c_uint64(), C.c_int()
+            rc = L.lib().fg_frame_capnp_device(self._ctx, d_bytes.data_ptr(), nbytes, int(final), d_offsets.data_ptr(), cap, C.byref(n),
+                                               C.byref(consumed), C.byref(stop), C.c_void_p(stream.cuda_stream))
+            if rc == L.FG_ERR_ENT_OVERFLOW and cap_frames is None:
+                cap = int(n.value) + 16
+                continue
+            L.check(rc, "fg_frame_capnp_device")
+            k = int(n.value)
+            return d_offsets[:k + 1], k, int(consumed.value), int(stop.value)
+
+    def last_capnp_stop(self) -> int:
+        """how the chain of segment tables of the last FG_FRAME_CAPNP frame_decode_batch / Pipeline.run_stream on this decoder ended
+        (FG_CAPNP_*)"""
+        return int(L.lib().fg_last_capnp_stop(self._ctx))
+
+    def last_host_path(self) -> int:
+        """which form the last host-buffer call on this decoder took (FG_PATH_*)"""
+        return int(L.lib().fg_last_host_path(self._ctx))
+
     def last_syslen_stop(self) -> int:
         """how the prefix chain of the last FG_FRAME_SYSLEN frame_decode_batch / Pipeline.run_stream on this decoder ended (FG_SYSLEN_*)"""
         return int(L.lib().fg_last_syslen_stop(self._ctx))
@@ -229,7 +263,9 @@ class Decoder:
         (HostTables, offsets uint64[n+1], consumed): frame i = raw[offsets[i]:offsets[i+1]] including
         its terminator; raw[consumed:] is an unterminated tail to carry over (empty when `final`).
         framing = FG_FRAME_SYSLEN (the loop of SyslenSplitter::run): frame i starts with its "<len> " prefix and the tables' spans are
-        relative to its payload; last_syslen_stop() says how the chain ended at `consumed`."""
+        relative to its payload; last_syslen_stop() says how the chain ended at `consumed`.
+        framing = FG_FRAME_CAPNP (CapnpDecoder only; the read_message loop of CapnpSplitter::run): frame i is one whole message, its
+        segment table included; last_capnp_stop() says how the chain ended at `consumed`."""
         buf = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, np.uint8)
         padded = np.zeros(buf.size + 16, np.uint8)
         padded[:buf.size] = buf
@@ -449,6 +485,37 @@ class CapnpFramer:
         return len(self._carry)
 
 
+class _GpuCapnpCarry:
+    """The carry-over of the gpu_framing routes of CapnpSplitter / CapnpTranscodingSplitter: what CapnpFramer.feed does around the walk,
+    around FG_FRAME_CAPNP calls instead.  The tail behind `consumed` is kept for the next chunk; a table that ends the connection
+    raises the CapnpStreamError CapnpFramer would -- after the whole messages in front of it have been returned, at once when there
+    are none."""
+
+    def __init__(self):
+        self._carry = b""
+        self._ended = None
+
+    def begin(self, chunk: bytes) -> bytes:
+        if self._ended is not None:
+            raise self._ended
+        return self._carry + bytes(chunk)
+
+    def end(self, buf: bytes, n: int, consumed: int, stop: int) -> None:
+        self._carry = buf[consumed:]
+        if stop in (L.FG_CAPNP_TOO_MANY_SEGMENTS, L.FG_CAPNP_TOO_LARGE):
+            try:
+                CapnpFramer.frame(self._carry)  # (the text of the error: the few words of the table at `consumed`)
+                raise AssertionError("the device framer stopped at a table the host walk accepts")
+            except CapnpStreamError as e:
+                self._ended = e
+            if n == 0:
+                raise self._ended
+
+    @property
+    def pending(self) -> int:
+        return len(self._carry)
+
+
 class CapnpDecoder(Decoder):
     """handle_message of src/flowgger/splitter/capnp_splitter.rs:65-167 (input.format = "capnp"; the reference has no Decoder for
     it: the splitter reads Records off the wire itself).  A "line" is one whole message, segment table included."""
@@ -466,16 +533,26 @@ class CapnpSplitter:
     """CapnpSplitter::run (splitter/capnp_splitter.rs:15-63) without the encoder: chunks of the stream in, Records (or the
     DecodeError the reference prints) out, in stream order."""
 
-    def __init__(self, decoder: Optional[CapnpDecoder] = None, device: int = 0):
+    def __init__(self, decoder: Optional[CapnpDecoder] = None, device: int = 0, gpu_framing: bool = False):
+        """gpu_framing: the chunk (behind the tail carried over) goes to the GPU as it is and is framed there (FG_FRAME_CAPNP); the
+        Records, the carry-over and the CapnpStreamError are the host-framed route's."""
         self.decoder = decoder or CapnpDecoder(device=device)
-        self.framer = CapnpFramer()
+        self.framer = _GpuCapnpCarry() if gpu_framing else CapnpFramer()
+        self.gpu_framing = gpu_framing
 
     def feed(self, chunk: bytes) -> List[Union[Record, DecodeError]]:
-        data, offsets = self.framer.feed(chunk)
-        n = len(offsets) - 1
+        if self.gpu_framing:
+            buf = self.framer.begin(chunk)
+            tab, offsets, consumed = self.decoder.frame_decode_batch(buf, L.FG_FRAME_CAPNP, final=False)
+            n = len(offsets) - 1
+            self.framer.end(buf, n, consumed, self.decoder.last_capnp_stop())
+            data = np.frombuffer(buf[:consumed], np.uint8)
+        else:
+            data, offsets = self.framer.feed(chunk)
+            n = len(offsets) - 1
+            tab = self.decoder.decode_packed(data, offsets) if n else None
         if n == 0:
             return []
-        tab = self.decoder.decode_packed(data, offsets)
         blob, offs = tab.serialize(L.FG_CAPNP, data, offsets)
         raw = blob.tobytes()
         return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
@@ -487,17 +564,24 @@ class CapnpTranscodingSplitter:
     (FG_CAPNP, FG_FRAME_NONE); the tables never leave the device.  ``feed`` returns a :class:`~flowgger_amd.encoder.Transcoded`
     (``.out`` the bytes for the output, ``.dec_status`` / ``.enc_status`` what the reference prints per dropped message)."""
 
-    def __init__(self, encoder, decoder: Optional[CapnpDecoder] = None, device: int = 0, now_ts: float = 0.0):
+    def __init__(self, encoder, decoder: Optional[CapnpDecoder] = None, device: int = 0, now_ts: float = 0.0, gpu_framing: bool = False):
+        """gpu_framing: as for CapnpSplitter -- one fg_transcode_batch (FG_CAPNP, FG_FRAME_CAPNP) frames, decodes and encodes the chunk"""
         from .encoder import Pipeline
 
         self.decoder = decoder or CapnpDecoder(device=device)
         self.pipeline = Pipeline(self.decoder, encoder)
-        self.framer = CapnpFramer()
+        self.framer = _GpuCapnpCarry() if gpu_framing else CapnpFramer()
+        self.gpu_framing = gpu_framing
         self.now_ts = now_ts
 
     def feed(self, chunk: bytes):
         from .encoder import Transcoded
 
+        if self.gpu_framing:
+            buf = self.framer.begin(chunk)
+            res = self.pipeline.run_stream(buf, L.FG_FRAME_CAPNP, final=False, now_ts=self.now_ts)
+            self.framer.end(buf, len(res.out_offsets) - 1, res.consumed, self.decoder.last_capnp_stop())
+            return res
         data, offsets = self.framer.feed(chunk)
         if len(offsets) < 2:  # no whole message yet
             return Transcoded(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), None, 0)

@@ -182,8 +182,9 @@ class Pipeline:
 
     def run_stream(self, raw, framing: int, final: bool = True, now_ts: float = 0.0) -> Transcoded:
         """a raw stream chunk, framed on the GPU ("\\n" / NUL / FG_FRAME_SYSLEN: "<len> " prefixes -- `.frame_offsets` are then the frame
-        starts, prefixes included, and decoder.last_syslen_stop() says how the chain ended); bytes past `.consumed` belong to the
-        next chunk"""
+        starts, prefixes included, and decoder.last_syslen_stop() says how the chain ended; FG_FRAME_CAPNP with a CapnpDecoder: the segment
+        tables of a Cap'n Proto stream -- `.frame_offsets` are the message starts and decoder.last_capnp_stop() says how the chain
+        ended); bytes past `.consumed` belong to the next chunk"""
         import numpy as np
 
         data = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)

@@ -291,8 +291,8 @@ class CapnpDecoder : public Decoder {  // handle_message of splitter/capnp_split
 };
 
 // The framing half of CapnpSplitter::run (splitter/capnp_splitter.rs:24-46, capnp::serialize::read_message): a Cap'n Proto stream is
-// a chain of length prefixes -- message k + 1 starts where the segment table of message k says -- so the walk stays on the host, like
-// syslen, and reads one table per message.  frame(): the whole messages at the front of buf[0 .. n) -> their offsets (offsets.size()
+// a chain of length prefixes -- message k + 1 starts where the segment table of message k says.  This is the walk on the host, one
+// table per message: the model of fg_frame_capnp_device and the route CapnpTranscodingSplitter takes without gpu_framing.  frame(): the whole messages at the front of buf[0 .. n) -> their offsets (offsets.size()
 // - 1 messages, all multiples of 8 from a buffer that starts at a message) and the bytes they cover; the caller carries the rest
 // over.  The two conditions under which capnp 0.14's read_message (default ReaderOptions) ends the connection are reported as such.
 struct CapnpFramer {
@@ -1152,9 +1152,12 @@ class TranscodingSplitter {
 // `out` receives the re-encoded messages in stream order; `err` what the reference prints: the handle_message / encoder error of a
 // dropped message (:48-58) and "Capnp decoding error: ..." when read_message ends the connection (:28-31; the text behind the colon
 // is capnp 0.14's and unpinned) -- after the messages in front of it have been handled.
+// gpu_framing: the chunk (behind the tail carried over) goes to the GPU as it is and one fg_transcode_batch(FG_CAPNP, FG_FRAME_CAPNP)
+// frames, decodes and encodes it; fg_last_capnp_stop says how the chain of segment tables ended.  The output is the same.
 class CapnpTranscodingSplitter {
   public:
-    explicit CapnpTranscodingSplitter(EncoderConfig enc, size_t chunk_bytes = 8u << 20) : enc_(std::move(enc)), chunk_(chunk_bytes) {}
+    explicit CapnpTranscodingSplitter(EncoderConfig enc, size_t chunk_bytes = 8u << 20, bool gpu_framing = false)
+        : enc_(std::move(enc)), chunk_(chunk_bytes), gpu_framing_(gpu_framing) {}
     void run(std::istream& in, const Decoder& d, std::ostream& out, std::ostream& err) {
         std::vector<const char*> ks, vs;
         for (auto& kv : enc_.extra) { ks.push_back(kv.first.c_str()); vs.push_back(kv.second.c_str()); }
@@ -1168,6 +1171,38 @@ class CapnpTranscodingSplitter {
         ec.now_ts = enc_.now_ts;
         CapnpFramer fr;
         std::vector<uint8_t> chunk(chunk_), batch;
+        auto report = [&](const fg_transcoded& r) {
+            if (r.out_bytes) {
+                out.write((const char*)r.out, (std::streamsize)r.out_bytes);
+                out.flush();
+            }
+            for (uint64_t i = 0; i < r.n; ++i) {
+                const uint8_t ds = FG_META_STATUS(r.meta[i]), es = r.enc_status[i];
+                if (ds == 0 && es == 0) continue;
+                const char* msg = ds ? fg_error_string(FG_CAPNP, ds) : fg_encode_error_string(es);
+                err << (msg ? msg : "?") << "\n";  // :50, :57
+            }
+        };
+        for (; gpu_framing_;) {  // `batch` = the tail carried over + the chunk
+            in.read((char*)chunk.data(), (std::streamsize)chunk.size());
+            const uint64_t got = (uint64_t)in.gcount();
+            batch.insert(batch.end(), chunk.data(), chunk.data() + got);
+            const uint64_t nb = batch.size();
+            batch.resize(nb + 16);  // readable slack
+            fg_transcoded r{};
+            const int rc = fg_transcode_batch(d.ctx(), FG_CAPNP, FG_FRAME_CAPNP, &ec, batch.data(), nb, nullptr, 0, 0, &r);
+            if (rc != FG_OK) throw std::runtime_error("fg_transcode_batch failed: " + std::to_string(rc));
+            report(r);
+            const int st = fg_last_capnp_stop(d.ctx());
+            batch.resize(nb);
+            batch.erase(batch.begin(), batch.begin() + (std::ptrdiff_t)r.consumed);
+            if (st == FG_CAPNP_TOO_MANY_SEGMENTS) { err << "Capnp decoding error: Too many segments\n"; return; }
+            if (st == FG_CAPNP_TOO_LARGE) { err << "Capnp decoding error: Message is too large\n"; return; }
+            if (got == 0 || !in) {
+                err << "Capnp decoding error: Premature end of file\n";
+                return;
+            }
+        }
         for (;;) {
             in.read((char*)chunk.data(), (std::streamsize)chunk.size());
             const uint64_t got = (uint64_t)in.gcount();
@@ -1178,16 +1213,7 @@ class CapnpTranscodingSplitter {
                 fg_transcoded r{};
                 const int rc = fg_transcode_batch(d.ctx(), FG_CAPNP, FG_FRAME_NONE, &ec, batch.data(), fr.nbytes(), fr.offsets().data(), fr.messages(), 1, &r);
                 if (rc != FG_OK) throw std::runtime_error("fg_transcode_batch failed: " + std::to_string(rc));
-                if (r.out_bytes) {
-                    out.write((const char*)r.out, (std::streamsize)r.out_bytes);
-                    out.flush();
-                }
-                for (uint64_t i = 0; i < r.n; ++i) {
-                    const uint8_t ds = FG_META_STATUS(r.meta[i]), es = r.enc_status[i];
-                    if (ds == 0 && es == 0) continue;
-                    const char* msg = ds ? fg_error_string(FG_CAPNP, ds) : fg_encode_error_string(es);
-                    err << (msg ? msg : "?") << "\n";  // :50, :57
-                }
+                report(r);
             }
             fr.consume();
             if (st == CapnpFramer::TooManySegments) { err << "Capnp decoding error: Too many segments\n"; return; }
@@ -1201,6 +1227,7 @@ class CapnpTranscodingSplitter {
   private:
     EncoderConfig enc_;
     size_t chunk_;
+    bool gpu_framing_ = false;
 };
 
 }  // namespace fg

@@ -36,8 +36,9 @@ extern "C" {
 /* FG_CAPNP (input.format = "capnp", splitter/capnp_splitter.rs:65-167): a "line" of the batch is ONE WHOLE Cap'n Proto message
  * INCLUDING its segment table; offsets[i] must be multiples of 8 (a message is an array of 8-byte words; the host-buffer entry
  * points answer FG_ERR_ARG otherwise, fg_decode_batch_device -- whose offsets live on the device -- gives such a row status 3);
- * spans are relative to offsets[i] as for every other format.  Only FG_FRAME_NONE is valid with it: a capnp stream is a chain
- * of length prefixes and is framed on the host (flowgger_amd/host/fg_decoder.hpp CapnpFramer).  FG_CAPNP is an additive value
+ * spans are relative to offsets[i] as for every other format.  FG_FRAME_NONE and FG_FRAME_CAPNP are valid with it: a capnp stream is a chain
+ * of length prefixes, framed where it lies by fg_frame_capnp_device (or by the host-buffer entry points with FG_FRAME_CAPNP) or on
+ * the host (flowgger_amd/host/fg_decoder.hpp CapnpFramer).  FG_CAPNP is an additive value
  * under the same FG_ABI_VERSION: a library without it rejects it with FG_ERR_ARG / FG_ERR_UNSUPPORTED.  All six encoders and the
  * mergers take FG_CAPNP tables (fg_encode_device, fg_encode_device_async, fg_transcode_batch with FG_FRAME_NONE): the relay's
  * handle_message + encoder.encode (capnp_splitter.rs:47-60) is one fg_transcode_batch.  The passthrough encoder emits the
@@ -100,11 +101,25 @@ typedef enum fg_framing {
     FG_FRAME_NONE = 0, /* offsets delimit bare lines (framing bytes already stripped by the caller) */
     FG_FRAME_LINE = 1, /* BufRead::lines(): "\n" terminated, the "\n" and one preceding "\r" are not part of the line */
     FG_FRAME_NUL = 2,  /* BufRead::split(0): "\0" terminated */
-    FG_FRAME_SYSLEN = 3 /* RFC 6587 octet counting (splitter/syslen_splitter.rs:17-57): "<len> " followed by exactly len bytes, untrimmed
+    FG_FRAME_SYSLEN = 3, /* RFC 6587 octet counting (splitter/syslen_splitter.rs:17-57): "<len> " followed by exactly len bytes, untrimmed
                            (a trailing "\n" belongs to the message); framed by fg_frame_syslen_device and by the host-buffer entry points
                            fg_frame_decode_batch / fg_transcode_batch.  An additive value under the same FG_ABI_VERSION: a library without
                            it rejects it with FG_ERR_ARG / FG_ERR_UNSUPPORTED */
+    FG_FRAME_CAPNP = 4  /* a Cap'n Proto stream (splitter/capnp_splitter.rs:24-46, capnp::serialize::read_message): a segment table, then
+                           the words it counts; frame i is one whole message, its table included.  Valid with FG_CAPNP only (FG_ERR_ARG
+                           otherwise), framed by fg_frame_capnp_device and by fg_frame_decode_batch / fg_transcode_batch.  An additive
+                           value under the same FG_ABI_VERSION */
 } fg_framing;
+
+/* How the chain of segment tables of an FG_FRAME_CAPNP chunk ended (fg_frame_capnp_device, fg_last_capnp_stop).  The whole messages
+ * in front of `consumed` are valid output in every case: the reference handles them first and ends the connection afterwards. */
+typedef enum fg_capnp_stop {
+    FG_CAPNP_CLEAN = 0,             /* consumed == nbytes: the chunk ended on a message boundary */
+    FG_CAPNP_TAIL = 1,              /* the table or the body of the message at `consumed` runs past nbytes (fewer than 8 bytes left
+                                       included): carry bytes[consumed ..) over */
+    FG_CAPNP_TOO_MANY_SEGMENTS = 2, /* the table at `consumed` counts 512 segments or more: "Too many segments", the connection is over */
+    FG_CAPNP_TOO_LARGE = 3          /* its sizes add up to more than 8 Mi words: "Message has N words, which is too large" */
+} fg_capnp_stop;
 
 /* How the "<len> " chain of an FG_FRAME_SYSLEN chunk ended (fg_frame_syslen_device, fg_last_syslen_stop): what the caller does next
  * to reproduce SyslenSplitter::run (syslen_splitter.rs:42-57). */
@@ -371,6 +386,28 @@ int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, cons
 int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint8_t* d_packed, uint64_t* d_offsets,
                            uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames, uint64_t* consumed,
                            int* stop_reason, void* stream);
+/* GPU FRAMING of a CAP'N PROTO stream (input.format = "capnp"; replaces the walk of capnp::serialize::read_message over the segment
+ * tables in CapnpSplitter::run, splitter/capnp_splitter.rs:24-46, for a chunk of the stream that lies in device-addressable memory
+ * and starts at a message).  At a message start p: fewer than 8 bytes left is a TAIL; segs = u32le(p) + 1, 512 or more stops with
+ * TOO_MANY_SEGMENTS; a table of roundup8(4 + 4 * segs) bytes that runs past the chunk is a TAIL; the 64-bit sum of the segs sizes
+ * beyond 8 Mi words stops with TOO_LARGE; a body of 8 * sum bytes that runs past the chunk is a TAIL; else the next message starts
+ * right behind the body (a message may be 8 bytes long).
+ *   d_bytes      raw stream chunk (device-addressable), 16-byte aligned, readable up to nbytes rounded up to 16
+ *   final        accepted for symmetry with the other framers: the messages found are the same either way (a message needs its
+ *                whole body); what a TAIL means at the end of the stream is the caller's business
+ *   d_offsets    out, cap_frames + 1 entries INTO d_bytes: message i = [off[i], off[i + 1]), its segment table included -- with
+ *                d_bytes exactly what fg_decode_frames_device(FG_CAPNP, FG_FRAME_NONE, ...) takes.  Nothing is packed and no
+ *                UTF-8 pass runs: Text is checked by the decoder
+ *   n_frames, consumed, stop_reason   out (host): messages, the bytes they cover (= off[n]; for every stop but CLEAN the position
+ *                of the table at which the walk stopped), an fg_capnp_stop; the call synchronises the stream
+ * Returns FG_ERR_ENT_OVERFLOW when cap_frames is too small (*n_frames holds the need; nbytes / 8 always suffices),
+ * FG_ERR_UNSUPPORTED when the launch DECLINES the chunk -- more words that other words' speculative messages end on than the
+ * node store holds (one per 6 words): nothing is valid, walk the chunk on the host (the host-buffer entry points do) --, and
+ * FG_ERR_ARG for a chunk of more than FG_CAPNP_FRAME_MAX_BYTES bytes (the scratch keeps word indices in 29 bits).
+ * The chain is resolved exactly: a result that is returned is the sequential walk's, bit for bit. */
+#define FG_CAPNP_FRAME_MAX_BYTES 0xFFFF0000ull
+int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint64_t* d_offsets, uint64_t cap_frames,
+                          uint64_t* n_frames, uint64_t* consumed, int* stop_reason, void* stream);
 int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                            uint64_t* d_offsets, uint64_t cap_frames, const fg_tables* tables, uint64_t avg_line_hint,
                            uint64_t* d_result, void* stream);
@@ -451,6 +488,10 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
  * FG_SYSLEN_PREFIX_LEN(bytes + off[i], off[i + 1] - off[i]); fg_last_syslen_stop says how the chain ended.  Every payload that is not
  * valid UTF-8 is flagged FG_ST_BAD_UTF8; the reference panics at the first one, and stopping there is the caller's job.  A chunk the
  * device framer declines is framed by a host hop over `bytes` instead, with the same results (fg_last_host_path tells).
+ * FG_FRAME_CAPNP (FG_CAPNP only; the read_message loop of CapnpSplitter::run, capnp_splitter.rs:24-46, for a chunk): the chunk is
+ * uploaded once, framed in HBM and decoded from the same buffer; out_offsets are the message starts in `bytes`, which the spans in
+ * `out` are relative to; fg_last_capnp_stop says how the chain ended at `consumed`.  A chunk the device framer declines is walked
+ * on the host over `bytes`, with the same results (fg_last_host_path tells).
  * Everything returned stays valid until the next call on this ctx. */
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes,
                           uint64_t nbytes, int final, fg_tables* out, const uint64_t** out_offsets,
@@ -475,9 +516,14 @@ enum {
     FG_PATH_FRAME_SLICED = 4,      /* fg_frame_decode_batch: upload slices + framing scan + decode per slice (rounds 3-5) */
     FG_PATH_FRAME_ONE_PIECE = 5,   /* fg_frame_decode_batch: upload, frame, count on the host, decode */
     FG_PATH_FRAME_SYSLEN_DEVICE = 6, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_SYSLEN: framed + packed by the device */
-    FG_PATH_FRAME_SYSLEN_HOST = 7  /* ... the device framer declined the chunk: the prefixes were hopped on the host */
+    FG_PATH_FRAME_SYSLEN_HOST = 7, /* ... the device framer declined the chunk: the prefixes were hopped on the host */
+    FG_PATH_FRAME_CAPNP_DEVICE = 8, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_CAPNP: framed by the device where the chunk lies */
+    FG_PATH_FRAME_CAPNP_HOST = 9   /* ... the device framer declined the chunk: the segment tables were walked on the host */
 };
 int fg_last_host_path(const fg_ctx* ctx);
+/* How the chain of segment tables of the last FG_FRAME_CAPNP call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an
+ * fg_capnp_stop; FG_CAPNP_CLEAN before the first such call). */
+int fg_last_capnp_stop(const fg_ctx* ctx);
 /* How the prefix chain of the last FG_FRAME_SYSLEN call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an
  * fg_syslen_stop; FG_SYSLEN_CLEAN before the first such call). */
 int fg_last_syslen_stop(const fg_ctx* ctx);
@@ -568,6 +614,8 @@ const char* fg_encode_error_string(uint8_t enc_status);
  *     the rest over to the next call (as for fg_frame_decode_batch).
  *   framing == FG_FRAME_SYSLEN: the same for an octet-counted chunk; frame_offsets are the frame starts, prefix included
  *     (FG_SYSLEN_PREFIX_LEN), and fg_last_syslen_stop says how the chain ended.
+ *   framing == FG_FRAME_CAPNP (FG_CAPNP only): the same for a Cap'n Proto stream chunk; frame_offsets are the message starts and
+ *     fg_last_capnp_stop says how the chain ended.
  * Results (pinned host memory owned by ctx, valid until the next host-buffer call on it):
  *   out / out_bytes / out_offsets[n + 1]   message i = out[out_offsets[i] .. out_offsets[i + 1]) -- empty when the
  *                                          line was dropped
