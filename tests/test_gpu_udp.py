@@ -108,6 +108,155 @@ def test_mutation_pool_in_one_launch(dec):
     um.check_batch(pool, um.DEFAULT_MAX, offs, packed, drop, st, "mutation pool")
 
 
+def rotations(cases, filler=b"pad"):
+    """the list, filled up to whole waves, 64 times over and shifted by one lane each time: every case sits in every lane once, next
+    to 63 other cases"""
+    padded = list(cases) + [filler] * (-len(cases) % 64)
+    return [padded[(k - j) % len(padded)] for j in range(64) for k in range(len(padded))]
+
+
+@pytest.mark.parametrize("cap", um.HAND_CAPS)
+def test_hand_streams_share_waves(dec, cap):
+    """the hand-built streams (tests/deflate_build.py) with 64 different code sets and verdicts per wave, every case in every lane
+    (lanes 0 and 63 among them); then a wave whose 64 lanes hold the same dynamic block; then a last wave of one lane"""
+    table = um.hand_streams(cap)
+    cases = [d for _, d, _ in table]
+    same = dict((n, d) for n, d, _ in table)["all_286_and_30_symbols_hlit29_hdist29_z"]
+    batch = rotations(cases) + [same] * 64 + [cases[0]]
+    assert len(batch) % 64 == 1
+    offs, packed, drop, st = unpack(dec, batch, cap)
+    um.check_batch(batch, cap, offs, packed, drop, st, f"hand-built streams, cap {cap}")
+    want = {d: w for n, d, w in table if n.startswith("cap_") or cap == um.DEFAULT_MAX}
+    for d, got in zip(batch[:len(cases)], st):  # (the first rotation is the list itself; the table's verdicts, not only the model's)
+        assert d not in want or got == want[d]
+    # every case once in a last, partial wave: 63 of them behind whole waves of the others
+    for s in range(0, len(cases), 63):
+        last = cases[s:s + 63]
+        front = cases[s + 63:] + cases[:s]
+        batch = front + [b"pad"] * (-len(front) % 64) + last
+        assert 0 < len(batch) % 64 == len(last)
+        offs, packed, drop, st = unpack(dec, batch, cap)
+        um.check_batch(batch, cap, offs, packed, drop, st, f"hand-built streams, cap {cap}, last wave from {s}")
+    if cap == um.DEFAULT_MAX:  # whole waves only, and whole waves plus one
+        for n in (len(cases) // 64 * 64, len(cases) // 64 * 64 + 1):
+            offs, packed, drop, st = unpack(dec, cases[:n], cap)
+            um.check_batch(cases[:n], cap, offs, packed, drop, st, f"hand-built streams, n = {n}")
+
+
+def test_random_code_sets(dec):
+    good, flipped = um.random_code_set_pool()
+    pool = [d for pair in zip(good, flipped) for d in pair]  # (valid and broken streams side by side in every wave)
+    offs, packed, drop, st = unpack(dec, pool, None)
+    um.check_batch(pool, um.DEFAULT_MAX, offs, packed, drop, st, "random code sets")
+    assert int((st[0::2] <= um.GZIP).sum()) == len(good)
+
+
+UTF8_VALID = [b"\xc3\xa9", b"\xe2\x9c\x93", b"\xf0\x9f\x98\x80", b"\xe0\xa0\x80", b"\xed\x9f\xbf", b"\xf0\x90\x80\x80", b"\xf4\x8f\xbf\xbf"]
+UTF8_INVALID = [b"\xc0\x80", b"\xc1\xbf", b"\xe0\x9f\x80", b"\xed\xa0\x80", b"\xf0\x8f\x80\x80", b"\xf4\x90\x80\x80", b"\xf5\x80\x80\x80", b"\x80",
+                b"\xc3A", b"\xe2\x9cA", b"\xf0\x9f\x98A"]
+UTF8_LENGTHS = (1, 15, 16, 17, 31, 32, 33, 1023, 1024, 1025, 1040, 2048, 2049)
+
+
+def utf8_payloads(length, probes):
+    """ASCII filler with one probe whose first byte lands at each of the offsets; a probe that does not fit is cut off by the payload's
+    end (after 1, 2 or 3 bytes: the offsets len - 3 .. len - 1)"""
+    fill = (b"0123456789abcdefghijklmnopqrstuvwxyz" * (length // 36 + 1))[:length]
+    offsets = sorted({o for o in (0, 1, 13, 14, 15, 16, 17, 1021, 1022, 1023, 1024, 1025, length - 3, length - 2, length - 1) if 0 <= o < length})
+    out = []
+    for o in offsets:
+        for p in probes:
+            out.append((fill[:o] + p + fill[o + len(p):])[:length])
+            assert len(out[-1]) == length
+    return out
+
+
+def unpack_exact(dec, datagrams, max_inflated):
+    """as unpack(), through the sizing call and then into a buffer of exactly the size it named, filled with 0xEE: nothing behind the
+    last slot is written (and check_batch holds every slot against its neighbours)"""
+    import torch
+
+    dev = torch.device("cuda", dec.device)
+    blob, offs = um.pack(datagrams)
+    n = len(datagrams)
+    d_bytes, d_offs = to_dev(blob, dev), torch.from_numpy(offs.astype(np.int64)).to(dev)
+    d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    d_drop, d_st = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+    total = C.c_uint64()
+    head = (dec._ctx, d_bytes.data_ptr(), d_bytes.numel(), d_offs.data_ptr(), n, max_inflated)
+    tail = (d_off.data_ptr(), d_drop.data_ptr(), d_st.data_ptr(), C.byref(total), None)
+    lib = L.lib()
+    assert lib.fg_udp_unpack_device(*head, None, 0, *tail) == L.FG_OK
+    need = int(total.value)
+    d_out = torch.full(((need + 15) // 16 * 16 + 16,), 0xEE, dtype=torch.uint8, device=dev)
+    assert d_out.data_ptr() % 16 == 0
+    assert lib.fg_udp_unpack_device(*head, d_out.data_ptr(), need, *tail) == L.FG_OK
+    torch.cuda.synchronize(dev)
+    out = d_out.cpu().numpy()
+    assert bool((out[need:] == 0xEE).all()), "bytes written behind the last payload"
+    return d_off.cpu().numpy().astype(np.uint64), out, d_drop.cpu().numpy(), d_st.cpu().numpy()
+
+
+def test_utf8_edges_of_inflated_and_bare_payloads(dec):
+    """utf8_bad() on inflated payloads and copy_check() on bare ones, which the CPU build replaces by a bytewise loop: a probe at the
+    16-byte chunk edges, at the 1024-byte wave stride and at the payload's end, the payload's length around the same edges, and for
+    the bare ones the slot starting at every residue mod 16 (copy_check's unaligned head).  The answer is bytes.decode's."""
+    probes = UTF8_VALID + UTF8_INVALID
+    batch, slot_at, seen = [], 0, set()
+
+    def put(d, size):  # (every datagram here keeps a slot of its payload's size, dropped for its UTF-8 or not)
+        nonlocal slot_at
+        batch.append(d)
+        slot_at += size
+
+    # three ways: bare, zlib, gzip
+    for length in UTF8_LENGTHS:
+        for k, p in enumerate(utf8_payloads(length, probes)):
+            put(p, length)
+            put(zlib.compress(p, (0, 1, 6)[k % 3]), length)
+            put(um.gz_member(p, level=(6, 0, 9)[k % 3], name=b"edge" if length < 16 else None), length)  # (24 bytes for the gate)
+            assert um.gate(batch[-1]) == um.GZIP and um.gate(batch[-2]) == um.ZLIB and um.gate(batch[-3]) == um.RAW
+    # the bare ones again with the slot at every residue: the short lengths whole, the long ones (whose head is filler unless the probe
+    # is among the first 17 bytes) with three probes
+    few = [UTF8_VALID[2], UTF8_INVALID[3], UTF8_INVALID[7]]
+    for h in range(16):
+        for length in UTF8_LENGTHS:
+            for p in utf8_payloads(length, probes if length <= 33 else few):
+                if slot_at % 16 != h:
+                    put(b"-" * ((h - slot_at) % 16), (h - slot_at) % 16)
+                seen.add((h, length))
+                put(p, length)
+    assert len(seen) == 16 * len(UTF8_LENGTHS)
+    st_model, kept, slots = um.expect(batch, CAP)
+    assert int(kept.sum()) > 1000 and int((st_model == um.BAD_UTF8).sum()) > 1000 and not bool((st_model == um.TOO_LARGE).any())
+    assert sum(len(s) for s in slots) == slot_at
+    offs, packed, drop, st = unpack_exact(dec, batch, CAP)
+    um.check_batch(batch, CAP, offs, packed, drop, st, "UTF-8 edges")
+
+
+def test_hand_built_gelf_streams_end_to_end(oracle):
+    """64 GELF lines in hand-built streams over random code sets, one wave of them, through fg_udp_decode_batch: rows against the oracle"""
+    d = GelfDecoder()
+    rng = np.random.default_rng(1953)
+    import deflate_build as db
+
+    lines = corpus(GELF, 64)
+    grams = [(db.wrap_zlib if k % 2 else db.wrap_gzip)(db.random_dynamic_stream(rng, l), l) for k, l in enumerate(lines)]
+    try:
+        blob, offs = um.pack(grams)
+        tab, out_lines, line_offs, ust = d.udp_decode_packed(blob, offs)
+        st, kept, slots = um.expect(grams)
+        assert bool(kept.all()) and np.array_equal(ust, st) and slots == lines
+        gblob, goffs = tab.serialize(d.fmt, out_lines, line_offs, cfg=d._cfg)
+        mblob, moffs = um.pack(lines)
+        oblob, ooffs = oracle.decode_batch(GELF, np.concatenate([mblob, np.zeros(16, np.uint8)]), moffs, config=None)
+        for i in range(64):
+            assert bytes(out_lines[int(line_offs[i]):int(line_offs[i + 1])]) == lines[i], f"inflated line {i}"
+            a, b = gblob[int(goffs[i]):int(goffs[i + 1])].tobytes(), oblob[int(ooffs[i]):int(ooffs[i + 1])].tobytes()
+            assert a == b, f"row {i}: {lines[i]!r}\n  gpu    {a!r}\n  oracle {b!r}"
+    finally:
+        d.close()
+
+
 def make_decoder(fmt, oracle):
     if fmt == RFC5424:
         return RFC5424Decoder(), None

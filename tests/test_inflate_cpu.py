@@ -78,6 +78,67 @@ def test_mutation_fuzz_small_cap(host):
     assert np.bincount(st, minlength=7)[um.TOO_LARGE] > 100
 
 
+def test_hand_table_is_what_zlib_says():
+    """every hand-built stream reaches the inflater and gets the verdict its table expects from Python's zlib: a case that stopped
+    reaching it (the gate, the padding, a slip in the bit writer) fails here instead of passing vacuously everywhere else"""
+    for cap in um.HAND_CAPS:
+        table = um.hand_streams(cap)
+        assert len({n for n, _, _ in table}) == len(table) >= 140
+        for name, d, want in table:
+            assert um.gate(d) == {"z": um.ZLIB, "g": um.GZIP}[name.replace("_check_off_by_one", "")[-1]], name
+            if name.startswith("cap_") or cap == um.DEFAULT_MAX:
+                assert um.model(d, cap)[0] == want, f"{name} at cap {cap}: zlib says {um.model(d, cap)[0]}, the table {want}"
+    # what the orderings at the cap rest on: a complete stream of cap + 1 bytes keeps its bytes, the others none
+    for name, d, _ in um.hand_streams(257):
+        if name.startswith("cap_"):
+            assert len(um.model(d, 257)[1]) == (258 if "_then_eob_" in name and "off_by_one" not in name else 0), name
+
+
+@pytest.mark.parametrize("cap", um.HAND_CAPS)
+def test_hand_streams(host, cap):
+    table = um.hand_streams(cap)
+    st = _run(host, [d for _, d, _ in table], cap, f"hand-built streams, cap {cap}")
+    for (name, _, want), got in zip(table, st):
+        if name.startswith("cap_") or cap == um.DEFAULT_MAX:
+            assert got == want, name
+
+
+def test_random_code_sets(host):
+    good, flipped = um.random_code_set_pool()
+    assert len(good) == len(flipped) == 2000
+    st_good, _, _ = um.expect(good)
+    st_flip, _, _ = um.expect(flipped)
+    # conditions on the generator, from the model's answers: every stream is valid, and a flipped header bit mostly is not
+    assert bool(((st_good == um.ZLIB) | (st_good == um.GZIP)).all()), np.bincount(st_good, minlength=7)
+    assert int(((st_flip == um.BAD_ZLIB) | (st_flip == um.BAD_GZIP)).sum()) >= len(flipped) // 2, np.bincount(st_flip, minlength=7)
+    _run(host, good + flipped, what="random code sets")
+    _run(host, good[:400] + flipped[:400], 200, "random code sets, cap 200")
+
+
+def test_sanitized_standalone_run(tmp_path):
+    """fg_inflate.hpp in a stand-alone program under AddressSanitizer and UBSan, over the hand-built streams at every cap and the
+    random code sets: malformed headers are where a table index would run off.  The program checks nothing but its own sanity;
+    what the answers must be is the other tests' business."""
+    import struct
+    import subprocess
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    exe = tmp_path / "inflate_sanitized"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    f"-I{root / 'flowgger_amd' / 'csrc'}", str(root / "tests/native/inflate_host.cpp"), str(root / "tests/native/inflate_sanitized_main.cpp"),
+                    "-o", str(exe)], check=True)
+    good, flipped = um.random_code_set_pool()
+    for k, cap in enumerate(um.HAND_CAPS):
+        grams = [d for _, d, _ in um.hand_streams(cap)] + (good + flipped if k == 0 else flipped[:300])
+        f = tmp_path / f"grams_{cap}.bin"
+        f.write_bytes(b"".join(struct.pack("<I", len(g)) + g for g in grams))
+        r = subprocess.run([str(exe), str(f), str(cap)], capture_output=True, text=True)
+        assert r.returncode == 0 and r.stderr == "" and r.stdout.split()[:2] == ["OK", str(len(grams))], r.stdout + r.stderr
+        # (the same library code as InflateHost: the two builds give the same total)
+        assert int(r.stdout.split()[2]) == sum(len(s) for s in um.expect(grams, cap)[2])
+
+
 def test_udp_batcher_keeps_its_state_when_a_flush_fails(tmp_path):
     """fg::UdpBatcher against a library whose fg_udp_decode_batch fails (the fake launchers have no inflate kernels:
     FG_ERR_UNSUPPORTED): the datagrams stay parked as they were, without the 16 bytes of slack, and later ones line up behind them"""

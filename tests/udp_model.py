@@ -4,6 +4,7 @@ tests/native/libinflate_host.so (flowgger_amd/csrc/fg_inflate.hpp compiled for t
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import gzip
 import json
 import struct
@@ -82,8 +83,8 @@ def model(d: bytes, max_inflated: int = DEFAULT_MAX):
     return (kind, out, True) if _valid_utf8(out) else (BAD_UTF8, out, False)
 
 
-def gz_member(payload: bytes, extra=None, name=None, comment=None, hcrc=False, level=6, bad_hcrc=False, crc_delta=0, isize_delta=0) -> bytes:
-    """an RFC 1952 member built by hand around a raw deflate stream"""
+def gz_header(extra=None, name=None, comment=None, hcrc=False, bad_hcrc=False) -> bytes:
+    """the header of an RFC 1952 member"""
     flg = (4 if extra is not None else 0) | (8 if name is not None else 0) | (16 if comment is not None else 0) | (2 if hcrc else 0)
     h = bytes([0x1F, 0x8B, 8, flg, 0, 0, 0, 0, 0, 255])
     if extra is not None:
@@ -94,6 +95,12 @@ def gz_member(payload: bytes, extra=None, name=None, comment=None, hcrc=False, l
         h += comment + b"\0"
     if hcrc:
         h += struct.pack("<H", ((zlib.crc32(h) & 0xFFFF) + (1 if bad_hcrc else 0)) & 0xFFFF)
+    return h
+
+
+def gz_member(payload: bytes, extra=None, name=None, comment=None, hcrc=False, level=6, bad_hcrc=False, crc_delta=0, isize_delta=0) -> bytes:
+    """an RFC 1952 member built by hand around a raw deflate stream"""
+    h = gz_header(extra, name, comment, hcrc, bad_hcrc)
     c = zlib.compressobj(level, zlib.DEFLATED, -15)
     body = c.compress(payload) + c.flush()
     return h + body + struct.pack("<II", (zlib.crc32(payload) + crc_delta) & 0xFFFFFFFF, (len(payload) + isize_delta) & 0xFFFFFFFF)
@@ -163,6 +170,213 @@ def case_list(max_inflated: int = DEFAULT_MAX):
     add("zlib_trailing", zlib.compress(JSON_LINE) + b"trailing bytes")
     add("gzip_trailing", gz_member(JSON_LINE) + gz_member(b"a second member"))
     return out
+
+
+HAND_CAPS = (DEFAULT_MAX, 259, 258, 257, 3, 1)
+
+
+def _hand_bodies(cap: int):
+    """[(name, raw deflate body, the payload it stands for, verdict)]: 'ok' the stream is kept, 'bad' zlib refuses it, 'big' it wants
+    more than `cap` bytes.  The names that begin with 'cap_' are built for `cap` and judged there, the others are judged at DEFAULT_MAX."""
+    import deflate_build as db
+
+    out = []
+    fx = db.fixed_codes()
+
+    def add(name, verdict, build, payload=b""):
+        w = db.BitWriter()
+        build(w)
+        out.append((name, w.bytes(), payload, verdict))
+
+    def tail(w, nbytes=8):  # bits behind a malformation: it is refused for what it is, not for the input's end
+        w.put(0, 8 * nbytes)
+
+    def fixed(last=1):
+        def start(w):
+            db.block_header(w, last, 1)
+        return start
+
+    lit2 = lambda a: [a.get(s, 0) for s in range(max(257, max(a) + 1))]  # lit/len lengths from {symbol: length}
+
+    # -- the code-length code
+    def clen_zero(nbytes):
+        def f(w):
+            db.dynamic_header(w, 1, [0] * 257, [0], clen_lengths=[0] * 19, clen_symbols=[])
+            tail(w, nbytes)  # (258 one-bit dummies are wanted: 33 bytes)
+        return f
+    add("clen_all_zero", "bad", clen_zero(40))
+    add("clen_all_zero_cut_in_dummies", "bad", clen_zero(5))
+    cl = lambda a: [a.get(s, 0) for s in range(19)]
+    add("clen_oversubscribed", "bad", lambda w: (db.dynamic_header(w, 1, [0] * 257, [0], clen_lengths=cl({16: 1, 17: 1, 18: 1, 0: 1}), clen_symbols=[]), tail(w)))
+    add("clen_incomplete", "bad", lambda w: (db.dynamic_header(w, 1, [0] * 257, [0], clen_lengths=cl({0: 2, 8: 2}), clen_symbols=[]), tail(w)))
+    add("clen_one_code", "bad", lambda w: (db.dynamic_header(w, 1, [0] * 257, [0], clen_lengths=cl({0: 1}), clen_symbols=[]), tail(w)))
+
+    # -- the literal/length code
+    add("lit_only_eob", "ok", lambda w: db.dynamic_header(w, 1, lit2({256: 1}), [0]).eob(w))
+    add("lit_only_eob_then_code_1", "bad", lambda w: (db.dynamic_header(w, 0, lit2({256: 1}), [0]), w.put(1, 1), tail(w)))
+    add("lit_oversubscribed", "bad", lambda w: (db.dynamic_header(w, 1, lit2({0x61: 1, 0x62: 1, 256: 1}), [0]), tail(w)))
+    add("lit_incomplete_two_2bit", "bad", lambda w: (db.dynamic_header(w, 1, lit2({0x61: 2, 256: 2}), [0]), tail(w)))
+    add("lit_no_eob", "bad", lambda w: (db.dynamic_header(w, 1, lit2({0x61: 1, 0x62: 1}), [0]), tail(w)))
+    text45 = bytes(0x78 + (k * 7 % 3 == 0) for k in range(45))  # 'x' and 'y'
+
+    def lit_15bit(w):
+        a = {k: k + 1 for k in range(13)}  # lengths 1 .. 13 for symbols nobody writes, 14 for the end, 15 + 15 for the text
+        a.update({256: 14, 0x78: 15, 0x79: 15})
+        assert db.kraft_left(lit2(a)) == 0
+        c = db.dynamic_header(w, 1, lit2(a), [0])
+        c.lits(w, text45)
+        c.eob(w)
+    add("lit_15bit_codes", "ok", lit_15bit, text45)
+    head32 = bytes(range(0x40, 0x60))
+
+    def all_symbols(w):  # hlit = hdist = 29: the largest that are valid
+        lit, dst = [8] * 226 + [9] * 60, [4] * 2 + [5] * 28
+        assert db.kraft_left(lit) == 0 and db.kraft_left(dst) == 0
+        c = db.dynamic_header(w, 1, lit, dst)
+        c.lits(w, head32)
+        c.match(w, 258, 32)
+        c.eob(w)
+    add("all_286_and_30_symbols_hlit29_hdist29", "ok", all_symbols, (head32 * 10)[:32 + 258])
+
+    # -- the distance code
+    abc = {0x61: 2, 0x62: 2, 256: 2, 257: 2}
+
+    def with_dist(dst, bits, last_sym=257):
+        def f(w):
+            c = db.dynamic_header(w, 1, lit2(abc), dst)
+            c.lits(w, b"ab")
+            c.sym(w, last_sym)  # length 3
+            for b in bits:
+                w.put(b, 1)
+            c.eob(w)
+        return f
+    add("dist_none_length_used", "bad", with_dist([0], []))
+    add("dist_none_unused", "ok", with_dist([0], [], last_sym=0x62), b"abb")
+    add("dist_one_code_bit_0", "ok", with_dist([1], [0]), b"abbbb")
+    add("dist_one_code_bit_1", "bad", with_dist([1], [1]))
+    add("dist_one_code_not_the_first", "ok", with_dist([0, 1], [0]), b"ababa")
+    add("dist_two_1bit_codes", "ok", with_dist([1, 1], [1]), b"ababa")
+    add("dist_incomplete_2bit", "bad", with_dist([2, 2], [0, 0]))
+    add("dist_oversubscribed", "bad", with_dist([1, 1, 1], [0]))
+
+    # -- repeat codes
+    add("repeat_16_first", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], clen_symbols=[(16, 0)]), tail(w)))
+    add("repeat_18_past_the_lengths", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], clen_symbols=[(18, 127), (18, 127)]), tail(w)))
+    add("repeat_16_past_the_lengths", "bad",
+        lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], clen_symbols=[(18, 127), (18, 107), (2,), (16, 0)]), tail(w)))  # 256 + 3 > 258
+
+    def rep_into_dist(w):  # 97 zeros, a = 1, b = 3, 157 zeros, end = 3, length 3 = 2, then 16 carries the 2 over all four distance lengths
+        a = {0x61: 1, 0x62: 3, 256: 3, 257: 2}
+        c = db.dynamic_header(w, 1, lit2(a), [2, 2, 2, 2], clen_symbols=[(18, 86), (1,), (3,), (18, 127), (18, 8), (3,), (2,), (16, 1)])
+        c.lits(w, b"ab")
+        c.match(w, 3, 2)
+        c.eob(w)
+    add("repeat_16_from_literal_into_distance_lengths", "ok", rep_into_dist, b"ababa")
+
+    def rep_after_zero_runs(w):  # 16 directly after 17 and after 18 repeats their zero
+        a = {0x61: 1, 0x62: 2, 256: 2}
+        spelt = [(17, 7), (16, 3), (18, 70), (1,), (2,), (18, 127), (16, 3), (17, 7), (16, 0), (2,), (0,)]
+        c = db.dynamic_header(w, 1, lit2(a), [0], clen_symbols=spelt)
+        c.lits(w, b"abba")
+        c.eob(w)
+    add("repeat_16_after_17_and_18", "ok", rep_after_zero_runs, b"abba")
+
+    # -- header fields, block type
+    add("hlit_30", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], hlit=30), tail(w)))
+    add("hlit_31", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], hlit=31), tail(w)))
+    add("hdist_30", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], hdist=30), tail(w)))
+    add("hdist_31", "bad", lambda w: (db.dynamic_header(w, 1, lit2(abc), [0], hdist=31), tail(w)))
+    add("block_type_3", "bad", lambda w: (db.block_header(w, 1, 3), tail(w)))
+    add("block_type_3_second", "bad", lambda w: (fixed(0)(w), fx.lits(w, b"ab"), fx.eob(w), db.block_header(w, 1, 3), tail(w)))
+
+    # -- symbols of the fixed codes
+    for s in (286, 287):
+        add(f"fixed_symbol_{s}", "bad", lambda w, s=s: (fixed()(w), fx.lits(w, b"a"), fx.sym(w, s), tail(w)))
+    for s in (30, 31):
+        add(f"fixed_distance_{s}", "bad", lambda w, s=s: (fixed()(w), fx.lits(w, b"a"), fx.sym(w, 257), fx.dsym(w, s), tail(w)))
+    add("length_258_as_285", "ok", lambda w: (fixed()(w), fx.lits(w, b"a"), fx.match(w, 258, 1), fx.eob(w)), b"a" * 259)
+    add("length_258_as_284_extra_31", "ok", lambda w: (fixed()(w), fx.lits(w, b"a"), fx.match(w, 258, 1, long284=True), fx.eob(w)), b"a" * 259)
+
+    # -- distances against the bytes produced so far (no distance is longer than 32 768: o + 1 cannot be said at o = 32 768)
+    for o, dist, verdict in ((0, 1, "bad"), (1, 2, "bad"), (1, 1, "ok"), (32767, 32768, "bad"), (32767, 32767, "ok"), (32768, 32768, "ok")):
+        def f(w, o=o, dist=dist):
+            fixed()(w)
+            if o:
+                fx.run(w, o)
+            fx.match(w, 3, dist)
+            fx.eob(w)
+        add(f"distance_{dist}_at_{o}", verdict, f, b"a" * (o + 3))
+
+    # -- stored blocks
+    line = b"a stored line"
+    add("stored_empty_then_final", "ok", lambda w: (db.stored_block(w, 0, b""), db.stored_block(w, 1, line)), line)
+    add("stored_len_not_nlen", "bad", lambda w: db.stored_block(w, 1, line, nlength=len(line) ^ 0xFFFE))
+    add("stored_after_unaligned_fixed", "ok", lambda w: (fixed(0)(w), fx.lits(w, b"ab"), fx.eob(w), db.stored_block(w, 1, line)), b"ab" + line)
+    add("stored_len_past_the_input", "bad", lambda w: db.stored_block(w, 1, line, length=100))
+
+    # -- fixed, dynamic, fixed: the tables are rebuilt for the second fixed block, whose match reaches into the first one's bytes
+    def three_blocks(w):
+        fixed(0)(w)
+        fx.lits(w, b"hello ")
+        fx.eob(w)
+        a = {s: 3 for s in b"world "}
+        a.update({256: 3, 257: 3})  # w o r l d ' ' + end + length 3: eight 3-bit codes
+        c = db.dynamic_header(w, 0, lit2(a), [1, 1])
+        c.lits(w, b"world ")
+        c.eob(w)
+        fixed(1)(w)
+        fx.match(w, 5, 12)
+        fx.eob(w)
+    add("fixed_dynamic_fixed", "ok", three_blocks, b"hello world hello")
+
+    # -- the order of the verdicts at the cap: cap + 1 bytes (what zlib is given room for), then one more thing
+    pre = cap + 1
+    after = [("eob", "big", lambda w: None), ("literal", "big", lambda w: fx.lits(w, b"a")), ("match", "big", lambda w: fx.match(w, 3, 1)),
+             ("distance_30", "bad", lambda w: (fx.sym(w, 257), fx.dsym(w, 30))), ("symbol_286", "bad", lambda w: fx.sym(w, 286))]
+    if pre + 1 <= 32768:
+        after.append(("match_too_far", "big", lambda w: fx.match(w, 3, pre + 1)))  # (room is asked for before the distance is looked at)
+    for nm, verdict, more in after:
+        add(f"cap_plus_1_then_{nm}", verdict, lambda w, more=more: (fixed()(w), fx.run(w, pre), more(w), fx.eob(w)),
+            b"a" * pre if nm == "eob" else b"")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def hand_streams(max_inflated: int = DEFAULT_MAX):
+    """[(name, datagram, expected status)]: deflate streams no compressor writes (tests/deflate_build.py), every body as a zlib stream
+    and as a gzip member, and every valid one once more with its checksum off by one.  The expected status is the table's, not the
+    model's: tests/test_inflate_cpu.py holds the two against each other, the 'cap_' cases at `max_inflated` (they are built for it),
+    the others at DEFAULT_MAX."""
+    import deflate_build as db
+
+    out = []
+    for name, body, payload, verdict in _hand_bodies(max_inflated):
+        for wrap, tag, ok, bad in ((db.wrap_zlib, "z", ZLIB, BAD_ZLIB), (db.wrap_gzip, "g", GZIP, BAD_GZIP)):
+            out.append((f"{name}_{tag}", wrap(body, payload), {"ok": ok, "bad": bad, "big": TOO_LARGE}[verdict]))
+            if verdict == "ok":
+                out.append((f"{name}_{tag}_check_off_by_one", wrap(body, payload, check_delta=1), bad))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def random_code_set_pool(n: int = 2000, seed: int = 1952):
+    """-> (n valid streams over random code sets (tests/deflate_build.py) around the lines of corpus_lines(16), alternating wrappers;
+    the same streams with one bit flipped in the first 40 bytes of the deflate body)"""
+    import deflate_build as db
+
+    rng = np.random.default_rng(seed)
+    lines = corpus_lines(16)
+    good, flipped = [], []
+    for k in range(n):
+        line = lines[k % len(lines)]
+        body = db.random_dynamic_stream(rng, line)
+        d = db.wrap_zlib(body, line) if k % 2 == 0 else db.wrap_gzip(body, line)
+        good.append(d)
+        head = 2 if k % 2 == 0 else 10
+        f = bytearray(d)
+        f[head + int(rng.integers(min(40, len(body))))] ^= 1 << int(rng.integers(8))
+        flipped.append(bytes(f))
+    return good, flipped
 
 
 def truncations():
