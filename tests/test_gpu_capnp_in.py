@@ -306,6 +306,8 @@ def encoder_corpus():
            simple(extra_ptrs={1: bad, 2: bad, 3: bad, 4: bad, 5: bad}), simple(extra_ptrs={5: txt(b"")}), simple(d1=3 | 5 << 8, extra_ptrs={4: txt(b"m")}),
            simple(d1=3 | 0xFF << 8), simple(ts=float("nan")), hand_built()[0]]
     r = __import__("random").Random(77)
+    from encode_sweep import qualified
+    stamps = [t for t in qualified("timestamps") if 0 < t < math.inf]  # (this route rejects NaN and ts <= 0)
     for _ in range(300):
         items = [(r.choice([b"k%d" % r.randrange(6), b"_k%d" % r.randrange(6), b"shared_prefix_%d" % r.randrange(4), b"\xc3\xa9"]), r.randrange(7), r.getrandbits(64),
                   r.choice([b"v", b"", b'q"\\', b"\xe2\x82\xac"]), r.random() < 0.5) for _ in range(r.choice([0, 1, 3, 9, 40]))]
@@ -318,7 +320,7 @@ def encoder_corpus():
             ptrs[4] = txt(b"msg %d" % r.randrange(99))
         if r.random() < 0.7:
             ptrs[5] = txt(b"full %d" % r.randrange(99))
-        out.append(simple(ts=r.choice([1.5, 1438790025.637824, 1e25]), d1=r.randrange(40) | r.randrange(10) << 8, extra_ptrs=ptrs))
+        out.append(simple(ts=r.choice([1.5, 1438790025.637824, 1e25] + stamps), d1=r.randrange(40) | r.randrange(10) << 8, extra_ptrs=ptrs))
     big = W.serialize(W.Record(ts=9.0, hostname="h", msg="m", full_msg="x" * 9000, sd=[W.StructuredData("id", [("k", W.SDValue("U64", 7))])]), [("e", "v")])
     return out + [big]
 
