@@ -658,6 +658,18 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
             __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): LDS writes retired
             tm2 = __builtin_amdgcn_s_memtime();
         }
+        // ---- the next group's geometry from its offsets, BEFORE the row goes out: the readfirstlane of the offsets is the one vmcnt
+        // wait of this stretch, and in front of the stores it covers the two offset loads alone, requested a whole stage A ago (the
+        // window has landed, the stores are not issued yet).  Behind the stores -- which sit under an exec-masked branch, so the
+        // compiler cannot count them, and gfx950 has no store counter of its own -- the same wait was a vmcnt(0) for ten store
+        // acknowledgements, every group, before the first window load went out.
+        uint64_t pa0 = 0;
+        uint32_t pspan = 0, pnl = 0, pst = 0, ptb = 0, plast2 = 0;
+        if (more) {
+            if constexpr (HEAD) geometry_head(pn, no0, no1, &pnl, &pspan, &pst, &ptb);
+            else geometry(pn, no0, no1, &pnl, &pa0, &pspan);
+        }
+        FG_MARK(ST);
 #if defined(FG_ROW64_AB) && FG_ROW64_AB == 2
         if (rq_nl != 0u && !(ablate & 1u)) {
             uint4* g = reinterpret_cast<uint4*>(t.meta) + rq_p * 4u;
@@ -671,20 +683,19 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
 #else
         if (pend_valid && !(ablate & 1u)) store_row(t, pend_li, pend);
 #endif
-        // ---- prefetch: the next group's geometry from its offsets, then its bytes into the register window ----
-        uint64_t pa0 = 0;
-        uint32_t pspan = 0, pnl = 0, pst = 0, ptb = 0, plast2 = 0;
+        // ---- prefetch: the next group's bytes into the register window, back to back with the stores (stores first: stage A's
+        // progressive vmcnt(k) waits count the loads behind them exactly) ----
+        FG_MARK(W0);
         if (more) {
             if constexpr (HEAD) {
-                geometry_head(pn, no0, no1, &pnl, &pspan, &pst, &ptb);
                 load_window_head(no0, pst, v);
                 plast2 = load_last2(no0, no1);
             } else {
-                geometry(pn, no0, no1, &pnl, &pa0, &pspan);
                 load_window(pa0, pspan, v);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
+        FG_MARK(W1);
         FG_MARK(B);
         if (PROF) tm3 = __builtin_amdgcn_s_memtime();
         __syncthreads();  // single-wave workgroup: orders the LDS writes before stage B's reads
@@ -695,24 +706,41 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
             // terminator stripping (BufRead::lines / split(0) semantics, see fg_frame.hip)
             uint64_t e1 = o1;
             uint32_t l2 = last2;  // (HEAD) the last two bytes of the line AS DECODED, i.e. behind its terminator
-            if (fr.strip != FG_FRAME_NONE && valid && e1 > o0) {
-                auto byte_at = [&](uint64_t q) -> uint32_t {
-                    if constexpr (HEAD) return (uint32_t)bytes[q];
-                    return (q - a0) < (uint64_t)span ? (uint32_t)smem[q - a0] : (uint32_t)bytes[q];
-                };
-                const uint32_t b1 = HEAD ? (last2 & 0xFFu) : byte_at(e1 - 1);
-                if (fr.strip == FG_FRAME_LINE) {
-                    if (b1 == '\n') {
-                        --e1;
-                        if (e1 > o0 && (HEAD ? ((last2 >> 8) & 0xFFu) : byte_at(e1 - 1)) == '\r') --e1;
+            if (fr.strip != FG_FRAME_NONE) {  // (wave-uniform)
+                // The line's last byte and the one before it (0 where it has none).  Whole lines are read where they lie, in the tile:
+                // every line of a group is there by construction.  The one exception, a line longer than the tile, is a group of its own
+                // (nl == 1, wave-uniform) and takes its two bytes from global memory in a branch that waits for them itself.  One
+                // expression that picked between the tile and global memory per lane was a flat load, and a flat load left stage B with
+                // a full vmcnt wait -- for the whole next window -- whatever the framing.
+                uint32_t b1 = last2 & 0xFFu, b2 = (last2 >> 8) & 0xFFu;
+                if constexpr (!HEAD) {
+                    const uint64_t len = o1 - o0;
+                    const bool over = nl == 1u && __builtin_amdgcn_readfirstlane((int)((o1 - a0) > (uint64_t)span)) != 0;
+                    if (over) {
+                        FG_RARE_BEGIN();
+                        if (valid && len >= 1u) b1 = bytes[o1 - 1u];
+                        if (valid && len >= 2u) b2 = bytes[o1 - 2u];
+                        FG_RARE_END();  // (waits for the two bytes here, not where the paths meet again)
+                    } else if (valid) {
+                        const uint32_t q = (uint32_t)(o1 - a0);  // <= span
+                        if (len >= 1u) b1 = smem[q - 1u];
+                        if (len >= 2u) b2 = smem[q - 2u];
                     }
-                } else if (b1 == 0u) {
-                    --e1;
                 }
-                if (HEAD && e1 != o1) {  // (rare in HEAD mode -- long lines come framed by offsets -- so: two plain loads)
-                    l2 = 0u;
-                    if (e1 - o0 >= 1u) l2 = byte_at(e1 - 1);
-                    if (e1 - o0 >= 2u) l2 |= byte_at(e1 - 2) << 8;
+                if (valid && e1 > o0) {
+                    if (fr.strip == FG_FRAME_LINE) {
+                        if (b1 == '\n') {
+                            --e1;
+                            if (e1 > o0 && b2 == '\r') --e1;
+                        }
+                    } else if (b1 == 0u) {
+                        --e1;
+                    }
+                    if (HEAD && e1 != o1) {  // (rare in HEAD mode -- long lines come framed by offsets -- so: two plain loads)
+                        l2 = 0u;
+                        if (e1 - o0 >= 1u) l2 = bytes[e1 - 1];
+                        if (e1 - o0 >= 2u) l2 |= (uint32_t)bytes[e1 - 2] << 8;
+                    }
                 }
             }
             // Every line of the group lies inside the tile by construction -- except a single line longer than the whole tile,

@@ -812,6 +812,7 @@ struct Rfc5424FormatT {
     const uint64_t sd_ballot = __ballot(sd_any);
     const bool group_has_sd = __any(sd_any && len - f.d0 > kShortSdTail) || __popcll(sd_ballot) > 4;  // wave-uniform
     const bool sd_lane = sd_any && group_has_sd;
+    FG_MARK(F);  // the end of the straight-line fast path: up to here no line of a staged group waits for global memory
     tick(0);
     sd2::Lds SL{};
     sd2::LineIn sin{false, 0u, 0u, 0u, false};
@@ -919,8 +920,10 @@ struct Rfc5424FormatT {
                 r.off[k] = 0;
                 r.len[k] = FG_NONE;
             }
+            FG_RARE_BEGIN();  // (a line that is not in the tile: it waits for its own loads, dword by dword)
             GlobalReader rd(reinterpret_cast<const uint32_t*>(bytes), o0);
             parse_line_generic(rd, len, r, t);
+            FG_RARE_END();
         }
     }
 
@@ -969,16 +972,20 @@ struct Rfc5424FormatT {
             } else if (from_global || (sd_lane && stash)) {
                 // parsed from global memory -- or a line whose records did not fit its consumed bytes, whose copy in the tile is
                 // therefore no longer intact
+                FG_RARE_BEGIN();
                 GlobalReader rd(reinterpret_cast<const uint32_t*>(bytes), o0);
                 sd_walk<true>(rd, r.data0, len, &msg_at, &cnt, t, first);
+                FG_RARE_END();
             } else if (sd_lane) {  // (measurement build without records: the tile is intact)
                 sd_walk_tile<SD_EMIT>(T, base, r.data0, walk_len, &msg_at, &cnt, t, first);
             } else if (in_tile) {
                 LdsReader rd(T.w, base);
                 sd_walk<true>(rd, r.data0, len, &msg_at, &cnt, t, first);
             } else {
+                FG_RARE_BEGIN();
                 GlobalReader rd(reinterpret_cast<const uint32_t*>(bytes), o0);
                 sd_walk<true>(rd, r.data0, len, &msg_at, &cnt, t, first);
+                FG_RARE_END();
             }
         }
     }

@@ -22,12 +22,25 @@
 #endif
 
 // FG_MARK(k): with -DFG_ASM_MARKS a comment line "; FGMARK k" in the device assembly (tools/valu_count.py counts the instructions
-// between marks: these kernels are VALU-issue bound, so the static count of a straight-line phase IS its cost); else nothing
+// between marks: these kernels are VALU-issue bound, so the static count of a straight-line phase IS its cost); else nothing.
+// tools/hot_waits.py lists the vmcnt waits by the mark they follow.  The marks of the streaming loop (fg_pipeline.hpp): A stage A,
+// S stage A done (the row stores follow), W0 / W1 in front of the first / behind the last window load, B stage B, Z its end; a format
+// marks the end of its straight-line fast path with F.  RARE_BEGIN .. RARE_END bracket a block that is seldom run and may wait for
+// loads of its own (a line longer than the tile, read from global memory).
 #if defined(__HIP_DEVICE_COMPILE__) && defined(FG_ASM_MARKS)
 #define FG_MARK(k) asm volatile("; FGMARK " #k)
 #else
 #define FG_MARK(k) ((void)0)
 #endif
+// A rare block waits for its loads BEFORE it ends (vmcnt(0), lgkmcnt untouched): a load still pending where the block meets the common
+// path again -- one that a walk issued ahead and then left without reading -- makes the compiler wait for ALL loads, the next group's
+// window among them, in front of the next instruction on the common path that writes the same register.
+#define FG_RARE_BEGIN() FG_MARK(RARE_BEGIN)
+#define FG_RARE_END()                        \
+    do {                                     \
+        __builtin_amdgcn_s_waitcnt(0x0F70);  \
+        FG_MARK(RARE_END);                   \
+    } while (0)
 
 namespace fg {
 namespace wv {
