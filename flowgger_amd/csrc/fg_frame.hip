@@ -68,6 +68,17 @@ __device__ __forceinline__ uint32_t utf8_err_flags(uint32_t b, uint32_t p) {
     return err & 0x80808080u;
 }
 
+// the chunk that holds the stream's end: its bytes behind position nv are the caller's memory, readable (nbytes rounded up to 16) and
+// nothing more -- read as zeros, so that the error bit AT position nv says "a sequence cut off by the end of the stream" and nothing else
+__device__ __forceinline__ uint4 zero_behind(uint4 q, uint32_t nv) {
+    if (nv < 16u) {
+        // dword d holds chunk bytes 4d .. 4d + 3:  nv >= 4d + 4 -> all four kept;  nv <= 4d -> none;  else its low nv - 4d bytes (1 .. 3)
+        auto keep = [&](uint32_t d) -> uint32_t { return nv >= 4u * d + 4u ? 0xFFFFFFFFu : nv <= 4u * d ? 0u : (1u << (8u * (nv - 4u * d))) - 1u; };
+        q.x &= keep(0u), q.y &= keep(1u), q.z &= keep(2u), q.w &= keep(3u);
+    }
+    return q;
+}
+
 // pass 1.  masks[chunk] = delimiter mask | error mask << 16 (chunk = 16 bytes); counts[block].
 // (blk0: first block of the range this launch covers -- a SLICE of the stream whose bytes have arrived; the pipelined host path frames
 //  slice by slice while the next one is still on the link)
@@ -99,11 +110,11 @@ __global__ __launch_bounds__(kWave) void k_frame_scan(const uint8_t* __restrict_
     uint32_t prev_row_last = before;
 #pragma unroll
     for (int k = 0; k < (int)kFrameRows; ++k) {
-        const uint4 q = make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]);
         // bytes of this chunk inside the stream: valid positions 0..nv-1; position nv (one past the
         // end of the stream) may carry the "sequence cut off by the end" error bit
         const uint64_t cpos = base + (uint64_t)(k * kWave + lane) * 16u;
         const uint32_t nv = cpos >= nbytes ? 0u : (nbytes - cpos >= 16u ? 16u : (uint32_t)(nbytes - cpos));
+        const uint4 q = zero_behind(make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]), nv);
         uint32_t dm = mask16_eq(q, delim_pat) & ((1u << nv) - 1u);
         // previous dword: lane-1's last dword; lane 0: last dword of the previous row / block
         uint32_t pw = __shfl_up(q.w, 1, kWave);
@@ -113,7 +124,7 @@ __global__ __launch_bounds__(kWave) void k_frame_scan(const uint8_t* __restrict_
         uint32_t em = 0;
         if (((q.x | q.y | q.z | q.w | pw) & 0x80808080u) != 0u) {
             em = gather16(utf8_err_flags(q.x, pw), utf8_err_flags(q.y, q.x), utf8_err_flags(q.z, q.y), utf8_err_flags(q.w, q.z));
-            em &= nv >= 16u ? 0xFFFFu : ((2u << nv) - 1u);  // keep position nv itself (zero fill = "not a continuation")
+            em &= nv >= 16u ? 0xFFFFu : ((2u << nv) - 1u);  // keep position nv itself (zero_behind: "not a continuation")
             if (cpos > nbytes) em = 0;
         }
         masks[blk * (kFrameBlock / 16u) + k * kWave + lane] = dm | (em << 16);
@@ -253,9 +264,9 @@ __global__ __launch_bounds__(kWave* kTileWaves) void k_frame_onepass(const uint8
     uint32_t prev_row_last = before;
 #pragma unroll
     for (int k = 0; k < (int)kFrameRows; ++k) {
-        const uint4 q = make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]);
         const uint64_t cpos = base + (uint64_t)(k * kWave + lane) * 16u;
         const uint32_t nv = cpos >= nbytes ? 0u : (nbytes - cpos >= 16u ? 16u : (uint32_t)(nbytes - cpos));
+        const uint4 q = zero_behind(make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]), nv);
         const uint32_t dm = mask16_eq(q, delim_pat) & ((1u << nv) - 1u);
         uint32_t pw = __shfl_up(q.w, 1, kWave);
         const uint32_t row_last = __shfl(q.w, kWave - 1, kWave);
@@ -264,7 +275,7 @@ __global__ __launch_bounds__(kWave* kTileWaves) void k_frame_onepass(const uint8
         uint32_t em = 0;
         if (((q.x | q.y | q.z | q.w | pw) & 0x80808080u) != 0u) {
             em = gather16(utf8_err_flags(q.x, pw), utf8_err_flags(q.y, q.x), utf8_err_flags(q.z, q.y), utf8_err_flags(q.w, q.z));
-            em &= nv >= 16u ? 0xFFFFu : ((2u << nv) - 1u);  // keep position nv itself (zero fill = "not a continuation")
+            em &= nv >= 16u ? 0xFFFFu : ((2u << nv) - 1u);  // keep position nv itself (zero_behind: "not a continuation")
             if (cpos > nbytes) em = 0;
         }
         m_lds[wv][k * kWave + lane] = dm | (em << 16);

@@ -354,7 +354,7 @@ __device__ __forceinline__ void fused_loop(const uint8_t* __restrict__ bytes, co
             dst[idx] = q;
             F::classify_store(q, bm16, idx, bm_stride, idx < nchunk ? term4 : wv::kPastSpan);
             const uint32_t pw = wv::shfl_up1(q.w, row_last);
-            row_last = (uint32_t)__builtin_amdgcn_readlane((int)q.w, 63);
+            row_last = (uint32_t)__builtin_amdgcn_readlane((int)q.w, 63);  // (lane 63: only a whole row is followed by another)
             uint32_t m = fuse::chunk_masks(q.x, q.y, q.z, q.w, pw, term4, 16);
             if (idx == 0u) m = fuse::pre_chunk_mask(m, false);
             if (idx >= nchunk) m = 0u;
@@ -426,7 +426,7 @@ __device__ __forceinline__ void fused_loop(const uint8_t* __restrict__ bytes, co
                 uint4 q = make_uint4(0u, 0u, 0u, 0u);
                 if (in_row && cpos + 16u <= padded) q = stream_load(reinterpret_cast<const uint4*>(bytes + cpos));
                 const uint32_t pw = wv::shfl_up1(q.w, carry);
-                carry = (uint32_t)__builtin_amdgcn_readlane((int)q.w, 63);
+                carry = wv::shfl(q.w, (ext >> 4) - 1u);  // (the row's last chunk: lane 63 only when the row is a whole KiB)
                 uint32_t m = 0u;
                 if (in_row) {
                     dst[idx] = q;

@@ -11,7 +11,8 @@ import numpy as np
 HERE = Path(__file__).resolve().parent / "native"
 ROOT = HERE.parent.parent
 LIB = HERE / "libfuse_host.so"
-SRC = [HERE / "fuse_host.cpp", HERE / "fg_wave_emu.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_fuse.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_wave.hpp"]
+SRC = [HERE / "fuse_host.cpp", HERE / "fg_wave_emu.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_fuse.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_wave.hpp",
+       ROOT / "flowgger_amd" / "csrc" / "fg_fused_plan.hpp"]
 
 
 def build() -> Path:
@@ -33,6 +34,14 @@ class FuseHost:
         look = C.c_uint32()
         s = self.lib.fgf_plan(C.c_uint64(avg_len), C.c_uint32(lines), C.c_uint32(tile_cap), C.byref(look))
         return int(s), int(look.value)
+
+    def geometry(self, fmt: int, avg_line: int, lines_per_group: int = 0, tile_cap: int = 0, fused_look: int = 0, fused_ext: int = 0,
+                 flags: int = 0, link_bound: bool = False) -> dict:
+        """fg::fused_geometry: what a fused launch of `fmt` looks like under these launch options"""
+        out = (C.c_uint32 * 8)()
+        self.lib.fgf_geometry(C.c_int(fmt), C.c_uint64(avg_line), C.c_uint32(lines_per_group), C.c_uint32(tile_cap), C.c_uint32(fused_look),
+                              C.c_uint32(fused_ext), C.c_uint32(flags), C.c_int(1 if link_bound else 0), out)
+        return dict(S=int(out[0]), look=int(out[1]), tile=int(out[2]), ext=int(out[3]), L=int(out[4]), variant=int(out[5]), ok=bool(out[6]))
 
     def frame(self, raw: bytes, delim: int, final: bool, S: int, look: int, tile_cap: int, lines: int = 64, garbage: int = 0x0A):
         """-> (starts, ends, bad, consumed, passes, scans); what lies behind the stream's end inside its last 16 bytes is `garbage`"""

@@ -24,6 +24,20 @@ extern "C" uint32_t fgf_plan(uint64_t avg_len, uint32_t lines, uint32_t tile_cap
     return p.S;
 }
 
+// The geometry a fused launch of `fmt` takes for lines of avg_line bytes under these launch options (fg::fused_geometry, the arithmetic the
+// C ABI plans every fused launch with): out = S, look, tile, ext, L, variant, ok, plan.
+extern "C" void fgf_geometry(int fmt, uint64_t avg_line, uint32_t lines_per_group, uint32_t tile_cap, uint32_t fused_look, uint32_t fused_ext,
+                             uint32_t flags, int link_bound, uint32_t out[8]) {
+    fg_launch_opts lo{};
+    lo.lines_per_group = lines_per_group;
+    lo.tile_cap = tile_cap;
+    lo.fused_look = fused_look;
+    lo.fused_ext = fused_ext;
+    lo.flags = flags;
+    const FusedGeom g = fused_geometry((fg_format)fmt, avg_line, lo, link_bound != 0);
+    out[0] = g.S, out[1] = g.look, out[2] = g.tile, out[3] = g.ext, out[4] = g.L, out[5] = g.variant, out[6] = g.ok ? 1u : 0u, out[7] = g.plan;
+}
+
 // Frames of bytes[0 .. nbytes) (readable up to nbytes rounded up to 16; what lies behind nbytes is garbage on purpose), delimiter
 // `delim`, tiles of S bytes with `look` bytes of look-ahead, at most `lines` lines per pass.  starts / ends / bad: cap entries.
 // Returns the number of frames (may exceed cap: then only cap were written), -1 on an error.  *consumed = the bytes the frames cover.

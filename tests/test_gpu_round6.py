@@ -102,12 +102,14 @@ def check_rows(oracle, fmt, cfg, dec_cfg, raw, framing, starts, ends, valid, tab
         j += 1
 
 
-def run_device(dec, raw, framing, final, avg_line=0, cap=None):
+def run_device(dec, raw, framing, final, avg_line=0, cap=None, fill=None):
     import torch
 
     dev = torch.device("cuda", dec.device)
     padded = (len(raw) + 15) & ~15
-    host = np.full(padded + 16, 0x0A if framing == L.FG_FRAME_LINE else 0, np.uint8)  # what lies behind the stream is terminators on purpose
+    if fill is None:
+        fill = 0x0A if framing == L.FG_FRAME_LINE else 0  # what lies behind the stream is terminators on purpose
+    host = np.full(padded + 16, fill, np.uint8)
     host[: len(raw)] = np.frombuffer(raw, np.uint8)
     d_bytes = torch.from_numpy(host).to(dev)[: len(raw)]
     cap = cap if cap is not None else len(raw) // 2 + 16
