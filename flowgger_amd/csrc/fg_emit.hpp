@@ -234,10 +234,8 @@ struct PackSink {
     // bytes [lo, hi) of the block at q, from its completed dwords (index < full) and `ac` (index == full): whole dwords as dwords.
     // A message's first and last block only -- ONE copy of the code per kernel, by value (inlined at each of the emitters' ~150 sink
     // calls it was most of the write kernel's 74 000 vector instructions).
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FG_EMIT_INLINE_STORE_PART)  // (the macro: an A/B build)
+#if defined(__HIP_DEVICE_COMPILE__)
     static __device__ __attribute__((noinline))
-#elif defined(__HIP_DEVICE_COMPILE__)
-    static __device__ __forceinline__
 #else
     static inline
 #endif
