@@ -99,16 +99,7 @@ int fg_last_capnp_stop(const fg_ctx* ctx) { return ctx ? ctx->last_capnp_stop : 
 
 int fg_tables_layout(uint64_t n, uint64_t ent_cap, uint64_t sizes[FG_TABLE_ARRAYS]) {
     if (!sizes) return FG_ERR_ARG;
-    sizes[0] = n * 4;
-    sizes[1] = n * 8;
-    for (int k = 2; k < 8; ++k) sizes[k] = n * 8;
-    sizes[8] = n * 4;
-    sizes[9] = n * 4;
-    sizes[10] = ent_cap * 8;
-    sizes[11] = ent_cap * 8;
-    sizes[12] = ent_cap;
-    sizes[13] = ent_cap;
-    sizes[14] = 8;
+    fg::layout(n, ent_cap, sizes);
     return FG_OK;
 }
 
@@ -338,10 +329,7 @@ int fg_merge_tables_device(fg_ctx* ctx, const fg_tables* parts, uint32_t g, cons
     uint64_t rows = 0, cap = 0, max_rows = 0, max_cap = 0;
     // every column the merge kernels read or write must be there (a table without its entry counter was a device fault)
     auto complete = [](const fg_tables& t, bool entries) {
-        const bool rows_ok = t.n == 0 || (t.meta && t.ts && t.hostname && t.appname && t.procid && t.msgid && t.msg && t.full_msg && t.ent_first &&
-                                          t.ent_count);
-        const bool ent_ok = !entries || (t.ent_name && t.ent_val && t.ent_type && t.ent_flags);
-        return rows_ok && ent_ok && t.ent_used != nullptr;
+        return (t.n == 0 || fg::has_rows(t)) && (!entries || fg::has_entries(t)) && t.ent_used != nullptr;
     };
     if (!complete(*out, out->ent_cap != 0)) return FG_ERR_ARG;
     for (uint32_t k = 0; k < g; ++k) {

@@ -16,6 +16,7 @@
 #include "fg_device.hpp"
 #include "fg_enc_cfg.hpp"
 #include "fg_fused_plan.hpp"
+#include "fg_table_cols.hpp"
 #include <time.h>
 
 #include "fg_rfc3164_parse.hpp"
@@ -251,33 +252,32 @@ inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 // carve `base` into the arrays of an fg_tables (256-byte aligned pieces)
 void carve(uint8_t* base, uint64_t n, uint64_t ent_cap, fg_tables* t, uint64_t* total) {
     uint64_t sizes[FG_TABLE_ARRAYS];
-    fg_tables_layout(n, ent_cap, sizes);
+    fg::layout(n, ent_cap, sizes);
+    if (t) {
+        t->n = n;
+        t->ent_cap = ent_cap;
+    }
     uint64_t off = 0;
-    uint8_t* p[FG_TABLE_ARRAYS];
     for (int k = 0; k < FG_TABLE_ARRAYS; ++k) {
-        p[k] = base ? base + off : nullptr;
+        if (t) fg::set_col(t, k, base ? base + off : nullptr);
         off += up(sizes[k], 256);
     }
     if (total) *total = off;
-    if (!t) return;
-    t->n = n;
-    t->ent_cap = ent_cap;
-    t->meta = (uint32_t*)p[0];
-    t->ts = (double*)p[1];
-    t->hostname = (fg_span*)p[2];
-    t->appname = (fg_span*)p[3];
-    t->procid = (fg_span*)p[4];
-    t->msgid = (fg_span*)p[5];
-    t->msg = (fg_span*)p[6];
-    t->full_msg = (fg_span*)p[7];
-    t->ent_first = (uint32_t*)p[8];
-    t->ent_count = (uint32_t*)p[9];
-    t->ent_name = (fg_span*)p[10];
-    t->ent_val = (uint64_t*)p[11];
-    t->ent_type = (uint8_t*)p[12];
-    t->ent_flags = (uint8_t*)p[13];
-    t->ent_used = (uint64_t*)p[14];
 }
+inline uint64_t carved_bytes(uint64_t n, uint64_t ent_cap) {
+    uint64_t total = 0;
+    carve(nullptr, n, ent_cap, nullptr, &total);
+    return total;
+}
+
+// The entry table of a host-buffer call is sized from the input bytes and grown from what the counter reports (include/fg_hip.h,
+// fg_tables::ent_used): one entry per 16 (RFC5424) / 8 input bytes to start with; RFC3164 produces no entries.
+constexpr uint64_t kEntCapMax = 0xFFFFFFF0ull;  // (ent_first is 32 bits wide)
+inline uint64_t first_ent_cap(fg_format fmt, uint64_t nbytes) {
+    if (fmt == FG_RFC3164) return 16;
+    return std::min(fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024, kEntCapMax);
+}
+inline uint64_t next_ent_cap(uint64_t used) { return std::min(used + used / 8 + 1024, kEntCapMax); }
 
 fg::DevTables to_dev(const fg_tables& t) {
     fg::DevTables d;
@@ -329,6 +329,39 @@ int grow_pinned(fg_ctx* ctx, void** p, uint64_t* cap, uint64_t need) {
     FG_HIP(ctx, hipHostMalloc(p, want, hipHostMallocDefault));
     *cap = want;
     return FG_OK;
+}
+
+// ctx->h_cnt: one pinned 64 KiB block of words the pipelined host paths read small results through.  Who owns which words:
+constexpr uint32_t kCntWords = 8192;
+constexpr uint32_t kCntSlices = 0, kMaxFrameSlices = 4096;  // frame_decode_sliced: the frame count after slice k, one word more for a tail's end
+constexpr uint32_t kCntEnts = kCntSlices + kMaxFrameSlices, kMaxDecodeSlices = 256;  // fg_decode_batch: the entry counter after slice k
+constexpr uint32_t kCntFused = kCntEnts + kMaxDecodeSlices;  // frame_decode_fused: frames, abort flag, entries
+constexpr uint32_t kCntEnd = kCntFused + 256;                // transcode_sliced: where the slice's messages end (a page of its own, as ever)
+static_assert(kCntFused + 3 <= kCntEnd && kCntEnd + 1 <= kCntWords && kCntEnd * 8 % 4096 == 0, "the regions of h_cnt overlap or leave the block");
+int ensure_h_cnt(fg_ctx* ctx) {
+    if (!ctx->h_cnt) FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_cnt, kCntWords * 8, hipHostMallocDefault));
+    return FG_OK;
+}
+
+// device -> host copies of table columns on `stream`: one hipMemcpyAsync per column, in fg_tables order, nothing for an empty range
+int copy_cols(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, fg::ColKind kind, uint64_t i0, uint64_t cnt, hipStream_t stream) {
+    for (int k = 0; k < FG_TABLE_ARRAYS && cnt; ++k) {
+        const fg::TableCol& c = fg::kTableCols[k];
+        if (c.kind == kind) FG_HIP(ctx, hipMemcpyAsync(fg::col(dst, k) + i0 * c.elem, fg::col(src, k) + i0 * c.elem, cnt * c.elem, hipMemcpyDeviceToHost, stream));
+    }
+    return FG_OK;
+}
+int copy_rows(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, uint64_t r0, uint64_t rows, hipStream_t stream) {
+    return copy_cols(ctx, dst, src, fg::COL_ROW, r0, rows, stream);
+}
+int copy_entries(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, uint64_t e0, uint64_t e1, hipStream_t stream) {
+    return copy_cols(ctx, dst, src, fg::COL_ENT, e0, e1 > e0 ? e1 - e0 : 0, stream);
+}
+// a whole table: n rows, the first `used` entry slots, the counter
+int copy_table(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, uint64_t n, uint64_t used, hipStream_t stream) {
+    int rc;
+    if ((rc = copy_rows(ctx, dst, src, 0, n, stream)) != FG_OK || (rc = copy_entries(ctx, dst, src, 0, used, stream)) != FG_OK) return rc;
+    return copy_cols(ctx, dst, src, fg::COL_COUNTER, 0, 1, stream);
 }
 
 }  // namespace

@@ -17,7 +17,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/fg_hip.h"
+#include "fg_table_cols.hpp"
 
 namespace {
 
@@ -46,22 +46,18 @@ void parallel_for(uint64_t n, unsigned threads, F f) {
 uint64_t used_of(const fg_tables& t) { return t.ent_used ? *t.ent_used : 0; }
 
 bool part_ok(const fg_tables& p) {
-    if (p.n && (!p.meta || !p.ts || !p.hostname || !p.appname || !p.procid || !p.msgid || !p.msg || !p.full_msg || !p.ent_first ||
-                !p.ent_count))
-        return false;
+    if (p.n && !fg::has_rows(p)) return false;
     const uint64_t u = used_of(p);
     if (u > p.ent_cap) return false;
-    if (u && (!p.ent_name || !p.ent_val || !p.ent_type || !p.ent_flags)) return false;
+    if (u && !fg::has_entries(p)) return false;
     return true;
 }
 
 // the output table of a gather / merge: every column the n rows and e entries are written to must be there
 bool out_ok(const fg_tables* out, uint64_t n, uint64_t e) {
     if (!out || out->n < n || out->ent_cap < e || !out->ent_used) return false;
-    if (n && (!out->meta || !out->ts || !out->hostname || !out->appname || !out->procid || !out->msgid || !out->msg || !out->full_msg ||
-              !out->ent_first || !out->ent_count))
-        return false;
-    if (e && (!out->ent_name || !out->ent_val || !out->ent_type || !out->ent_flags)) return false;
+    if (n && !fg::has_rows(*out)) return false;
+    if (e && !fg::has_entries(*out)) return false;
     return true;
 }
 
@@ -69,10 +65,10 @@ bool out_ok(const fg_tables* out, uint64_t n, uint64_t e) {
 void copy_entries(const fg_tables& p, uint64_t base, fg_tables* out) {
     const uint64_t u = used_of(p);
     if (!u) return;
-    memcpy(out->ent_name + base, p.ent_name, u * sizeof(fg_span));
-    memcpy(out->ent_val + base, p.ent_val, u * 8);
-    memcpy(out->ent_type + base, p.ent_type, u);
-    memcpy(out->ent_flags + base, p.ent_flags, u);
+    for (int k = 0; k < FG_TABLE_ARRAYS; ++k) {
+        const fg::TableCol& c = fg::kTableCols[k];
+        if (c.kind == fg::COL_ENT) memcpy(fg::col(*out, k) + base * c.elem, fg::col(p, k), u * c.elem);
+    }
 }
 
 }  // namespace
@@ -106,12 +102,10 @@ int fg_gather_tables(const fg_tables* parts, uint32_t g, fg_tables* out) {
         const uint64_t r0 = row0, b = ent0;
         parallel_for(p.n, threads, [&, r0, b](uint64_t a, uint64_t z) {
             const uint64_t m = z - a;
-            memcpy(out->meta + r0 + a, p.meta + a, m * 4);
-            memcpy(out->ts + r0 + a, p.ts + a, m * 8);
-            fg_span* const dst[6] = {out->hostname, out->appname, out->procid, out->msgid, out->msg, out->full_msg};
-            const fg_span* const src[6] = {p.hostname, p.appname, p.procid, p.msgid, p.msg, p.full_msg};
-            for (int j = 0; j < 6; ++j) memcpy(dst[j] + r0 + a, src[j] + a, m * sizeof(fg_span));
-            memcpy(out->ent_count + r0 + a, p.ent_count + a, m * 4);
+            for (int k = 0; k < FG_TABLE_ARRAYS; ++k) {  // every row column as it is, but ent_first: rebased below
+                const fg::TableCol& c = fg::kTableCols[k];
+                if (c.kind == fg::COL_ROW && k != fg::kColEntFirst) memcpy(fg::col(*out, k) + (r0 + a) * c.elem, fg::col(p, k) + a * c.elem, m * c.elem);
+            }
             for (uint64_t i = a; i < z; ++i) out->ent_first[r0 + i] = p.ent_count[i] ? (uint32_t)(p.ent_first[i] + b) : 0u;
         });
         copy_entries(p, b, out);
@@ -148,13 +142,14 @@ int fg_merge_tables(const fg_tables* parts, uint32_t g, const uint64_t* const* i
         const uint64_t b = ent0;
         const uint64_t* ix = index[k];
         parallel_for(p.n, threads, [&, b, ix, k](uint64_t a, uint64_t z) {
-            fg_span* const dst[6] = {out->hostname, out->appname, out->procid, out->msgid, out->msg, out->full_msg};
-            const fg_span* const src[6] = {p.hostname, p.appname, p.procid, p.msgid, p.msg, p.full_msg};
+            fg_span* dst[fg::kSpanCols];
+            const fg_span* src[fg::kSpanCols];
+            for (int c = 0; c < fg::kSpanCols; ++c) dst[c] = fg::span_col(*out, c), src[c] = fg::span_col(p, c);
             for (uint64_t j = a; j < z; ++j) {
                 const uint64_t i = ix[j];
                 out->meta[i] = p.meta[j];
                 out->ts[i] = p.ts[j];
-                for (int c = 0; c < 6; ++c) dst[c][i] = src[c][j];
+                for (int c = 0; c < fg::kSpanCols; ++c) dst[c][i] = src[c][j];
                 out->ent_count[i] = p.ent_count[j];
                 out->ent_first[i] = p.ent_count[j] ? (uint32_t)(p.ent_first[j] + b) : 0u;
                 if (src_part) src_part[i] = (uint8_t)k;

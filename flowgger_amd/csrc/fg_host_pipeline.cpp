@@ -183,6 +183,12 @@ static int ensure_pipeline(fg_ctx* ctx, uint32_t slices) {
     ctx->s_down = ctx->stream3;
     return FG_OK;
 }
+// wait for everything a pipelined call has queued (its error paths: copies of earlier slices may still be in flight into the ctx's buffers)
+static void drain(fg_ctx* ctx) {
+    if (ctx->s_up) (void)hipStreamSynchronize(ctx->s_up);
+    (void)hipStreamSynchronize(ctx->stream);  // (s_run, and the one stream of a batch too small to be sliced)
+    if (ctx->s_down) (void)hipStreamSynchronize(ctx->s_down);
+}
 // slices of a host batch: small enough that filling and draining the pipeline costs little (1/8 of the batch at most), large
 // enough that a slice's fourteen API calls stay far below its transfer time
 static uint32_t slice_count(uint64_t nbytes, uint64_t n) {
@@ -192,7 +198,7 @@ static uint32_t slice_count(uint64_t nbytes, uint64_t n) {
     if (slice > (32ull << 20)) slice = 32ull << 20;
     uint64_t k = (nbytes + slice - 1) / slice;
     if (k < 1) k = 1;
-    if (k > 256) k = 256;
+    if (k > kMaxDecodeSlices) k = kMaxDecodeSlices;
     if (n < k) k = n ? n : 1;
     return (uint32_t)k;
 }
@@ -270,6 +276,15 @@ static const void* device_view_of_pinned(const void* p) {
     }
     return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
 }
+// ... and is [p, p + bytes) ONE mapping with a constant device-view delta from its first byte to its last?  (the first and
+// the last byte of two adjacent registrations both qualify, the bytes between their device views need not be contiguous.)
+static const void* pinned_span_device_view(const void* p, uint64_t bytes) {
+    const uint8_t* const dv = (const uint8_t*)device_view_of_pinned(p);
+    if (!dv || !bytes) return dv;
+    const uint8_t* const last = (const uint8_t*)p + bytes - 1u;
+    const uint8_t* const dv_last = (const uint8_t*)device_view_of_pinned(last);
+    return dv_last && dv_last - dv == last - (const uint8_t*)p ? dv : nullptr;
+}
 
 static int pinned_tables_for_kernels(fg_ctx* ctx, const fg_tables& ht, fg_tables* kt);
 
@@ -305,30 +320,16 @@ static int decode_batch_zero_copy(fg_ctx* ctx, fg_format fmt, const uint8_t* byt
     //  offsets before bytes, GELF's exact form: LTSV 0.81 -> 0.89 of the link, structured data 0.90 -> 0.93, GELF 0.85 -> 0.87 with four,
     //  profiles/r06aa_decode_batch_waves.log)
     LinkBoundGrid grid(ctx, fmt == FG_GELF ? 4u : 2u);
-    const uint8_t* d_bytes = (const uint8_t*)device_view_of_pinned(bytes);
-    const uint64_t* d_offsets = (const uint64_t*)device_view_of_pinned(offsets);
+    // one mapping each, up to the last byte the kernels touch: their 16-byte loads reach up to nbytes rounded up to 16 (include/fg_hip.h:
+    // the packed buffer must be readable that far)
+    const uint8_t* d_bytes = (const uint8_t*)pinned_span_device_view(bytes, up(nbytes, 16));
+    const uint64_t* d_offsets = (const uint64_t*)pinned_span_device_view(offsets, (n + 1) * 8);
     if (!d_bytes || !d_offsets || ((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_UNSUPPORTED;
-    {
-        // ONE mapping with a constant device-view delta from the first byte to the last the kernels touch (the first and
-        // the last byte of two adjacent registrations both qualify, the bytes between their device views need not be contiguous).
-        // The kernels' 16-byte loads reach up to nbytes rounded up to 16 (include/fg_hip.h: the packed buffer must be readable that far):
-        // that byte must be part of the same mapping too.
-        const uint8_t* last_b = bytes + ((nbytes + 15u) & ~15ull) - 1u;
-        const uint8_t* dv_last_b = (const uint8_t*)device_view_of_pinned(last_b);
-        const uint8_t* dv_last_o = (const uint8_t*)device_view_of_pinned(offsets + n);
-        if (!dv_last_b || !dv_last_o || dv_last_b - d_bytes != last_b - bytes ||
-            dv_last_o - (const uint8_t*)d_offsets != (const uint8_t*)(offsets + n) - (const uint8_t*)offsets)
-            return FG_ERR_UNSUPPORTED;
-    }
     int rc;
-    uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    if (fmt == FG_RFC3164) ent_cap = 16;  // RFC3164 produces no entries
+    uint64_t ent_cap = first_ent_cap(fmt, nbytes);
     const hipStream_t s = ctx->stream;
     for (;;) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t total = 0;
-        carve(nullptr, n, ent_cap, nullptr, &total);
-        if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, total)) != FG_OK) return rc;
+        if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, carved_bytes(n, ent_cap))) != FG_OK) return rc;
         fg_tables ht;
         carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
         fg_tables kt;  // what the kernels see: the pinned columns (their device view) and the counter in HBM
@@ -340,8 +341,8 @@ static int decode_batch_zero_copy(fg_ctx* ctx, fg_format fmt, const uint8_t* byt
         FG_HIP(ctx, hipMemcpyAsync(&used, ctx->d_used, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         if (used > ent_cap) {
-            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
-            ent_cap = used + used / 8 + 1024;
+            if (ent_cap >= kEntCapMax) return FG_ERR_ENT_OVERFLOW;
+            ent_cap = next_ent_cap(used);
             continue;
         }
         *ht.ent_used = used;
@@ -364,25 +365,16 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
     const uint32_t slices = slice_count(nbytes, n);
     TableShares shares(ctx, slices);
     if (slices > 1 && (rc = ensure_pipeline(ctx, slices)) != FG_OK) return rc;  // (a small batch stays on the ctx's own stream)
-    if (slices > 1 && !ctx->h_cnt) FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_cnt, 65536, hipHostMallocDefault));
+    if (slices > 1 && (rc = ensure_h_cnt(ctx)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 1) * 8)) != FG_OK) return rc;
     std::vector<uint64_t> cut(slices + 1);
     if (fg_shard_plan(offsets, n, slices, cut.data()) != FG_OK) return FG_ERR_ARG;
     const bool piped = slices > 1;
     const hipStream_t s_down = piped ? ctx->s_down : ctx->stream, s_up = piped ? ctx->s_up : s_down, s_run = piped ? ctx->s_run : s_down;
-    auto drain = [&]() {
-        (void)hipStreamSynchronize(s_up);
-        (void)hipStreamSynchronize(s_run);
-        (void)hipStreamSynchronize(s_down);
-    };
-    // entry capacity: start from one entry per 16 (RFC5424) / 8 input bytes, grow on overflow
-    uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    if (fmt == FG_RFC3164) ent_cap = 16;  // RFC3164 produces no entries
+    uint64_t ent_cap = first_ent_cap(fmt, nbytes);  // grown on overflow
     for (;;) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t total = 0;
-        carve(nullptr, n, ent_cap, nullptr, &total);
+        const uint64_t total = carved_bytes(n, ent_cap);
         if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, total)) != FG_OK) return rc;
         if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, total)) != FG_OK) return rc;
         fg_tables dt, ht;
@@ -394,10 +386,8 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
         // the entries its kernels appended -- the range between two counter values -- come back on the download stream).  The host
         // issues sixteen slices ahead of the one it collects, so the link has uploads queued at all times and every table, the
         // entry columns included, crosses it while later slices are still going up.
-        uint64_t* const ent_cnt = piped ? ctx->h_cnt + 1024 : nullptr;
+        uint64_t* const ent_cnt = piped ? ctx->h_cnt + kCntEnts : nullptr;
         bool first_issued = false;  // offsets[l0] of a slice belongs to the slice before it -- except for the first slice that has rows
-        fg_span* hs[6] = {ht.hostname, ht.appname, ht.procid, ht.msgid, ht.msg, ht.full_msg};
-        fg_span* ds[6] = {dt.hostname, dt.appname, dt.procid, dt.msgid, dt.msg, dt.full_msg};
         auto issue = [&](uint32_t k) -> int {
             const uint64_t l0 = cut[k], l1 = cut[k + 1], rows = l1 - l0;
             if (rows == 0) return FG_OK;
@@ -414,18 +404,7 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
                 FG_HIP(ctx, hipStreamWaitEvent(s_run, ctx->ev_slice[2 * k], 0));
             }
             // ---- decode
-            fg_tables sl = dt;  // the slice's rows: same arrays, shifted by l0
-            sl.n = rows;
-            sl.meta += l0;
-            sl.ts += l0;
-            sl.hostname += l0;
-            sl.appname += l0;
-            sl.procid += l0;
-            sl.msgid += l0;
-            sl.msg += l0;
-            sl.full_msg += l0;
-            sl.ent_first += l0;
-            sl.ent_count += l0;
+            const fg_tables sl = fg::rows_of(dt, l0, rows);  // the slice's rows: same arrays, shifted by l0
             const int drc = fg_decode_frames_impl(ctx, fmt, FG_FRAME_NONE, ctx->d_bytes, nbytes, ctx->d_offsets + l0, rows, nullptr, &sl, (void*)s_run, false,
                                                offsets[l1] - offsets[l0]);
             if (drc != FG_OK) return drc;
@@ -435,29 +414,13 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
             }
             return FG_OK;
         };
-        auto download_rows = [&](uint64_t l0, uint64_t rows) -> int {
-            FG_HIP(ctx, hipMemcpyAsync(ht.meta + l0, dt.meta + l0, rows * 4, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ts + l0, dt.ts + l0, rows * 8, hipMemcpyDeviceToHost, s_down));
-            for (int j = 0; j < 6; ++j) FG_HIP(ctx, hipMemcpyAsync(hs[j] + l0, ds[j] + l0, rows * 8, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_first + l0, dt.ent_first + l0, rows * 4, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_count + l0, dt.ent_count + l0, rows * 4, hipMemcpyDeviceToHost, s_down));
-            return FG_OK;
-        };
-        auto download_entries = [&](uint64_t e0, uint64_t e1) -> int {
-            if (e1 <= e0) return FG_OK;
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_name + e0, dt.ent_name + e0, (e1 - e0) * 8, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_val + e0, dt.ent_val + e0, (e1 - e0) * 8, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_type + e0, dt.ent_type + e0, e1 - e0, hipMemcpyDeviceToHost, s_down));
-            FG_HIP(ctx, hipMemcpyAsync(ht.ent_flags + e0, dt.ent_flags + e0, e1 - e0, hipMemcpyDeviceToHost, s_down));
-            return FG_OK;
-        };
         uint64_t used = 0;
         bool overflow = false;
         uint32_t issued = 0;
         for (uint32_t k = 0; k < slices && n; ++k) {
             while (issued < slices && issued < k + 16) {
                 if ((rc = issue(issued)) != FG_OK) {  // copies of earlier slices may still be in flight into h_tab / d_tab
-                    drain();
+                    drain(ctx);
                     return rc;
                 }
                 ++issued;
@@ -466,7 +429,7 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
             if (rows == 0) continue;
             if (piped) {
                 if (hipEventSynchronize(ctx->ev_slice[2 * k + 1]) != hipSuccess) {
-                    drain();
+                    drain(ctx);
                     return FG_ERR_HIP;
                 }
                 const uint64_t cnt = ent_cnt[k];  // the counter after this slice's kernels: its entries are [used, cnt)
@@ -474,37 +437,37 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
                     overflow = true;
                     break;
                 }
-                if ((rc = download_rows(l0, rows)) != FG_OK || (rc = download_entries(used, cnt)) != FG_OK) {
-                    drain();
+                if ((rc = copy_rows(ctx, ht, dt, l0, rows, s_down)) != FG_OK || (rc = copy_entries(ctx, ht, dt, used, cnt, s_down)) != FG_OK) {
+                    drain(ctx);
                     return rc;
                 }
                 used = cnt;
-            } else if ((rc = download_rows(l0, rows)) != FG_OK) {
-                drain();
+            } else if ((rc = copy_rows(ctx, ht, dt, l0, rows, s_down)) != FG_OK) {
+                drain(ctx);
                 return rc;
             }
         }
         if (!piped || overflow) {  // one stream (a small batch), or the entry table ran out: the counter's final value
             while (overflow && issued < slices) {  // (kernels past the capacity still count: the counter then says what the batch needs)
                 if ((rc = issue(issued)) != FG_OK) {
-                    drain();
+                    drain(ctx);
                     return rc;
                 }
                 ++issued;
             }
-            if (overflow) drain();
+            if (overflow) drain(ctx);
             FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s_run));
             FG_HIP(ctx, hipStreamSynchronize(s_run));
             overflow = used > ent_cap;
         }
         if (overflow) {
-            drain();
-            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
-            ent_cap = used + used / 8 + 1024;
+            drain(ctx);
+            if (ent_cap >= kEntCapMax) return FG_ERR_ENT_OVERFLOW;
+            ent_cap = next_ent_cap(used);
             continue;
         }
-        if (!piped && (rc = download_entries(0, used)) != FG_OK) {
-            drain();
+        if (!piped && (rc = copy_entries(ctx, ht, dt, 0, used, s_down)) != FG_OK) {
+            drain(ctx);
             return rc;
         }
         *ht.ent_used = used;
@@ -517,6 +480,8 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
 }
 
 static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int final, uint64_t* n_frames, uint64_t* consumed);
+static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t nbytes, uint64_t n, const uint8_t* d_bad,
+                                const uint8_t* d_src, fg_tables* out);
 
 // FG_FRAME_SYSLEN stage shared by fg_frame_decode_batch and fg_transcode_batch (the read_msglen / read_exact loop of
 // SyslenSplitter::run, syslen_splitter.rs:42-57, for a chunk): the chunk goes up as it is (one copy; from a pinned
@@ -537,15 +502,7 @@ static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int 
         if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
         if ((r = grow_dev(ctx, (void**)&ctx->d_sl_starts, &ctx->d_sl_starts_cap, (cap + 2) * 8)) != FG_OK) return r;
         if ((r = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return r;
-        if ((cap + 2) * 8 > ctx->h_off_cap) {
-            if (ctx->h_off) FG_HIP(ctx, hipHostFree(ctx->h_off));
-            ctx->h_off = nullptr;
-            ctx->h_off_cap = 0;
-            const uint64_t want = up((cap + 2) * 10, 1 << 16);
-            FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_off, want, hipHostMallocDefault));
-            ctx->h_off_cap = want;
-        }
-        return FG_OK;
+        return grow_pinned(ctx, (void**)&ctx->h_off, &ctx->h_off_cap, (cap + 2) * 8);
     };
     uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 1024, n = 0;
     int stop = FG_SYSLEN_CLEAN;
@@ -666,15 +623,10 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
     }
     *n_frames = n;
     if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
-    if (!syslen && (n + 1) * 8 > ctx->h_off_cap) {
-        if (ctx->h_off) FG_HIP(ctx, hipHostFree(ctx->h_off));
-        ctx->h_off = nullptr;
-        ctx->h_off_cap = 0;
-        uint64_t want = up((n + 1) * 8 + (n + 1) * 2, 1 << 16);
-        FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_off, want, hipHostMallocDefault));
-        ctx->h_off_cap = want;
+    if (!syslen) {
+        if ((rc = grow_pinned(ctx, (void**)&ctx->h_off, &ctx->h_off_cap, (n + 1) * 8)) != FG_OK) return rc;
+        FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     }
-    if (!syslen) FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     *out_offsets = ctx->h_off;
     if (n == 0) {
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -686,45 +638,7 @@ static int frame_decode_one_piece(fg_ctx* ctx, fg_format fmt, fg_framing framing
     const uint64_t used_bytes = syslen ? payload : *consumed;
     const uint8_t* const dec_bytes = syslen ? ctx->d_sl_packed : ctx->d_bytes;
     const fg_framing dec_framing = syslen || capnp ? FG_FRAME_NONE : framing;
-    uint64_t ent_cap = fmt == FG_RFC5424 ? used_bytes / 16 + 1024 : used_bytes / 8 + 1024;
-    for (;;) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t bytes_total = 0;
-        carve(nullptr, n, ent_cap, nullptr, &bytes_total);
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, bytes_total)) != FG_OK) return rc;
-        if (bytes_total > ctx->h_tab_cap) {
-            if (ctx->h_tab) FG_HIP(ctx, hipHostFree(ctx->h_tab));
-            ctx->h_tab = nullptr;
-            ctx->h_tab_cap = 0;
-            uint64_t want = up(bytes_total + bytes_total / 4, 1 << 20);
-            FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
-            ctx->h_tab_cap = want;
-        }
-        fg_tables dt, ht;
-        carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
-        carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
-        rc = fg_decode_frames_device(ctx, fmt, dec_framing, dec_bytes, used_bytes, ctx->d_offsets, n, capnp ? nullptr : ctx->d_bad, &dt, FG_STREAM_OWN);
-        if (rc != FG_OK) return rc;
-        uint64_t used = 0;
-        FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        if (used > ent_cap) {
-            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
-            ent_cap = used + used / 8 + 1024;
-            continue;
-        }
-        uint64_t sizes[FG_TABLE_ARRAYS];
-        fg_tables_layout(n, used, sizes);
-        void* dsts[FG_TABLE_ARRAYS] = {ht.meta, ht.ts, ht.hostname, ht.appname, ht.procid, ht.msgid, ht.msg, ht.full_msg,
-                                       ht.ent_first, ht.ent_count, ht.ent_name, ht.ent_val, ht.ent_type, ht.ent_flags, ht.ent_used};
-        void* srcs[FG_TABLE_ARRAYS] = {dt.meta, dt.ts, dt.hostname, dt.appname, dt.procid, dt.msgid, dt.msg, dt.full_msg,
-                                       dt.ent_first, dt.ent_count, dt.ent_name, dt.ent_val, dt.ent_type, dt.ent_flags, dt.ent_used};
-        for (int k = 0; k < FG_TABLE_ARRAYS; ++k)
-            if (sizes[k]) FG_HIP(ctx, hipMemcpyAsync(dsts[k], srcs[k], sizes[k], hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        *out = ht;
-        return FG_OK;
-    }
+    return decode_stage_to_host(ctx, fmt, dec_framing, used_bytes, n, capnp ? nullptr : ctx->d_bad, dec_bytes, out);
 }
 
 // the kernels' view of tables carved from the ctx's PINNED host block (zero-copy output): every column pointer translated to the
@@ -733,22 +647,7 @@ static int pinned_tables_for_kernels(fg_ctx* ctx, const fg_tables& ht, fg_tables
     const uint8_t* dv = (const uint8_t*)device_view_of_pinned(ctx->h_tab);
     if (!dv) return FG_ERR_UNSUPPORTED;
     if (!ctx->d_used) FG_HIP(ctx, hipMalloc((void**)&ctx->d_used, 256));
-    const ptrdiff_t delta = dv - ctx->h_tab;  // (0 under unified addressing)
-    *kt = ht;
-    kt->meta = (uint32_t*)((uint8_t*)ht.meta + delta);
-    kt->ts = (double*)((uint8_t*)ht.ts + delta);
-    kt->hostname = (fg_span*)((uint8_t*)ht.hostname + delta);
-    kt->appname = (fg_span*)((uint8_t*)ht.appname + delta);
-    kt->procid = (fg_span*)((uint8_t*)ht.procid + delta);
-    kt->msgid = (fg_span*)((uint8_t*)ht.msgid + delta);
-    kt->msg = (fg_span*)((uint8_t*)ht.msg + delta);
-    kt->full_msg = (fg_span*)((uint8_t*)ht.full_msg + delta);
-    kt->ent_first = (uint32_t*)((uint8_t*)ht.ent_first + delta);
-    kt->ent_count = (uint32_t*)((uint8_t*)ht.ent_count + delta);
-    kt->ent_name = (fg_span*)((uint8_t*)ht.ent_name + delta);
-    kt->ent_val = (uint64_t*)((uint8_t*)ht.ent_val + delta);
-    kt->ent_type = (uint8_t*)ht.ent_type + delta;
-    kt->ent_flags = (uint8_t*)ht.ent_flags + delta;
+    *kt = fg::shifted(ht, dv - ctx->h_tab);  // (by 0 under unified addressing)
     kt->ent_used = ctx->d_used;
     return FG_OK;
 }
@@ -791,27 +690,20 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
     const uint64_t nblk_total = nbytes / blk + 1;
     if ((rc = ensure_pipeline(ctx, slices)) != FG_OK) return rc;
     const hipStream_t s_up = ctx->s_up, s_run = ctx->s_run, s_down = ctx->s_down;
-    auto drain = [&]() {
-        (void)hipStreamSynchronize(s_up);
-        (void)hipStreamSynchronize(s_run);
-        (void)hipStreamSynchronize(s_down);
-    };
     // capacities from the ctx's experience: frames, rows, entries
     const uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 4096;
-    const uint64_t ent_cap0 = fmt == FG_RFC3164 ? 16 : fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    const uint64_t ent_cap = ent_cap0 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : ent_cap0;
+    const uint64_t ent_cap = first_ent_cap(fmt, nbytes);
     if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
     if ((rc = grow_pinned(ctx, (void**)&ctx->h_off, &ctx->h_off_cap, (cap + 2) * 8)) != FG_OK) return rc;
-    if (!ctx->h_cnt) FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_cnt, 65536, hipHostMallocDefault));
-    if (slices + 2 > 4096) return FG_ERR_UNSUPPORTED;
-    uint64_t* const cnt_dv = (uint64_t*)const_cast<void*>(device_view_of_pinned(ctx->h_cnt));
+    if ((rc = ensure_h_cnt(ctx)) != FG_OK) return rc;
+    if (slices + 2 > kMaxFrameSlices) return FG_ERR_UNSUPPORTED;
+    uint64_t* const h_slice_cnt = ctx->h_cnt + kCntSlices;
+    uint64_t* const cnt_dv = (uint64_t*)const_cast<void*>(device_view_of_pinned(h_slice_cnt));
     if (!cnt_dv) return FG_ERR_UNSUPPORTED;
-    uint64_t tab_bytes = 0;
-    carve(nullptr, cap, ent_cap, nullptr, &tab_bytes);
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, tab_bytes)) != FG_OK) return rc;
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, carved_bytes(cap, ent_cap))) != FG_OK) return rc;
     fg_tables ht, kt;
     carve(ctx->h_tab, cap, ent_cap, &ht, nullptr);
     if ((rc = pinned_tables_for_kernels(ctx, ht, &kt)) != FG_OK) return rc;
@@ -864,10 +756,7 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
     auto decode_rows = [&](uint64_t f0, uint64_t f1, uint64_t span_bytes) -> int {  // frames [f0, f1): decode into the pinned tables
         if (f1 == f0) return FG_OK;
         const uint64_t rows = f1 - f0;
-        fg_tables sl = kt;
-        sl.n = rows;
-        sl.meta += f0; sl.ts += f0; sl.hostname += f0; sl.appname += f0; sl.procid += f0; sl.msgid += f0; sl.msg += f0; sl.full_msg += f0;
-        sl.ent_first += f0; sl.ent_count += f0;
+        const fg_tables sl = fg::rows_of(kt, f0, rows);
         int r = fg_decode_frames_impl(ctx, fmt, framing, ctx->d_bytes, nbytes, ctx->d_offsets + f0, rows, ctx->d_bad + f0, &sl, (void*)s_run, false, span_bytes);
         if (r != FG_OK) return r;
         // the frames' offsets (8 bytes per frame) are the one thing still copied: behind the uploads on the copy engine, i.e. at the end
@@ -880,29 +769,29 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
     for (uint32_t k = 0; k < slices; ++k) {
         while (queued < slices && queued < k + (src_dv ? 4u : 2u)) {  // framing queued ahead of the decode being issued
             if ((rc = enqueue(queued)) != FG_OK) {
-                drain();
+                drain(ctx);
                 return rc;
             }
             ++queued;
         }
         if (hipEventSynchronize(ev[2 * k + 1]) != hipSuccess) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
-        const uint64_t total = ctx->h_cnt[k];  // delimiters up to the end of slice k = frames that are complete
+        const uint64_t total = h_slice_cnt[k];  // delimiters up to the end of slice k = frames that are complete
         if (total == FG_FRAME_ABORTED) {  // the one-pass scan gave up waiting on a tile (never seen): the one-piece path frames classically
-            drain();
+            drain(ctx);
             return FG_ERR_UNSUPPORTED;
         }
         if (total + 1 > cap) {
-            drain();
+            drain(ctx);
             ctx->frames_per_byte = (double)(total + 1) / (double)(((uint64_t)k + 1) * slice);
             return FG_ERR_UNSUPPORTED;
         }
         const uint64_t b1 = k + 1 == slices ? nbytes : ((uint64_t)k + 1) * slice;
         if (k + 1 < slices) {
             if ((rc = decode_rows(done, total, b1 - (uint64_t)k * slice)) != FG_OK) {
-                drain();
+                drain(ctx);
                 return rc;
             }
             done = total;
@@ -915,13 +804,13 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
         const bool tail = last_end != nbytes;
         uint64_t n = total;
         if (tail && final) {
-            ctx->h_cnt[slices] = nbytes;
-            FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets + total + 1, ctx->h_cnt + slices, 8, hipMemcpyHostToDevice, s_run));
+            h_slice_cnt[slices] = nbytes;
+            FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets + total + 1, h_slice_cnt + slices, 8, hipMemcpyHostToDevice, s_run));
             n = total + 1;
         }
         *consumed = (tail && !final) ? last_end : nbytes;
         if ((rc = decode_rows(done, n, *consumed > (uint64_t)k * slice ? *consumed - (uint64_t)k * slice : 1)) != FG_OK) {
-            drain();
+            drain(ctx);
             return rc;
         }
         done = n;
@@ -930,7 +819,7 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
         fg_tables all = kt;
         all.n = done;
         if ((rc = fg_finish_deferred_general(ctx, framing, ctx->d_bytes, ctx->d_offsets, done, ctx->d_bad, &all, (void*)s_run)) != FG_OK) {
-            drain();
+            drain(ctx);
             return rc;
         }
     }
@@ -938,7 +827,7 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
     FG_HIP(ctx, hipMemcpyAsync(&used, kt.ent_used, 8, hipMemcpyDeviceToHost, s_run));
     FG_HIP(ctx, hipStreamSynchronize(s_run));
     if (done) ctx->frames_per_byte = (double)done / (double)nbytes;
-    drain();
+    drain(ctx);
     if (used > ent_cap) return FG_ERR_UNSUPPORTED;
     *ht.ent_used = used;
     ht.n = done;
@@ -963,29 +852,21 @@ static int frame_decode_fused(fg_ctx* ctx, fg_format fmt, fg_framing framing, co
                               const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     if (nbytes == 0 || (ctx->lo.flags & (FG_LO_NO_FUSED_FRAMING | FG_LO_NO_ZERO_COPY | FG_LO_FRAME_CLASSIC | FG_LO_FRAME_SELFTEST_STALL | FG_LO_FRAME_KERNEL_UPLOAD))) return FG_ERR_UNSUPPORTED;
     if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF) return FG_ERR_UNSUPPORTED;
-    const uint8_t* d_bytes = (const uint8_t*)device_view_of_pinned(bytes);
+    const uint8_t* d_bytes = (const uint8_t*)pinned_span_device_view(bytes, up(nbytes, 16));  // (ONE mapping up to the last byte the kernels load)
     if (!d_bytes || ((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_UNSUPPORTED;
-    {
-        const uint8_t* last_b = bytes + ((nbytes + 15u) & ~15ull) - 1u;
-        const uint8_t* dv_last = (const uint8_t*)device_view_of_pinned(last_b);
-        if (!dv_last || dv_last - d_bytes != last_b - bytes) return FG_ERR_UNSUPPORTED;  // (ONE mapping up to the last byte the kernels load)
-    }
     LinkBoundGrid grid(ctx);
     int rc;
     // tables from the ctx's experience (frames per byte of its last chunk) and one entry per 16 / 8 input bytes; a chunk that holds more
     // of either says how many, and the launch is repeated ONCE PER TABLE with what it needs (another pass over the link -- the price
     // of the older forms' count-first as well -- and the next chunk is sized from this one)
     uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 4096;
-    uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    if (!ctx->h_cnt) FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_cnt, 65536, hipHostMallocDefault));
+    uint64_t ent_cap = first_ent_cap(fmt, nbytes);
+    if ((rc = ensure_h_cnt(ctx)) != FG_OK) return rc;
     const hipStream_t s = ctx->stream;
     fg_tables ht;
     uint64_t total = 0, used = 0;
     for (int attempt = 0;; ++attempt) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t tab_bytes = 0;
-        carve(nullptr, cap, ent_cap, nullptr, &tab_bytes);
-        if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, tab_bytes)) != FG_OK) return rc;
+        if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, carved_bytes(cap, ent_cap))) != FG_OK) return rc;
         if ((rc = grow_pinned(ctx, (void**)&ctx->h_off, &ctx->h_off_cap, (cap + 2) * 8)) != FG_OK) return rc;
         fg_tables kt;
         carve(ctx->h_tab, cap, ent_cap, &ht, nullptr);
@@ -994,7 +875,7 @@ static int frame_decode_fused(fg_ctx* ctx, fg_format fmt, fg_framing framing, co
         if (!off_dv) return FG_ERR_UNSUPPORTED;
         unsigned long long* d_total = nullptr;
         if ((rc = fg_frame_decode_impl(ctx, fmt, framing, d_bytes, nbytes, final, off_dv, cap, &kt, 0, (void*)s, &d_total)) != FG_OK) return rc;
-        uint64_t* const res = ctx->h_cnt + 2048;  // [0] frames [1] abort [2] entries
+        uint64_t* const res = ctx->h_cnt + kCntFused;  // [0] frames [1] abort [2] entries
         FG_HIP(ctx, hipMemcpyAsync(res, d_total, 16, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipMemcpyAsync(res + 2, kt.ent_used, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -1003,9 +884,9 @@ static int frame_decode_fused(fg_ctx* ctx, fg_format fmt, fg_framing framing, co
         const bool rows_short = total > cap, ents_short = used > ent_cap;
         if (!rows_short && !ents_short) break;
         if (rows_short) ctx->frames_per_byte = (double)(total + 1) / (double)nbytes;
-        if (attempt >= 2 || (ents_short && ent_cap >= 0xFFFFFFF0ull)) return FG_ERR_UNSUPPORTED;
+        if (attempt >= 2 || (ents_short && ent_cap >= kEntCapMax)) return FG_ERR_UNSUPPORTED;
         if (rows_short) cap = total + total / 16 + 1024;
-        if (ents_short) ent_cap = used + used / 8 + 1024;  // (rows beyond the old capacity had no entries yet: a third launch may follow)
+        if (ents_short) ent_cap = next_ent_cap(used);  // (rows beyond the old capacity had no entries yet: a third launch may follow)
     }
     if (total && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)total / (double)nbytes;
     *n_frames = total;
@@ -1084,49 +965,13 @@ int fg_udp_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64
     if (total) FG_HIP(ctx, hipMemcpyAsync(h_lines, ctx->d_sl_packed, total, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync(h_offs, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync(h_st, ctx->d_udp_st, n, hipMemcpyDeviceToHost, s));
-    // 3. decode the payloads where they lie (as the second half of frame_decode_one_piece)
-    uint64_t ent_cap = fmt == FG_RFC5424 ? total / 16 + 1024 : total / 8 + 1024;
-    for (;;) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t bytes_total = 0;
-        carve(nullptr, n, ent_cap, nullptr, &bytes_total);
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, bytes_total)) != FG_OK) return rc;
-        if (bytes_total > ctx->h_tab_cap) {
-            if (ctx->h_tab) FG_HIP(ctx, hipHostFree(ctx->h_tab));
-            ctx->h_tab = nullptr;
-            ctx->h_tab_cap = 0;
-            const uint64_t want = up(bytes_total + bytes_total / 4, 1 << 20);
-            FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
-            ctx->h_tab_cap = want;
-        }
-        fg_tables dt, ht;
-        carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
-        carve(ctx->h_tab, n, ent_cap, &ht, nullptr);
-        rc = fg_decode_frames_device(ctx, fmt, FG_FRAME_NONE, ctx->d_sl_packed, total, ctx->d_offsets, n, ctx->d_bad, &dt, FG_STREAM_OWN);
-        if (rc != FG_OK) return rc;
-        uint64_t used = 0;
-        FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        if (used > ent_cap) {
-            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
-            ent_cap = used + used / 8 + 1024;
-            continue;
-        }
-        uint64_t sizes[FG_TABLE_ARRAYS];
-        fg_tables_layout(n, used, sizes);
-        void* dsts[FG_TABLE_ARRAYS] = {ht.meta, ht.ts, ht.hostname, ht.appname, ht.procid, ht.msgid, ht.msg, ht.full_msg,
-                                       ht.ent_first, ht.ent_count, ht.ent_name, ht.ent_val, ht.ent_type, ht.ent_flags, ht.ent_used};
-        void* srcs[FG_TABLE_ARRAYS] = {dt.meta, dt.ts, dt.hostname, dt.appname, dt.procid, dt.msgid, dt.msg, dt.full_msg,
-                                       dt.ent_first, dt.ent_count, dt.ent_name, dt.ent_val, dt.ent_type, dt.ent_flags, dt.ent_used};
-        for (int k = 0; k < FG_TABLE_ARRAYS; ++k)
-            if (sizes[k]) FG_HIP(ctx, hipMemcpyAsync(dsts[k], srcs[k], sizes[k], hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        *out = ht;
-        *out_lines = h_lines;
-        *out_line_offsets = h_offs;
-        *udp_status = h_st;
-        return FG_OK;
-    }
+    // 3. decode the payloads where they lie (as the second half of frame_decode_one_piece; the entry table is sized from what the batch
+    //    inflated to)
+    if ((rc = decode_stage_to_host(ctx, fmt, FG_FRAME_NONE, total, n, ctx->d_bad, ctx->d_sl_packed, out)) != FG_OK) return rc;
+    *out_lines = h_lines;
+    *out_line_offsets = h_offs;
+    *udp_status = h_st;
+    return FG_OK;
 }
 
 int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, int final,
@@ -1201,13 +1046,9 @@ static int decode_stage(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t
     if (!d_src) d_src = ctx->d_bytes;
     hipStream_t s = ctx->stream;
     int rc;
-    uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    if (fmt == FG_RFC3164) ent_cap = 16;  // RFC3164 produces no entries
+    uint64_t ent_cap = first_ent_cap(fmt, nbytes);
     for (;;) {
-        if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-        uint64_t bytes_total = 0;
-        carve(nullptr, n, ent_cap, nullptr, &bytes_total);
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, bytes_total)) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, carved_bytes(n, ent_cap))) != FG_OK) return rc;
         carve(ctx->d_tab, n, ent_cap, dt, nullptr);
         rc = fg_decode_frames_device(ctx, fmt, framing, d_src, nbytes, ctx->d_offsets, n, d_bad, dt, FG_STREAM_OWN);
         if (rc != FG_OK) return rc;
@@ -1215,13 +1056,27 @@ static int decode_stage(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t
         FG_HIP(ctx, hipMemcpyAsync(&used, dt->ent_used, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         if (used > ent_cap) {
-            if (ent_cap >= 0xFFFFFFF0ull) return FG_ERR_ENT_OVERFLOW;
-            ent_cap = used + used / 8 + 1024;
+            if (ent_cap >= kEntCapMax) return FG_ERR_ENT_OVERFLOW;
+            ent_cap = next_ent_cap(used);
             continue;
         }
         *ent_used = used;
         return FG_OK;
     }
+}
+// ... and the whole table into the ctx's pinned mirror: *out (host pointers) is complete when the call returns
+static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t nbytes, uint64_t n, const uint8_t* d_bad,
+                                const uint8_t* d_src, fg_tables* out) {
+    int rc;
+    fg_tables dt, ht;
+    uint64_t used = 0;
+    if ((rc = decode_stage(ctx, fmt, framing, nbytes, n, d_bad, &dt, &used, d_src)) != FG_OK) return rc;
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tab, &ctx->h_tab_cap, carved_bytes(n, dt.ent_cap))) != FG_OK) return rc;
+    carve(ctx->h_tab, n, dt.ent_cap, &ht, nullptr);
+    if ((rc = copy_table(ctx, ht, dt, n, used, ctx->stream)) != FG_OK) return rc;
+    FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *out = ht;
+    return FG_OK;
 }
 
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB
@@ -1267,18 +1122,14 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     if ((rc = ensure_pipeline(ctx, slices * 2u)) != FG_OK) return rc;  // (four events per slice)
     const hipStream_t s_up = ctx->s_up, s_run = ctx->s_run, s_down = ctx->s_down, s_ahead = ctx->s_up;
     hipStream_t lanes[1] = {s_run};
-    if (!ctx->h_cnt) FG_HIP(ctx, hipHostMalloc((void**)&ctx->h_cnt, 65536, hipHostMallocDefault));
+    if ((rc = ensure_h_cnt(ctx)) != FG_OK) return rc;
     std::vector<hipEvent_t>& ev = ctx->ev_slice;  // [4k + 1] slice k is decoded and counted, [4k + 2] its messages are written
     TableShares shares(ctx, slices);
     // ---- device buffers: input, tables (whole batch), out_offsets / enc_status, encoder scratch ----
     if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 1) * 8)) != FG_OK) return rc;
-    uint64_t ent_cap = fmt == FG_RFC5424 ? nbytes / 16 + 1024 : nbytes / 8 + 1024;
-    if (fmt == FG_RFC3164) ent_cap = 16;
-    if (ent_cap > 0xFFFFFFF0ull) ent_cap = 0xFFFFFFF0ull;
-    uint64_t tab_bytes = 0;
-    carve(nullptr, n, ent_cap, nullptr, &tab_bytes);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, tab_bytes)) != FG_OK) return rc;
+    const uint64_t ent_cap = first_ent_cap(fmt, nbytes);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, carved_bytes(n, ent_cap))) != FG_OK) return rc;
     fg_tables dt{};
     carve(ctx->d_tab, n, ent_cap, &dt, nullptr);
     const uint64_t offs_bytes = up((n + 1) * 8, 256);
@@ -1309,19 +1160,8 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     // ---- host buffer: fixed-size arrays first, the messages behind them (they grow slice by slice) ----
     const uint64_t o_offs = 0, o_meta = o_offs + offs_bytes, o_st = o_meta + up(n * 4, 256), o_msgs = o_st + up(n, 256);
     uint64_t base = 0;  // encoded bytes of the slices finished so far
-    auto sl_tables = [&](uint64_t l0, uint64_t l1) {
-        fg_tables sl = dt;
-        sl.n = l1 - l0;
-        sl.meta += l0; sl.ts += l0; sl.hostname += l0; sl.appname += l0; sl.procid += l0; sl.msgid += l0; sl.msg += l0; sl.full_msg += l0;
-        sl.ent_first += l0; sl.ent_count += l0;
-        return sl;
-    };
+    auto sl_tables = [&](uint64_t l0, uint64_t l1) { return fg::rows_of(dt, l0, l1 - l0); };
     auto blocks_before = [&](uint32_t k) { return cut[k] / 64 + k; };  // first scratch sum of slice k (disjoint per slice)
-    auto drain = [&]() {
-        (void)hipStreamSynchronize(s_up);
-        (void)hipStreamSynchronize(s_run);
-        (void)hipStreamSynchronize(s_down);
-    };
     // queue a slice's upload, decode and count kernel (sixteen-byte aligned cuts: a slice starts with the sixteen bytes its first line begins in)
     auto enqueue = [&](uint32_t k) -> int {
         hipStream_t s = s_ahead;
@@ -1355,7 +1195,7 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     for (uint32_t k = 0; k < slices; ++k) {
         while (queued < slices && queued < k + 3u) {
             if ((rc = enqueue(queued)) != FG_OK) {
-                drain();
+                drain(ctx);
                 return rc;
             }
             ++queued;
@@ -1366,20 +1206,20 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
         const uint64_t l0 = cut[k], l1 = cut[k + 1], rows = l1 - l0;
         if (rows == 0) continue;
         if (hipStreamWaitEvent(s, ev[4 * k + 1], 0) != hipSuccess) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
         if (fg_launch_encode_scan(d_sizes + l0, d_block_sums + blocks_before(k), rows, d_out_offsets + l0, base, s) != 0) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
-        uint64_t* const h_end = ctx->h_cnt + 4096;
+        uint64_t* const h_end = ctx->h_cnt + kCntEnd;
         if (hipMemcpyAsync(h_end, d_out_offsets + l1, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipEventRecord(ctx->ev_ready, s) != hipSuccess) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
         if (hipEventSynchronize(ctx->ev_ready) != hipSuccess) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
         const uint64_t end = *h_end;
@@ -1388,19 +1228,19 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
             const uint64_t in0 = offsets[l1] - offsets[l0];
             const uint64_t est = (uint64_t)((double)end * ((double)nbytes / (double)(in0 ? in0 : 1)) * 1.12) + (4ull << 20);
             if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, est)) != FG_OK || (rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, o_msgs + est)) != FG_OK) {
-                drain();
+                drain(ctx);
                 return rc;
             }
         }
         if (end > ctx->d_tout_cap || o_msgs + end > ctx->h_tout_cap) {
-            drain();
+            drain(ctx);
             return FG_ERR_UNSUPPORTED;
         }
         const fg_tables sl = sl_tables(l0, l1);
         fg::DevTables sdt = to_dev(sl);
         sdt.ent_cap = ddt.ent_cap;
         if (fg_launch_encode_write(ctx->d_bytes, ctx->d_offsets + l0, rows, &sdt, &cfg, tile_cap, cfg_lds, d_out_offsets + l0, ctx->d_tout, d_sizes + l0, s) != 0) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
         uint8_t* hh = ctx->h_tout;
@@ -1414,7 +1254,7 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
         if (ok && end > base) ok = hipMemcpyAsync(hh + o_msgs + base, ctx->d_tout + base, end - base, hipMemcpyDeviceToHost, s_down) == hipSuccess;
         ok = ok && hipEventRecord(ev[4 * k + 3], s_down) == hipSuccess;
         if (!ok) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
         base = end;
@@ -1428,11 +1268,11 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
         ok = ok && hipMemcpyAsync(hh + o_meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s_down) == hipSuccess;
         ok = ok && hipMemcpyAsync(hh + o_st, d_enc_status, n, hipMemcpyDeviceToHost, s_down) == hipSuccess;
         if (!ok) {
-            drain();
+            drain(ctx);
             return FG_ERR_HIP;
         }
     }
-    drain();
+    drain(ctx);
     // an entry table that was too small shows up as FG_ST_OVERFLOW rows: the one-piece path sizes it exactly
     uint64_t used = 0;
     FG_HIP(ctx, hipMemcpy(&used, dt.ent_used, 8, hipMemcpyDeviceToHost));

@@ -338,6 +338,44 @@ def test_udp_decode_batch_end_to_end(oracle, fmt, pinned):
         d.close()
 
 
+def dense_ltsv_datagrams(n=30, pairs=100):
+    """LTSV lines of many short pairs (five bytes each), a third bare, a third zlib, a third gzip: more entries than one per eight
+    inflated bytes plus 1024, the entry table fg_udp_decode_batch starts with.  30 datagrams of 100 pairs are the fewest: 3000 entries
+    in 15 710 bytes (2987 slots to start with); 29 hold 2900 in 15 186 (2922 slots)"""
+    keys = [bytes([a, b]) for a in range(97, 123) for b in range(97, 123)]
+    lines = [b"time:%d\thost:h%d\t" % (1_600_000_000 + i, i) + b"\t".join(k + b":%d" % ((i + j) % 10) for j, k in enumerate(keys[i:i + pairs]))
+             for i in range(n)]
+    grams = [l if i % 3 == 0 else zlib.compress(l, 6) if i % 3 == 1 else gzip.compress(l, mtime=0) for i, l in enumerate(lines)]
+    return lines, grams
+
+
+def test_udp_decode_batch_grows_the_entry_table(oracle):
+    """a batch whose entries outnumber the first guess (inflated bytes / 8 + 1024): the decode is repeated with the table the counter
+    asked for, and every row and entry is the oracle's"""
+    from flowgger_amd.record import Record, parse_canonical
+
+    lines, grams = dense_ltsv_datagrams()
+    mblob, moffs = um.pack(lines)
+    oblob, ooffs = oracle.decode_batch(LTSV, np.concatenate([mblob, np.zeros(16, np.uint8)]), moffs, config=synth.LTSV_CONFIG)
+    recs = [parse_canonical(oblob[int(ooffs[i]):int(ooffs[i + 1])].tobytes()) for i in range(len(lines))]
+    assert all(isinstance(r, Record) for r in recs)
+    entries = sum(len(sd.pairs) for r in recs for sd in r.sd)
+    assert entries > int(mblob.size) // 8 + 1024, (entries, int(mblob.size))
+    d = LTSVDecoder(synth.LTSV_CONFIG)
+    try:
+        blob, offs = um.pack(grams)
+        tab, out_lines, line_offs, ust = d.udp_decode_packed(blob, offs)
+        st, kept, slots = um.expect(grams)
+        assert bool(kept.all()) and np.array_equal(ust, st) and slots == lines
+        assert int(tab.a["ent_count"][:len(lines)].sum()) == entries and not bool((tab.status[:len(lines)] == L.FG_ST_OVERFLOW).any())
+        gblob, goffs = tab.serialize(d.fmt, out_lines, line_offs, cfg=d._cfg)
+        for i in range(len(lines)):
+            a, b = gblob[int(goffs[i]):int(goffs[i + 1])].tobytes(), oblob[int(ooffs[i]):int(ooffs[i + 1])].tobytes()
+            assert a == b, f"row {i}: {lines[i]!r}\n  gpu    {a!r}\n  oracle {b!r}"
+    finally:
+        d.close()
+
+
 def test_decode_datagrams_returns_records_and_the_reference_errors(oracle):
     from flowgger_amd import DecodeError, Record
 

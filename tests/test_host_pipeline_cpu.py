@@ -17,7 +17,7 @@ ROOT = Path(__file__).resolve().parent.parent
 HERE = ROOT / "tests" / "native"
 LIB = HERE / "libhost_pipeline_fake.so"
 SRC = [HERE / "host_pipeline_fake.cpp", HERE / "fakehip/hip/hip_runtime.h"] + [ROOT / "flowgger_amd/csrc" / f for f in
-                                                                                ("fg_capi.cpp", "fg_host_pipeline.cpp", "fg_ctx.hpp", "fg_fused_plan.hpp", "fg_tile_cap.hpp", "fg_gather.cpp", "fg_materialize.cpp")] + [ROOT / "include/fg_hip.h"]
+                                                                                ("fg_capi.cpp", "fg_host_pipeline.cpp", "fg_ctx.hpp", "fg_table_cols.hpp", "fg_fused_plan.hpp", "fg_tile_cap.hpp", "fg_gather.cpp", "fg_materialize.cpp")] + [ROOT / "include/fg_hip.h"]
 u64, vp = C.c_uint64, C.c_void_p
 COLS = ["meta", "ts", "hostname", "appname", "procid", "msgid", "msg", "full_msg", "ent_count"]
 
@@ -263,6 +263,38 @@ def test_raw_stream_sliced_equals_one_piece(fake, final, dense):
     same_lines(a, b, an)
     assert (a["meta"][1234] & 0xFF) == 0xFD and int((a["meta"] & 0xFF == 0xFD).sum()) == 1
     assert a["used"] == int(a["ent_count"].sum()) == b["used"]
+
+
+def test_tables_layout_is_the_documented_one(fake):
+    sizes = (u64 * L.FG_TABLE_ARRAYS)()
+    assert fake.fg_tables_layout(3, 5, sizes) == 0
+    assert list(sizes) == [12, 24, 24, 24, 24, 24, 24, 24, 12, 12, 40, 40, 5, 5, 8]
+
+
+def test_raw_stream_one_piece_grows_the_entry_table(fake):
+    """the one-piece raw-stream form decodes through the stage fg_transcode_batch uses: a chunk with more entries than one per 16 bytes
+    is decoded again with the table its counter asked for, and comes back whole"""
+    rng = np.random.default_rng(11)
+    lines = corpus(3000, rng, 30, 40, 300)
+    raw = np.frombuffer(b"".join(ln + b"\n" for ln in lines), np.uint8).copy()
+    data, offsets = pack(lines)
+    want = device_reference(fake, data, offsets, raw.size // 4 + 1024)
+    assert want["used"] > raw.size // 16 + 1024
+    c = Ctx(fake)
+    lo = L.fg_launch_opts()
+    lo.flags = L.FG_LO_TRANSCODE_ONE_PIECE
+    assert fake.fg_set_launch_opts(c.h, C.byref(lo)) == 0
+    st, po, nf, cons = L.fg_tables(), vp(), u64(), u64()
+    pad = np.concatenate([raw, np.zeros(64, np.uint8)])
+    fake.fgf_launches(1)
+    assert fake.fg_frame_decode_batch(c.h, 0, 1, pad.ctypes.data, raw.size, 1, C.byref(st), C.byref(po), C.byref(nf), C.byref(cons)) == 0
+    n = int(nf.value)
+    assert n == len(lines) and int(cons.value) == raw.size and fake.fgf_launches(1) == 2
+    got = snapshot(st, n)
+    assert got["used"] == want["used"] and not (got["meta"] & 0xFF == 0xFE).any()
+    assert int(st.ent_cap) == got["used"] + got["used"] // 8 + 1024  # (include/fg_hip.h, fg_tables::ent_used: what the retry is sized with)
+    same_lines(got, want, n)
+    c.close()
 
 
 @pytest.mark.parametrize("one_piece", [False, True])
