@@ -96,6 +96,8 @@ FG_LO_RFC3164_REGROUP, FG_LO_RFC3164_NO_REGROUP = 32768, 65536
 FG_PATH_DECODE_ZERO_COPY, FG_PATH_DECODE_SLICED, FG_PATH_FRAME_FUSED, FG_PATH_FRAME_SLICED, FG_PATH_FRAME_ONE_PIECE = 1, 2, 3, 4, 5
 FG_PATH_FRAME_SYSLEN_DEVICE, FG_PATH_FRAME_SYSLEN_HOST = 6, 7
 FG_PATH_FRAME_CAPNP_DEVICE, FG_PATH_FRAME_CAPNP_HOST = 8, 9
+FG_PATH_FRAME_MULTI = 10
+FG_SLOT_FRAME, FG_SLOT_BAD_UTF8, FG_SLOT_CARRY = 0, 1, 2  # fg_slot_kind
 FG_LO_RESERVED = 0x40000000  # the library's own (fg_set_launch_opts clears it)
 
 
@@ -198,6 +200,9 @@ def lib() -> C.CDLL:
     L.fg_udp_unpack_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
     L.fg_udp_decode_batch.argtypes = [vp, C.c_int, vp, u64, vp, u64, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.fg_frame_decode_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, vp, u64, C.POINTER(fg_tables), u64, vp, vp]
+    L.fg_frame_multi_device.argtypes = [vp, C.c_int, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64), vp]
+    L.fg_frame_decode_multi_batch.argtypes = [vp, C.c_int, C.c_int, vp, u64, vp, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp),
+                                              C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

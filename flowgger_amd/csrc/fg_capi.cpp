@@ -243,6 +243,8 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_udp_off) (void)hipFree(ctx->d_udp_off);
     if (ctx->d_udp_st) (void)hipFree(ctx->d_udp_st);
     if (ctx->h_udp) (void)hipHostFree(ctx->h_udp);
+    if (ctx->d_ms) (void)hipFree(ctx->d_ms);
+    if (ctx->h_ms) (void)hipHostFree(ctx->h_ms);
     if (ctx->d_enc) (void)hipFree(ctx->d_enc);
     if (ctx->h_enc_ring) (void)hipHostFree(ctx->h_enc_ring);
     for (hipEvent_t e : ctx->ev_enc)
@@ -393,6 +395,46 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     FG_HIP(ctx, hipStreamSynchronize(s));
     *n_frames = last_end == nbytes ? total : total + 1;
     return FG_OK;
+}
+
+// replaces the per-connection `buf_reader.lines()` / `split(0)` + str::from_utf8 (tcp_input.rs:39-47, line_splitter.rs:17-25,
+// nul_splitter.rs:18-40) for the chunks of n_segs connections at once
+int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts,
+                          const uint8_t* d_seg_final, uint64_t n_segs, uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap_slots,
+                          uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint64_t* n_slots, void* stream) {
+    if (!ctx || !d_offsets || !n_slots || (cap_slots && !d_kind) || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (n_segs && (!d_seg_starts || !d_seg_first || !d_seg_consumed)) return FG_ERR_ARG;
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_ARG;
+    if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;
+    *n_slots = 0;
+    if (!fg_launch_frame_multi || !fg_frame_multi_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    if (nbytes == 0 || n_segs == 0) {  // no slots: every segment is empty
+        if (n_segs) {
+            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
+            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
+            FG_HIP(ctx, hipStreamSynchronize(s));
+        }
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
+    uint64_t res[2] = {0, 0};
+    for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : 0;; classic = 1) {
+        uint64_t* d_res = nullptr;
+        const int lrc = fg_launch_frame_multi(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, d_seg_starts, d_seg_final, n_segs, ctx->d_frame,
+                                              d_offsets, d_kind, cap_slots, d_seg_first, d_seg_consumed, &d_res, s, classic);
+        if (lrc != 0) {
+            ctx->last_hip = lrc;
+            return FG_ERR_HIP;
+        }
+        FG_HIP(ctx, hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        if (res[0] != FG_FRAME_ABORTED || classic == 1) break;  // (the one-pass scan gave up waiting on a tile: the classic form)
+    }
+    *n_slots = res[1];
+    return res[1] > cap_slots ? FG_ERR_ENT_OVERFLOW : FG_OK;
 }
 
 // replaces read_msglen + read_exact + String::from_utf8 of SyslenSplitter::run (splitter/syslen_splitter.rs:17-57) for a chunk

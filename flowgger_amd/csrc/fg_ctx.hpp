@@ -86,6 +86,13 @@ extern "C" int fg_launch_udp_write(const uint8_t* d_bytes, const uint64_t* d_off
                                    uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
 extern "C" int fg_launch_udp_finish(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
                                     uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
+// the segmented framer (fg_frame_multi.hip): *d_result = two device words, the delimiter count (FG_FRAME_ABORTED: launch again, classic)
+// and the slot count.  (WEAK references, as fg_launch_syslen above: without the kernels fg_frame_multi_device answers
+// FG_ERR_UNSUPPORTED.  The product library always has them: build.py checks the link.)
+extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t n_segs) __attribute__((weak));
+extern "C" int fg_launch_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, const uint64_t* d_seg_starts, const uint8_t* d_seg_final,
+                                     uint64_t n_segs, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first,
+                                     uint64_t* d_seg_consumed, uint64_t** d_result, hipStream_t stream, int classic) __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
@@ -182,6 +189,10 @@ struct fg_ctx {
     uint64_t d_udp_st_cap = 0;
     uint8_t* h_udp = nullptr;        // ... pinned: inflated lines | their offsets | fg_udp_status
     uint64_t h_udp_cap = 0;
+    uint8_t* d_ms = nullptr;         // fg_frame_decode_multi_batch: seg_starts | seg_first | seg_consumed | seg_final
+    uint64_t d_ms_cap = 0;
+    uint8_t* h_ms = nullptr;         // ... pinned: seg_first | seg_consumed | slot offsets | slot kinds
+    uint64_t h_ms_cap = 0;
     uint8_t* d_bad = nullptr;    // fg_frame_decode_batch: per-frame UTF-8 verdicts
     uint64_t d_bad_cap = 0;
     uint64_t* h_off = nullptr;   // fg_frame_decode_batch: pinned host copy of the frame offsets

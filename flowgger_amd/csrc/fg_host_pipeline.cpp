@@ -1079,6 +1079,81 @@ static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, 
     return FG_OK;
 }
 
+// The chunks of many connections in one buffer: upload, frame every segment as its own stream, decode every slot (CARRY and
+// BAD_UTF8 slots are skipped rows), tables and slot lists back.  One piece: a batch of connection chunks is far below the sizes
+// from which the sliced forms pay.
+extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
+                                           const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs, fg_tables* out,
+                                           const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
+                                           const uint64_t** out_seg_consumed, uint64_t* n_slots) {
+    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !n_slots || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_ARG;
+    if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF && fmt != FG_RFC3164) return FG_ERR_ARG;
+    if (n_segs && !seg_starts) return FG_ERR_ARG;
+    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
+    for (uint64_t k = 0; k < n_segs; ++k)
+        if (seg_starts[k] > seg_starts[k + 1]) return FG_ERR_ARG;
+    *n_slots = 0;
+    *out = fg_tables{};
+    *out_offsets = nullptr;
+    *out_kind = nullptr;
+    *out_seg_first = nullptr;
+    *out_seg_consumed = nullptr;
+    ctx->last_host_path = 0;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    // seg_starts | seg_first | seg_consumed | seg_final on the device; seg_first | seg_consumed | offsets | kinds in the pinned mirror
+    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_final = o_cons + up(n_segs * 8 + 8, 256);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_final + up(n_segs + 1, 256))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
+    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
+    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
+    uint8_t* const d_final = seg_final ? ctx->d_ms + o_final : nullptr;
+    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_segs && seg_final) FG_HIP(ctx, hipMemcpyAsync(d_final, seg_final, n_segs, hipMemcpyHostToDevice, s));
+    // 1. frame: capacity one slot per 32 bytes and one tail per segment to start with, exact on retry (as frame_stage)
+    uint64_t cap = nbytes / 32 + n_segs + 1024, n = 0;
+    for (;;) {
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return rc;
+        rc = fg_frame_multi_device(ctx, framing, ctx->d_bytes, nbytes, d_starts, d_final, n_segs, ctx->d_offsets, ctx->d_bad, cap, d_first, d_cons, &n,
+                                   FG_STREAM_OWN);
+        if (rc != FG_ERR_ENT_OVERFLOW) break;
+        cap = n + 16;
+    }
+    if (rc != FG_OK) return rc;
+    const uint64_t h_cons = o_first, h_off = h_cons + up(n_segs * 8 + 8, 256), h_kind = h_off + up((n + 1) * 8, 256);
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_kind + up(n + 1, 256))) != FG_OK) return rc;
+    uint8_t* const h = ctx->h_ms;
+    if (n_segs) {
+        FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
+    } else {
+        memset(h, 0, 8);
+    }
+    if (nbytes && n_segs) FG_HIP(ctx, hipMemcpyAsync(h + h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    else memset(h + h_off, 0, 8);
+    if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_kind, ctx->d_bad, n, hipMemcpyDeviceToHost, s));
+    *n_slots = n;
+    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
+    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
+    *out_offsets = reinterpret_cast<const uint64_t*>(h + h_off);
+    *out_kind = h + h_kind;
+    ctx->last_host_path = FG_PATH_FRAME_MULTI;
+    if (n == 0) {
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    // 2. decode the slots where they lie (terminators stripped in-kernel; a nonzero kind -> FG_ST_BAD_UTF8, not decoded)
+    rc = decode_stage_to_host(ctx, fmt, framing, nbytes, n, ctx->d_bad, ctx->d_bytes, out);
+    if (rc != FG_OK) ctx->last_host_path = 0;
+    return rc;
+}
+
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB
 // on the ctx's two streams, so that the upload of slice k+1 and the (2-3x larger) download of slice k's messages share the
 // full-duplex link, and the kernels hide behind both.  The host only waits for one small number per slice (its encoded size:

@@ -280,6 +280,58 @@ class Decoder:
         offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), (nf + 1,)).copy()
         return HostTables.from_struct(st), offsets, int(used.value)
 
+    # -- the chunks of many connections in one launch ------------------------------------------------------
+    def frame_multi_device(self, d_bytes, d_seg_starts, d_seg_final, framing: int, cap_slots: Optional[int] = None, stream=None):
+        """fg_frame_multi_device: d_bytes holds the chunks of K connections back to back (segment k =
+        d_bytes[seg_starts[k]:seg_starts[k + 1]], torch int64 / uint64 [K + 1]; d_seg_final uint8 [K] or None); every segment is
+        framed as a stream of its own (`buf_reader.lines()` / `split(0)` + `str::from_utf8` per connection, tcp_input.rs:39-47).
+        Returns (d_offsets, d_kind, n_slots, d_seg_first, d_seg_consumed): slot i = d_bytes[offsets[i]:offsets[i + 1]] including
+        its terminator, kind FG_SLOT_FRAME / _BAD_UTF8 / _CARRY; d_kind is decode_frames_device's d_bad as it is."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        nbytes, K = d_bytes.numel(), d_seg_starts.numel() - 1
+        cap = cap_slots if cap_slots is not None else nbytes // 16 + K + 16
+        d_first = torch.empty(K + 1, dtype=torch.int64, device=d_bytes.device)
+        d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=d_bytes.device)
+        while True:
+            d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=d_bytes.device)
+            d_kind = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_bytes.device)
+            n = C.c_uint64()
+            rc = L.lib().fg_frame_multi_device(self._ctx, framing, d_bytes.data_ptr(), nbytes, d_seg_starts.data_ptr(),
+                                               d_seg_final.data_ptr() if d_seg_final is not None else None, K, d_offsets.data_ptr(),
+                                               d_kind.data_ptr(), cap, d_first.data_ptr(), d_cons.data_ptr(), C.byref(n),
+                                               C.c_void_p(stream.cuda_stream))
+            if rc == L.FG_ERR_ENT_OVERFLOW and cap_slots is None:
+                cap = int(n.value)
+                continue
+            L.check(rc, "fg_frame_multi_device")
+            return d_offsets, d_kind, int(n.value), d_first, d_cons[:K]
+
+    def frame_decode_multi(self, raw: Union[bytes, np.ndarray], seg_starts, seg_final, framing: int):
+        """fg_frame_decode_multi_batch: the chunks of K connections back to back in, tables out.  Returns (HostTables or None, offsets
+        uint64[n + 1], kind uint8[n], seg_first uint64[K + 1], seg_consumed uint64[K]); rows of FG_SLOT_BAD_UTF8 and FG_SLOT_CARRY slots
+        have status FG_ST_BAD_UTF8."""
+        buf = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, np.uint8)
+        starts = np.ascontiguousarray(seg_starts, np.uint64)
+        K = len(starts) - 1
+        final = None if seg_final is None else np.ascontiguousarray(seg_final, np.uint8)
+        st = L.fg_tables()
+        off, kind, first, cons = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = C.c_uint64()
+        L.check(L.lib().fg_frame_decode_multi_batch(self._ctx, self.fmt, framing, buf.ctypes.data if buf.size else None, buf.size,
+                                                    starts.ctypes.data, final.ctypes.data if final is not None and K else None, K,
+                                                    C.byref(st), C.byref(off), C.byref(kind), C.byref(first), C.byref(cons), C.byref(n)),
+                "fg_frame_decode_multi_batch")
+        ns = int(n.value)
+        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+        offsets = np.ctypeslib.as_array(C.cast(off, u64p), (ns + 1,)).copy()
+        kinds = np.ctypeslib.as_array(C.cast(kind, u8p), (ns,)).copy() if ns else np.zeros(0, np.uint8)
+        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
+        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
+        return (HostTables.from_struct(st) if ns else None), offsets, kinds, seg_first, seg_cons
+
     # -- the UDP input (input/udp_input.rs:100-143) -------------------------------------------------------
     def udp_decode_packed(self, data: np.ndarray, offsets: np.ndarray, max_inflated: Optional[int] = None):
         """Datagrams back to back in, tables out (fg_udp_decode_batch: upload, inflate / copy + UTF-8 on the GPU, decode).  Returns
@@ -387,6 +439,112 @@ class UdpUnpacker:
         d_out = torch.zeros((cap + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
         L.check(L.lib().fg_udp_unpack_device(*args, d_out.data_ptr(), cap, *tail), "fg_udp_unpack_device")
         return d_out[:cap], d_off, d_drop[:n], d_st[:n]
+
+
+class FlushPolicy:
+    """When a batching framer hands what it holds to the GPU (the fields of the C++ fg::FlushPolicy that make sense before the lines
+    are counted): max_bytes -- a batch never grows beyond this; max_latency_ms -- how long the first chunk of a batch may wait for
+    company."""
+
+    def __init__(self, max_bytes: int = 8 << 20, max_latency_ms: float = 5.0):
+        self.max_bytes, self.max_latency_ms = max_bytes, max_latency_ms
+
+
+_RUST_WS = "\t\n\x0b\x0c\r \x85\xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a\u2028\u2029\u202f\u205f\u3000"
+
+
+class MultiStreamSplitter:
+    """The stream-side sibling of the UDP batcher: parks the chunks of MANY connections and hands them to the GPU together -- one
+    fg_frame_decode_multi_batch call frames every connection's bytes as its own stream and decodes the frames.  Per connection the
+    output is what LineSplitter::run / NulSplitter::run (splitter/line_splitter.rs:17-54, nul_splitter.rs:18-60) produce for the bytes
+    pushed so far: a Record per decoded line, or a DecodeError whose text is the reference's stderr line -- "Invalid UTF-8 input", or
+    "<decoder's error>: [<trimmed line>]" (NUL framing prints nothing for a frame that trims to nothing, nul_splitter.rs:41-46).
+    The unterminated tail of a connection's chunk is carried over and prepended to its next one; close(conn) is its EOF."""
+
+    def __init__(self, decoder: Decoder, framing: int, policy: Optional[FlushPolicy] = None):
+        if framing not in (L.FG_FRAME_LINE, L.FG_FRAME_NUL):
+            raise ValueError("MultiStreamSplitter frames FG_FRAME_LINE or FG_FRAME_NUL streams")
+        self.decoder, self.framing, self.policy = decoder, framing, policy or FlushPolicy()
+        self._carry: dict = {}     # conn -> bytes carried over from its last flushed chunk
+        self._pending: dict = {}   # conn -> chunks pushed since the last flush (insertion order = arrival order)
+        self._closed: set = set()
+        self._bytes = 0
+        self._first_at: Optional[float] = None
+
+    def push(self, conn_id, chunk: bytes) -> list:
+        """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
+        import time
+
+        if conn_id in self._closed:
+            raise ValueError("push after close")
+        if chunk:
+            self._pending.setdefault(conn_id, []).append(bytes(chunk))
+            self._bytes += len(chunk)
+            if self._first_at is None:
+                self._first_at = time.monotonic()
+        due = self._bytes >= self.policy.max_bytes or (
+            self._first_at is not None and (time.monotonic() - self._first_at) * 1e3 >= self.policy.max_latency_ms)
+        return self.flush() if due else []
+
+    def close(self, conn_id) -> None:
+        """the connection's EOF: its unterminated tail is a frame at the next flush"""
+        self._closed.add(conn_id)
+        self._pending.setdefault(conn_id, [])
+
+    def pending_bytes(self) -> int:
+        return self._bytes
+
+    def flush(self) -> list:
+        """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
+        conns = list(self._pending)
+        segs = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
+        final = [1 if c in self._closed else 0 for c in conns]
+        self._pending, self._bytes, self._first_at = {}, 0, None
+        for c in conns:
+            self._closed.discard(c)
+        if not conns:
+            return []
+        raw = b"".join(segs)
+        starts = np.zeros(len(segs) + 1, np.uint64)
+        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
+        tab, offsets, kind, first, _ = self.decoder.frame_decode_multi(raw, starts, final, self.framing)
+        fmt, out = self.decoder.fmt, []
+        can, coffs = b"", None
+        if tab is not None:
+            data = np.frombuffer(raw + b"\0" * 32, np.uint8)
+            if fmt == L.FG_LTSV and bool(((tab.a["meta"][:tab.n] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
+                import sys
+
+                from .tables import tables_stdout
+
+                text = tables_stdout(tab, fmt, data, offsets, self.framing)  # (the decoder's stdout side effect, ltsv_decoder.rs:99)
+                if text:
+                    sys.stdout.write(text.decode("utf-8", "replace"))
+            blob, coffs = tab.serialize(fmt, data, offsets, cfg=self.decoder._cfg)
+            can = blob.tobytes()
+        for k, c in enumerate(conns):
+            res: list = []
+            for i in range(int(first[k]), int(first[k + 1])):
+                a, b = int(offsets[i]), int(offsets[i + 1])
+                if kind[i] == L.FG_SLOT_CARRY:
+                    self._carry[c] = raw[a:b]
+                elif kind[i] == L.FG_SLOT_BAD_UTF8:
+                    res.append(DecodeError("Invalid UTF-8 input"))
+                else:
+                    r = parse_canonical(can[int(coffs[i]):int(coffs[i + 1])])
+                    if isinstance(r, DecodeError):
+                        line = raw[a:b]
+                        if self.framing == L.FG_FRAME_LINE:
+                            line = line[:-2] if line.endswith(b"\r\n") else line[:-1] if line.endswith(b"\n") else line
+                        elif line.endswith(b"\0"):
+                            line = line[:-1]
+                        text = line.decode("utf-8").strip(_RUST_WS)
+                        if self.framing == L.FG_FRAME_NUL and not text:
+                            continue
+                        r = DecodeError(f"{r}: [{text}]")
+                    res.append(r)
+            out.append((c, res))
+        return out
 
 
 class RFC5424Decoder(Decoder):

@@ -337,6 +337,40 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
                     uint64_t* d_offsets, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames,
                     void* stream);
 
+/* GPU FRAMING OF THE CHUNKS OF MANY CONNECTIONS IN ONE LAUNCH (additive under the same FG_ABI_VERSION).  The reference gives every
+ * connection its own splitter (input/tcp/tcp_input.rs:39-47) whose `buf_reader.lines()` / `buf_reader.split(0)` frames that
+ * connection's stream alone (splitter/line_splitter.rs:17-54, nul_splitter.rs:18-60); this call replaces that for K connections at once.
+ *   d_bytes        the chunks back to back (device), 16-byte aligned, readable up to nbytes rounded up to 16
+ *   d_seg_starts   n_segs + 1 entries (device): segment k = bytes[seg_starts[k] .. seg_starts[k + 1]).  The segments tile the
+ *                  buffer: seg_starts[0] == 0, seg_starts[n_segs] == nbytes, non-decreasing; empty segments are allowed and a start
+ *                  needs NO alignment.  A list that does not tile is clamped (each value into [its predecessor, nbytes], the first
+ *                  to 0, the last to nbytes): the results are then those of the clamped list, and memory safety never depends on it.
+ *   d_seg_final    n_segs bytes (device) or NULL = all zero: nonzero = connection k ended with this chunk
+ *   framing        FG_FRAME_LINE or FG_FRAME_NUL (FG_ERR_ARG otherwise: FG_FRAME_SYSLEN / FG_FRAME_CAPNP keep their own entry points)
+ * Every segment is framed as if it were the whole stream.  The output is a list of SLOTS that tile the buffer, in buffer order:
+ *   d_offsets      out, cap_slots + 1 entries: slot i = [offsets[i], offsets[i + 1]), terminator included.  A nonempty segment has
+ *                  one slot per delimiter in it and one more when its last byte is no delimiter (its tail); an empty one has none
+ *   d_kind         out, cap_slots bytes, an fg_slot_kind per slot:
+ *                  FG_SLOT_FRAME     a frame, valid UTF-8
+ *                  FG_SLOT_BAD_UTF8  a frame whose bytes are not valid UTF-8 BY THEMSELVES (str::from_utf8 of exactly those bytes):
+ *                                    a neighbouring segment's bytes never make a slot valid or invalid; a sequence cut off by the end
+ *                                    of a final segment is invalid in its tail; a continuation byte that opens a segment is stray
+ *                  FG_SLOT_CARRY     the unterminated tail of a segment that is NOT final: no frame, no UTF-8 verdict -- the caller
+ *                                    carries those bytes over to the connection's next chunk.  (A final segment's tail is a frame.)
+ *                  d_kind is what fg_decode_frames_device takes as d_bad_utf8, unchanged: nonzero = not decoded, FG_ST_BAD_UTF8 --
+ *                  a CARRY slot costs one skipped row, at most one per segment
+ *   d_seg_first    out, n_segs + 1 entries: the slots of segment k are [seg_first[k], seg_first[k + 1]); seg_first[n_segs] = *n_slots
+ *   d_seg_consumed out, n_segs entries: the bytes of segment k that its frames cover (its length less its CARRY tail)
+ *   n_slots        out (host); the call synchronises the stream to read it
+ * With n_segs == 1 and seg_final[0] != 0 the slots, offsets and flags are those of fg_frame_device on the same bytes.
+ * Returns FG_ERR_ENT_OVERFLOW when cap_slots is too small (*n_slots holds the need; nothing beyond the capacity is written and the
+ * per-segment outputs are not).  Honours FG_LO_FRAME_CLASSIC. */
+typedef enum fg_slot_kind { FG_SLOT_FRAME = 0, FG_SLOT_BAD_UTF8 = 1, FG_SLOT_CARRY = 2 } fg_slot_kind;
+int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
+                          const uint64_t* d_seg_starts, const uint8_t* d_seg_final, uint64_t n_segs,
+                          uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap_slots,
+                          uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint64_t* n_slots, void* stream);
+
 /* Decode frames as produced by fg_frame_device: the kernels strip the terminators themselves, and
  * frames flagged in d_bad_utf8 (may be NULL) get status FG_ST_BAD_UTF8 instead of a decode.
  * fg_decode_batch_device(...) == fg_decode_frames_device(..., FG_FRAME_NONE, ..., NULL, ...).
@@ -497,6 +531,22 @@ int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
                           uint64_t nbytes, int final, fg_tables* out, const uint64_t** out_offsets,
                           uint64_t* n_frames, uint64_t* consumed);
 
+/* HOST-BUFFER decode of the chunks of MANY connections: one call uploads the buffer, frames every segment as its own stream
+ * (fg_frame_multi_device, whose contract this shares: segments, slots, kinds) and decodes every slot -- the stream-side sibling of
+ * fg_udp_decode_batch.  fmt: FG_RFC5424, FG_LTSV, FG_GELF or FG_RFC3164 (FG_CAPNP: FG_ERR_ARG); framing: FG_FRAME_LINE or FG_FRAME_NUL
+ * (FG_ERR_ARG otherwise).  Here the tiling of seg_starts IS checked (FG_ERR_ARG).  seg_final may be NULL (= all zero).
+ *   out               tables in ctx-owned pinned host memory, *n_slots rows; FG_SLOT_BAD_UTF8 and FG_SLOT_CARRY rows have status
+ *                     FG_ST_BAD_UTF8, (*out_kind)[i] tells them apart; spans are relative to (*out_offsets)[i]
+ *   out_offsets       *n_slots + 1 entries;  out_kind: *n_slots bytes
+ *   out_seg_first     n_segs + 1 entries;    out_seg_consumed: n_segs entries
+ * Everything returned is ctx-owned and stays valid until the next call on this ctx.  fg_last_host_path says FG_PATH_FRAME_MULTI.
+ * From which chunk size on a call per connection is as good has not been measured yet (tools/probe/multi_stream.py is the probe).
+ * Out of scope here: slicing over streams, the zero-copy fused launch, fg_transcode_batch for segmented input. */
+int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
+                                const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs,
+                                fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
+                                const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, uint64_t* n_slots);
+
 /* HOST-BUFFER UDP decode: upload the datagrams, fg_udp_unpack_device, decode -- the whole of handle_record_maybe_compressed for a
  * batch.  `bytes` / `offsets` pinned or pageable.  `out`: tables in ctx-owned pinned host memory, n rows; a dropped datagram has
  * status FG_ST_BAD_UTF8 and (*udp_status)[i] says why.  *out_lines / *out_line_offsets (n + 1 entries): the payloads as decoded, in
@@ -518,7 +568,8 @@ enum {
     FG_PATH_FRAME_SYSLEN_DEVICE = 6, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_SYSLEN: framed + packed by the device */
     FG_PATH_FRAME_SYSLEN_HOST = 7, /* ... the device framer declined the chunk: the prefixes were hopped on the host */
     FG_PATH_FRAME_CAPNP_DEVICE = 8, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_CAPNP: framed by the device where the chunk lies */
-    FG_PATH_FRAME_CAPNP_HOST = 9   /* ... the device framer declined the chunk: the segment tables were walked on the host */
+    FG_PATH_FRAME_CAPNP_HOST = 9,  /* ... the device framer declined the chunk: the segment tables were walked on the host */
+    FG_PATH_FRAME_MULTI = 10       /* fg_frame_decode_multi_batch: upload, segmented framing, decode */
 };
 int fg_last_host_path(const fg_ctx* ctx);
 /* How the chain of segment tables of the last FG_FRAME_CAPNP call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an
