@@ -81,7 +81,7 @@ def _depfile_deps(depfile: Path) -> list[Path] | None:
 
 
 # the object(s) whose kernel a bench workload times.  The launch geometry of the streaming decoders lives in their own sources
-# (fg_pipeline.hpp plan_launch); the RFC3164 decoder's and the encoders' tile is picked by fg_tile_cap.hpp.  The host side of the C ABI
+# (fg_plan_policy.hpp launch_geometry, fg_pipeline.hpp plan_launch); the RFC3164 decoder's and the encoders' tile is picked by fg_tile_cap.hpp.  The host side of the C ABI
 # (fg_capi.cpp: contexts, argument checks; fg_host_pipeline.cpp: copies, streams, events) is NOT part of a kernel's identity any
 # more (host-side edits disowned every measured HBM-traffic figure).
 WORKLOAD_UNITS = {

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fg_cus.hpp"
+
 namespace fg {
 
 constexpr int kCalibThreads = 256;
@@ -73,9 +75,8 @@ __global__ __launch_bounds__(kCalibThreads) void k_calib_read(const uint4* __res
 extern "C" int fg_launch_calib(int mode, const uint8_t* d_src, uint8_t* d_dst, uint64_t nbytes, uint32_t* d_sink, hipStream_t stream) {
     const uint64_t n16 = nbytes / 16;
     if (n16 == 0) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        return -1;
+    const int cus = fg::device_cus();
+    if (cus < 1) return -1;
     uint64_t blocks = (uint64_t)cus * 8u;  // 2048 threads per CU: every wave slot
     const uint64_t need = (n16 + fg::kCalibThreads - 1) / fg::kCalibThreads;
     if (blocks > need) blocks = need;

@@ -88,6 +88,46 @@ int upload_ltsv_cfg(fg_ctx* ctx) {
     return FG_OK;
 }
 
+// What every decode launch of a ctx needs on the device, allocated by the first: the per-wave entry stash (8 waves on every CU) and
+// the ring of hand-over words.
+int ensure_launch_state(fg_ctx* ctx) {
+    if (!ctx->d_stash) {
+        const int cus = fg::device_cus();  // (the DeviceGuard of the call has selected ctx->device)
+        if (cus < 1) {
+            ctx->last_hip = (int)hipErrorInvalidValue;
+            return FG_ERR_HIP;
+        }
+        const uint32_t blocks = 8u * (uint32_t)cus;
+        FG_HIP(ctx, hipMalloc((void**)&ctx->d_stash, fg_stash_bytes(blocks)));
+        ctx->stash_blocks = blocks;
+    }
+    if (!ctx->d_pending) {
+        FG_HIP(ctx, hipMalloc((void**)&ctx->d_pending, fg_ctx::kPendingRing * sizeof(uint32_t)));
+        FG_HIP(ctx, hipMemset(ctx->d_pending, 0, fg_ctx::kPendingRing * sizeof(uint32_t)));
+    }
+    return FG_OK;
+}
+// the ctx's launch counter (0 = the pending ring's initial content: never a valid epoch) and the hand-over word of an epoch
+uint32_t next_epoch(fg_ctx* ctx) {
+    ctx->epoch += 1u;
+    if (ctx->epoch == 0u) ctx->epoch = 1u;
+    return ctx->epoch;
+}
+uint32_t* pending_word(const fg_ctx* ctx, uint32_t epoch) { return ctx->d_pending + (epoch % fg_ctx::kPendingRing); }
+
+// the HIP-event bracket around the kernels of a call (fg_set_timing / fg_last_kernel_ms); end() only where every launch went out
+int timing_begin(fg_ctx* ctx, hipStream_t s) {
+    if (ctx->timing) FG_HIP(ctx, hipEventRecord(ctx->ev0, s));
+    return FG_OK;
+}
+int timing_end(fg_ctx* ctx, hipStream_t s) {
+    if (ctx->timing) {
+        FG_HIP(ctx, hipEventRecord(ctx->ev1, s));
+        ctx->ev_valid = true;
+    }
+    return FG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,12 +356,8 @@ int fg_calibrate_device(fg_ctx* ctx, int mode, const uint8_t* d_src, uint8_t* d_
     if ((((uintptr_t)d_src) | ((uintptr_t)d_dst)) & 15u) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
     if (!ctx->d_sink) FG_HIP(ctx, hipMalloc((void**)&ctx->d_sink, 256));
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
-    const int rc = fg_launch_calib(mode, d_src, d_dst, nbytes, ctx->d_sink, s);
-    if (rc != 0) {
-        ctx->last_hip = rc;
-        return FG_ERR_HIP;
-    }
+    hipStream_t s = stream_of(ctx, stream);
+    FG_LAUNCH(ctx, fg_launch_calib(mode, d_src, d_dst, nbytes, ctx->d_sink, s));
     return FG_OK;
 }
 
@@ -344,15 +380,11 @@ int fg_merge_tables_device(fg_ctx* ctx, const fg_tables* parts, uint32_t g, cons
     }
     if (out->n != rows || out->ent_cap < cap || cap > 0xFFFFFFFFull) return FG_ERR_ARG;
     DeviceGuard gd(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     (void)max_cap;
     int grc;
     if ((grc = grow_dev(ctx, (void**)&ctx->d_merge, &ctx->d_merge_cap, fg_merge_scratch_bytes(rows))) != FG_OK) return grc;
-    const int rc = fg_launch_merge_device(parts, g, d_index, out, d_src_part, max_rows, ctx->d_merge, s);
-    if (rc != 0) {
-        ctx->last_hip = rc;
-        return FG_ERR_HIP;
-    }
+    FG_LAUNCH(ctx, fg_launch_merge_device(parts, g, d_index, out, d_src_part, max_rows, ctx->d_merge, s));
     return FG_OK;
 }
 
@@ -367,7 +399,7 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_UNSUPPORTED;
     if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     *n_frames = 0;
     if (nbytes == 0) return FG_OK;
     int rc;
@@ -375,12 +407,8 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     uint64_t total = 0;
     for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0;; classic = 1) {
         uint64_t* d_total = nullptr;
-        int lrc = fg_launch_frame(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, ctx->d_frame, d_offsets, d_bad_utf8,
-                                  cap_frames, &d_total, s, classic);
-        if (lrc != 0) {
-            ctx->last_hip = lrc;
-            return FG_ERR_HIP;
-        }
+        FG_LAUNCH(ctx, fg_launch_frame(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, ctx->d_frame, d_offsets, d_bad_utf8,
+                                  cap_frames, &d_total, s, classic));
         // frames = delimiters (+1 when the stream does not end with one)
         FG_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -409,7 +437,7 @@ int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_byte
     *n_slots = 0;
     if (!fg_launch_frame_multi || !fg_frame_multi_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     if (nbytes == 0 || n_segs == 0) {  // no slots: every segment is empty
         if (n_segs) {
             FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
@@ -423,12 +451,8 @@ int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_byte
     uint64_t res[2] = {0, 0};
     for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : 0;; classic = 1) {
         uint64_t* d_res = nullptr;
-        const int lrc = fg_launch_frame_multi(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, d_seg_starts, d_seg_final, n_segs, ctx->d_frame,
-                                              d_offsets, d_kind, cap_slots, d_seg_first, d_seg_consumed, &d_res, s, classic);
-        if (lrc != 0) {
-            ctx->last_hip = lrc;
-            return FG_ERR_HIP;
-        }
+        FG_LAUNCH(ctx, fg_launch_frame_multi(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, d_seg_starts, d_seg_final, n_segs, ctx->d_frame,
+                                              d_offsets, d_kind, cap_slots, d_seg_first, d_seg_consumed, &d_res, s, classic));
         FG_HIP(ctx, hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         if (res[0] != FG_FRAME_ABORTED || classic == 1) break;  // (the one-pass scan gave up waiting on a tile: the classic form)
@@ -451,15 +475,11 @@ int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
     if (!fg_launch_syslen || !fg_syslen_max_bytes || !fg_syslen_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     if (nbytes > fg_syslen_max_bytes()) return FG_ERR_UNSUPPORTED;  // (the scratch keeps positions as 32-bit words)
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_syslen_scratch_bytes(nbytes))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
-    const int lrc = fg_launch_syslen(d_bytes, nbytes, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8, cap_frames, &d_hdr, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
+    FG_LAUNCH(ctx, fg_launch_syslen(d_bytes, nbytes, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8, cap_frames, &d_hdr, s));
     uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
@@ -485,15 +505,11 @@ int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, 
     if (!fg_launch_capnp_frame || !fg_capnp_frame_max_bytes || !fg_capnp_frame_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     if (nbytes > fg_capnp_frame_max_bytes()) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_capnp_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
-    const int lrc = fg_launch_capnp_frame(d_bytes, nbytes, ctx->d_frame, d_offsets, cap_frames, &d_hdr, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
+    FG_LAUNCH(ctx, fg_launch_capnp_frame(d_bytes, nbytes, ctx->d_frame, d_offsets, cap_frames, &d_hdr, s));
     uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
@@ -529,7 +545,7 @@ int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, c
     *total = 0;
     if (!fg_launch_udp_count || !fg_launch_udp_write || !fg_launch_udp_finish) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     if (n == 0) {
         FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -542,20 +558,14 @@ int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, c
     uint64_t* d_sums = (uint64_t*)(ctx->d_udp + sizes_bytes);
     int lrc = fg_launch_udp_count(d_bytes, d_offsets, n, (uint32_t)max_inflated, d_sizes, d_sums, d_udp_status, d_drop, s);
     if (lrc == 0) lrc = fg_launch_encode_scan(d_sizes, d_sums, n, d_out_offsets, 0ull, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
+    FG_LAUNCH(ctx, lrc);
     FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
     if (!d_out) return FG_OK;  // the sizing call
     if (*total > out_cap) return FG_ERR_ENT_OVERFLOW;
     lrc = fg_launch_udp_write(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
     if (lrc == 0) lrc = fg_launch_udp_finish(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
+    FG_LAUNCH(ctx, lrc);
     FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
 }
@@ -581,45 +591,29 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
     if (tables->n < n) return FG_ERR_ARG;
     if (tables->ent_cap > 0xFFFFFFFFull) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     fg::DevTables dt = to_dev(*tables);
     if (dt.ent_used && reset_counter) FG_HIP(ctx, hipMemsetAsync(dt.ent_used, 0, 8, s));
     if (n == 0) return FG_OK;
-    if (!ctx->d_stash) {
-        hipDeviceProp_t prop;
-        FG_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        uint32_t blocks = 8u * (uint32_t)prop.multiProcessorCount;
-        FG_HIP(ctx, hipMalloc((void**)&ctx->d_stash, fg_stash_bytes(blocks)));
-        ctx->stash_blocks = blocks;
-    }
+    int rc;
+    if ((rc = ensure_launch_state(ctx)) != FG_OK) return rc;
     uint64_t* stash = ctx->d_stash;
     if (lane) {  // a second launch that may be in flight at the same time (fg_transcode_batch's second lane)
         if (!ctx->d_stash2) FG_HIP(ctx, hipMalloc((void**)&ctx->d_stash2, fg_stash_bytes(ctx->stash_blocks)));
         stash = ctx->d_stash2;
-    }
-    constexpr uint32_t kPendingRing = 1024;
-    if (!ctx->d_pending) {
-        FG_HIP(ctx, hipMalloc((void**)&ctx->d_pending, kPendingRing * sizeof(uint32_t)));
-        FG_HIP(ctx, hipMemset(ctx->d_pending, 0, kPendingRing * sizeof(uint32_t)));
     }
     dt.shares = ctx->table_shares ? ctx->table_shares : 1u;
     fg_launch_opts lo_call = ctx->lo;
     if (ctx->link_bound_waves && lo_call.waves_per_cu == 0) lo_call.waves_per_cu = ctx->link_bound_waves;
     if (ctx->defer_general && fmt == FG_GELF) {
         // the slices of one batch: one hand-over word for all of them, the exact form once behind the last (fg_finish_deferred_general)
-        if (!ctx->batch_epoch) {
-            ctx->epoch += 1u;
-            if (ctx->epoch == 0u) ctx->epoch = 1u;
-            ctx->batch_epoch = ctx->epoch;
-        }
+        if (!ctx->batch_epoch) ctx->batch_epoch = next_epoch(ctx);
         dt.epoch = ctx->batch_epoch;
         lo_call.flags |= (uint32_t)FG_LO_RESERVED;
     } else {
-        ctx->epoch += 1u;
-        if (ctx->epoch == 0u) ctx->epoch = 1u;  // (0 = the ring's initial content: never a valid epoch)
-        dt.epoch = ctx->epoch;
+        dt.epoch = next_epoch(ctx);
     }
-    dt.pending = ctx->d_pending + (dt.epoch % kPendingRing);
+    dt.pending = pending_word(ctx, dt.epoch);
     // the launch's ticket counter (dynamic chunk dispatch, fg_pipeline.hpp): one word of a ring per LAUNCH -- the slices of a batch may be
     // in flight on two streams at once and must not draw from one counter -- never reset: the host knows what every launch adds
     constexpr uint32_t kTicketRing = 1024;
@@ -631,8 +625,7 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
     const uint32_t tslot = ctx->ticket_seq++ % kTicketRing;
     fg::TicketSlot tk_slot{ctx->d_ticket + tslot, &ctx->h_ticket[tslot]};
     fg::TicketSlot* const tk = (ctx->lo.flags & FG_LO_STATIC_CHUNKS) ? nullptr : &tk_slot;
-    if (ctx->timing) FG_HIP(ctx, hipEventRecord(ctx->ev0, s));
-    int rc;
+    if ((rc = timing_begin(ctx, s)) != FG_OK) return rc;
     const uint64_t avg_len = (span_bytes + n - 1) / n;
     switch (fmt) {
         case FG_RFC5424:
@@ -678,11 +671,7 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
         ctx->last_hip = rc;
         return FG_ERR_HIP;
     }
-    if (ctx->timing) {
-        FG_HIP(ctx, hipEventRecord(ctx->ev1, s));
-        ctx->ev_valid = true;
-    }
-    return FG_OK;
+    return timing_end(ctx, s);
 }
 
 
@@ -711,29 +700,16 @@ int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const u
     const fg::FusedGeom g = fg::fused_geometry(fmt, avg_line, lo_call, ctx->link_bound_waves != 0);
     if (!g.ok) return FG_ERR_UNSUPPORTED;
     DeviceGuard guard(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_fused, &ctx->d_fused_cap, fg::fused_scratch_bytes(nbytes, g.S))) != FG_OK) return rc;
     fg::DevTables dt = to_dev(*tables);
     if (dt.ent_used) FG_HIP(ctx, hipMemsetAsync(dt.ent_used, 0, 8, s));
-    if (!ctx->d_stash) {
-        hipDeviceProp_t prop;
-        FG_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        uint32_t blocks = 8u * (uint32_t)prop.multiProcessorCount;
-        FG_HIP(ctx, hipMalloc((void**)&ctx->d_stash, fg_stash_bytes(blocks)));
-        ctx->stash_blocks = blocks;
-    }
-    constexpr uint32_t kPendingRing = 1024;
-    if (!ctx->d_pending) {
-        FG_HIP(ctx, hipMalloc((void**)&ctx->d_pending, kPendingRing * sizeof(uint32_t)));
-        FG_HIP(ctx, hipMemset(ctx->d_pending, 0, kPendingRing * sizeof(uint32_t)));
-    }
-    ctx->epoch += 1u;
-    if (ctx->epoch == 0u) ctx->epoch = 1u;
-    dt.epoch = ctx->epoch;
-    dt.pending = ctx->d_pending + (dt.epoch % kPendingRing);
+    if ((rc = ensure_launch_state(ctx)) != FG_OK) return rc;
+    dt.epoch = next_epoch(ctx);
+    dt.pending = pending_word(ctx, dt.epoch);
     dt.n = cap;
-    if (ctx->timing) FG_HIP(ctx, hipEventRecord(ctx->ev0, s));
+    if ((rc = timing_begin(ctx, s)) != FG_OK) return rc;
     int lrc;
     switch (fmt) {
         case FG_RFC5424:
@@ -750,15 +726,8 @@ int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const u
             if (lrc == 0) lrc = fg_launch_gelf_general_dev(d_bytes, d_offsets, cap, &dt, s, (uint32_t)framing, nullptr, *d_total);
             break;
     }
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
-    if (ctx->timing) {
-        FG_HIP(ctx, hipEventRecord(ctx->ev1, s));
-        ctx->ev_valid = true;
-    }
-    return FG_OK;
+    FG_LAUNCH(ctx, lrc);
+    return timing_end(ctx, s);
 }
 
 int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final, uint64_t* d_offsets,
@@ -768,7 +737,7 @@ int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const
     const int rc = fg_frame_decode_impl(ctx, fmt, framing, d_bytes, nbytes, final, d_offsets, cap_frames, tables, avg_line_hint, stream, &d_total);
     if (rc != FG_OK) return rc;
     DeviceGuard guard(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     FG_HIP(ctx, hipMemcpyAsync(d_result, d_total, 16, hipMemcpyDeviceToDevice, s));
     return FG_OK;
 }
@@ -792,16 +761,12 @@ int fg_finish_deferred_general(fg_ctx* ctx, fg_framing framing, const uint8_t* d
     ctx->defer_general = false;
     if (!epoch || n == 0) return FG_OK;
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     fg::DevTables dt = to_dev(*tables);
     dt.n = n;
     dt.epoch = epoch;
-    dt.pending = ctx->d_pending + (epoch % 1024u);
-    const int rc = fg_launch_gelf_general(d_bytes, d_offsets, n, &dt, s, (uint32_t)framing, d_bad_utf8);
-    if (rc != 0) {
-        ctx->last_hip = rc;
-        return FG_ERR_HIP;
-    }
+    dt.pending = pending_word(ctx, epoch);
+    FG_LAUNCH(ctx, fg_launch_gelf_general(d_bytes, d_offsets, n, &dt, s, (uint32_t)framing, d_bad_utf8));
     return FG_OK;
 }
 
@@ -818,7 +783,7 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
     if (tables->n < n) return FG_ERR_ARG;
     if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;  // (the emitters' global reader loads aligned 16-byte chunks: as the decoders require)
     DeviceGuard g(ctx->device);
-    hipStream_t s = stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream;
+    hipStream_t s = stream_of(ctx, stream);
     if (total) *total = 0;
     fg::EncCfgHost h;
     if (!fg::build_enc_cfg(src_fmt, ecfg, ctx->suffix, ctx->has_suffix, &h)) return FG_ERR_ARG;
@@ -872,12 +837,8 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
     // LDS tile of a 64-line group: average group + 6.25 % + 512 B, 4..40 KiB (longer groups read from global memory);
     // the tile is what limits the waves per CU (the emitters are latency-bound: occupancy is throughput)
     const uint32_t tile_cap = pick_tile_cap(ctx, nbytes, n, 40 * 1024, 1);
-    if (ctx->timing) FG_HIP(ctx, hipEventRecord(ctx->ev0, s));
-    int lrc = fg_launch_encode_sizes(d_bytes, d_offsets, n, &dt, &cfg, tile_cap, cfg_lds, d_sizes, d_block_sums, d_enc_status, d_out_offsets, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
+    if ((rc = timing_begin(ctx, s)) != FG_OK) return rc;
+    FG_LAUNCH(ctx, fg_launch_encode_sizes(d_bytes, d_offsets, n, &dt, &cfg, tile_cap, cfg_lds, d_sizes, d_block_sums, d_enc_status, d_out_offsets, s));
     if (!async) {
         FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
@@ -886,16 +847,8 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
     } else {
         cfg.out_cap = out_cap ? out_cap : 1;  // the write kernel reads out_offsets[n] itself and leaves d_out alone when it exceeds this
     }
-    lrc = fg_launch_encode_write(d_bytes, d_offsets, n, &dt, &cfg, tile_cap, cfg_lds, d_out_offsets, d_out, d_sizes, s);
-    if (lrc != 0) {
-        ctx->last_hip = lrc;
-        return FG_ERR_HIP;
-    }
-    if (ctx->timing) {  // count + scan + write (fg_last_kernel_ms)
-        FG_HIP(ctx, hipEventRecord(ctx->ev1, s));
-        ctx->ev_valid = true;
-    }
-    return FG_OK;
+    FG_LAUNCH(ctx, fg_launch_encode_write(d_bytes, d_offsets, n, &dt, &cfg, tile_cap, cfg_lds, d_out_offsets, d_out, d_sizes, s));
+    return timing_end(ctx, s);  // count + scan + write (fg_last_kernel_ms)
 }
 }  // namespace
 

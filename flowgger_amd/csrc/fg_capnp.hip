@@ -88,23 +88,11 @@ __global__ __launch_bounds__(kWave, 2) void k_capnp(const uint8_t* __restrict__ 
 extern "C" int fg_launch_capnp(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, uint64_t avg_len,
                                hipStream_t stream, const fg_launch_opts* lo, fg::TicketSlot* tk) {
     if (n == 0) return 0;
-    fg::LaunchPlan p;
-    if (fg::plan_launch(fg::k_capnp<fg::kWindowKiB, false>, n, avg_len, 0u, 57344u, 0u, &p, *lo, fg::PlanFormat().classes(0u))) return -1;
-    dim3 grid(p.blocks), block(fg::kWave);
-    fg::FrameArgs fr{FG_FRAME_NONE, nullptr};
-    fg::take_tickets(&fr, tk, p);
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, *lo, tt.shares);
-#if defined(FG_PROF_BUILD)
-    if (fg::prof_requested()) {
-        fg::ProfRun pr;
-        if (!pr.begin(stream)) return -1;
-        hipLaunchKernelGGL((fg::k_capnp<fg::kWindowKiB, true>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk, pr.d, fr);
-        pr.end(stream, "capnp", p);
-        return (int)hipGetLastError();
-    }
-#endif
-    hipLaunchKernelGGL((fg::k_capnp<fg::kWindowKiB, false>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk,
-                       (unsigned long long*)nullptr, fr);
-    return (int)hipGetLastError();
+    const auto ks = fg::kernels(fg::k_capnp<fg::kWindowKiB, false>, FG_PROF_TWIN(fg::k_capnp<fg::kWindowKiB, true>), "capnp");
+    return fg::plan_and_launch(ks, fg::DecodeCall{n, t, stream, fg::FrameArgs{FG_FRAME_NONE, nullptr}, lo, tk}, avg_len, 0u, fg::kMaxTile, 0u,
+                               fg::PlanFormat().classes(0u),
+                               [&](auto k, const fg::LaunchPlan& p, const fg::DevTables& tt, const fg::FrameArgs& fr, unsigned long long* prof) {
+                                   hipLaunchKernelGGL(k, dim3(p.blocks), dim3(fg::kWave), p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk,
+                                                      prof, fr);
+                               });
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/fg_hip.h"
+#include "fg_cus.hpp"
 #include "fg_device.hpp"
 #include "fg_enc_cfg.hpp"
 #include "fg_fused_plan.hpp"
@@ -154,6 +155,7 @@ struct fg_ctx {
     uint64_t* d_stash = nullptr;
     uint64_t* d_stash2 = nullptr;  // the second lane's (fg_transcode_batch)
     uint32_t stash_blocks = 0;
+    static constexpr uint32_t kPendingRing = 1024;
     uint32_t* d_pending = nullptr;  // ring of kPendingRing hand-over words (DevTables::pending), zeroed once
     uint32_t* d_ticket = nullptr;   // ring of ticket counters, one per decode launch (fg::TicketSlot); zeroed once
     std::vector<uint32_t> h_ticket; // ... what each word holds once the launches issued so far have run
@@ -257,6 +259,18 @@ struct DeviceGuard {
             return FG_ERR_HIP;                    \
         }                                         \
     } while (0)
+// ... and for the kernel launchers (fg_launch_*: 0, or what went wrong as an int)
+#define FG_LAUNCH(ctx, call)                      \
+    do {                                          \
+        const int l_ = (call);                    \
+        if (l_ != 0) {                            \
+            (ctx)->last_hip = l_;                 \
+            return FG_ERR_HIP;                    \
+        }                                         \
+    } while (0)
+
+// the stream a call runs on: the caller's, or the ctx's own
+inline hipStream_t stream_of(const fg_ctx* ctx, void* stream) { return stream == FG_STREAM_OWN ? ctx->stream : (hipStream_t)stream; }
 
 inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 

@@ -607,36 +607,59 @@ __device__ __forceinline__ void fused_loop(const uint8_t* __restrict__ bytes, co
 }
 #endif
 
-// ---- host side: the grid and the kernel's arguments of a fused launch ----------------------------------------------------------------
-// base_lds = the dynamic LDS the format's kernel needs for the tile g.tile without the fused block (as plan_launch adds it up).
-// Zeroes the launch's scratch on `stream`.  Returns 0, or -1 (no device / a HIP error).
-template <class K>
-inline int fused_prepare(K kernel, const FusedGeom& g, uint32_t base_lds, uint64_t nbytes, int final_, uint32_t delim, uint64_t* d_offsets,
-                         uint64_t cap, uint8_t* scratch, uint32_t stash_blocks, const fg_launch_opts& lo, hipStream_t stream, FusedArgs* fa,
-                         uint32_t* lds_total, uint32_t* blocks) {
-    fa->nbytes = nbytes;
-    fa->S = g.S;
-    fa->look = g.look;
-    fa->delim4 = delim * 0x01010101u;
-    fa->final_ = final_ ? 1u : 0u;
-    fa->ext = g.ext >= 16u && g.ext <= 1024u ? g.ext & ~15u : 1024u;
-    fa->cap = cap;
-    fa->offsets = d_offsets;
-    fused_carve(scratch, nbytes, g.S, fa);
-    fa->lds_off = (base_lds + 15u) & ~15u;
-    *lds_total = fa->lds_off + fuse::lds_bytes(g.tile);
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, *lds_total) != hipSuccess || per_cu < 1) per_cu = 1;
+// ---- host side: the grid, the kernel's arguments and the launch of a fused launch -------------------------------------------------------
+// What a fused launcher (fg_launch_*_fused) was handed and passes on
+struct FusedCall {
+    uint64_t nbytes;
+    const DevTables* t;
+    const FusedGeom* g;
+    hipStream_t stream;
+    uint32_t strip;
+    int final_;
+    uint64_t* d_offsets;
+    uint64_t cap;
+    uint8_t* scratch;
+    const fg_launch_opts* lo;
+    unsigned long long** d_total;
+};
+// base_lds = the dynamic LDS the format's kernel needs for the tile g.tile without the fused block (as launch_geometry adds it up).
+// Zeroes the launch's scratch on the stream, sizes the grid by the occupancy of `kernel`, leaves *d_total and launches:
+// go(kernel, blocks, lds, tables, fused args) puts the format's own arguments around them.  Returns 0, or -1 / the launch's HIP error.
+template <class K, class Go>
+inline int launch_fused(K kernel, const FusedCall& c, uint32_t base_lds, uint32_t stash_blocks, Go go) {
+    const FusedGeom& g = *c.g;
+    if (c.nbytes == 0 || !g.ok) return -1;
+    const fg_launch_opts& lo = *c.lo;
+    FusedArgs fa{};
+    fa.nbytes = c.nbytes;
+    fa.S = g.S;
+    fa.look = g.look;
+    fa.delim4 = (c.strip == FG_FRAME_LINE ? 0x0Au : 0u) * 0x01010101u;
+    fa.final_ = c.final_ ? 1u : 0u;
+    fa.ext = g.ext >= 16u && g.ext <= 1024u ? g.ext & ~15u : 1024u;
+    fa.cap = c.cap;
+    fa.offsets = c.d_offsets;
+    fused_carve(c.scratch, c.nbytes, g.S, &fa);
+    fa.lds_off = (base_lds + 15u) & ~15u;
+    const uint32_t lds = fa.lds_off + fuse::lds_bytes(g.tile);
+    const int cus = device_cus();
+    if (cus < 1) return -1;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     if (lo.waves_per_cu > 0 && per_cu > (int)lo.waves_per_cu) per_cu = (int)lo.waves_per_cu;
     uint64_t b = (uint64_t)per_cu * (uint64_t)cus;
     if (stash_blocks && b > stash_blocks) b = stash_blocks;
-    if (b > fa->ntiles) b = fa->ntiles;
+    if (b > fa.ntiles) b = fa.ntiles;
     if (b < 1u) b = 1u;
-    *blocks = (uint32_t)b;
-    fa->counters = (lo.flags & FG_LO_STATIC_CHUNKS) ? 0u : b < kFusedCounters ? (uint32_t)b : kFusedCounters;
-    if (hipMemsetAsync(scratch, 0, fused_scratch_bytes(nbytes, g.S), stream) != hipSuccess) return -1;
-    return 0;
+    fa.counters = (lo.flags & FG_LO_STATIC_CHUNKS) ? 0u : b < kFusedCounters ? (uint32_t)b : kFusedCounters;
+    if (hipMemsetAsync(c.scratch, 0, fused_scratch_bytes(c.nbytes, g.S), c.stream) != hipSuccess) return -1;
+    DevTables tt = *c.t;
+    // (the lines this launch will see, for the entry reservations: the stream over the bytes the geometry gives a line)
+    const uint32_t line_bytes = g.S / g.L ? g.S / g.L : 1u;
+    tt.alloc_chunk = entry_chunk(tt.ent_cap, (uint32_t)b, c.nbytes / line_bytes + 1u, lo, tt.shares);
+    *c.d_total = fa.total;
+    go(kernel, (uint32_t)b, lds, tt, fa);
+    return (int)hipGetLastError();
 }
 
 }  // namespace fg

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/fg_hip.h"
+#include "fg_plan_policy.hpp"
 
 namespace fg {
 namespace fuse {
@@ -53,19 +54,19 @@ struct FusedGeom {
 inline FusedGeom fused_geometry(fg_format fmt, uint64_t avg_len, const fg_launch_opts& lo, bool link_bound) {
     FusedGeom g;
     if (avg_len < 1u) avg_len = 1u;
-    const bool head = (lo.flags & FG_LO_FORCE_HEAD) || (avg_len >= 768u && !(lo.flags & FG_LO_NO_HEAD));
+    const Variant v = pick_variant(avg_len, lo.flags);
     uint32_t bound = 0;
     switch (fmt) {
         case FG_RFC5424:
-            if (head) return g;
-            g.variant = ((lo.flags & FG_LO_SD_PAIRS) || (avg_len >= 320u && !(lo.flags & FG_LO_SD_WALK))) ? 1u : 0u;
+            if (v.head) return g;
+            g.variant = v.pairs ? 1u : 0u;
             g.L = 64u;
             // (the pair-parallel kernel's tile -- twice that across the link, where the grid is capped anyway and every byte of look-ahead
             //  is read twice over the link: the input side of the link is the ceiling there, 48 GB/s --; else the register window)
             bound = g.variant ? (link_bound ? 24576u : 12288u) : 16384u;
             break;
         case FG_LTSV:
-            if (head) return g;
+            if (v.head) return g;
             g.L = 64u;
             bound = 18432u;
             break;
@@ -73,15 +74,15 @@ inline FusedGeom fused_geometry(fg_format fmt, uint64_t avg_len, const fg_launch
             // resident: eight lines to the pass (the row loop's geometry: more lines cost LDS, i.e. waves); across the link
             // the grid is capped anyway and the look-ahead is re-read over the link: thirty-two lines to the tile
             g.L = link_bound ? 48u : 8u;
-            bound = link_bound ? 16384u : 8u * avg_len * 17u / 16u + 256u <= 3072u ? 3072u : 8192u;
-            if (!link_bound && bound == 3072u && !lo.tile_cap && !lo.lines_per_group && !(lo.flags & FG_LO_GELF_GENERIC)) g.variant = 1u;
+            bound = link_bound ? 16384u : gelf_group_fits_3k(avg_len) ? 3072u : 8192u;
+            if (!link_bound && gelf_const_3k(avg_len, lo) && !lo.lines_per_group) g.variant = 1u;
             // (MEASURED, 4 M lines on one box: 5.14 ms as shipped, 7.46 / 7.18 with tiles planned for 16 / 32 lines: profiles/r06at_gelf_fused_plan.log)
             break;
         default:
             return g;
     }
     if (lo.lines_per_group >= 1u && lo.lines_per_group <= 64u) g.L = lo.lines_per_group;
-    if (lo.tile_cap >= 1024u && lo.tile_cap <= 57344u) bound = (lo.tile_cap + 1023u) / 1024u * 1024u;
+    if (lo.tile_cap >= 1024u && lo.tile_cap <= kMaxTile) bound = (lo.tile_cap + 1023u) / 1024u * 1024u;
     if (bound < 2048u) bound = 2048u;
     if (link_bound) g.ext = 256u;  // (a KiB read on for a line that needed 150 bytes more is look-ahead too)
     if (lo.fused_ext >= 16u && lo.fused_ext <= 1024u) g.ext = lo.fused_ext & ~15u;
@@ -91,7 +92,7 @@ inline FusedGeom fused_geometry(fg_format fmt, uint64_t avg_len, const fg_launch
     // (the tile keeps the room plan_tile left for staging on: the LDS tile is the bound it planned with unless the lines are short)
     g.tile = g.variant == 1u && fmt == FG_GELF ? 3072u : (fuse::kPreBytes + g.S + g.look + (bound >= 8192u ? 1024u : g.look) + 16u + 1023u) / 1024u * 1024u;
     if (g.tile > bound) g.tile = bound;
-    if (g.tile < 4096u && !(g.variant == 1u && fmt == FG_GELF)) g.tile = 4096u;  // (plan_launch's floor)
+    if (g.tile < 4096u && !(g.variant == 1u && fmt == FG_GELF)) g.tile = 4096u;  // (launch_geometry's floor)
     g.ok = g.S >= 16u && fuse::kPreBytes + g.S + g.look + 16u <= g.tile;
     return g;
 }

@@ -759,22 +759,30 @@ __global__ __launch_bounds__(kWave, 2) void k_gelf_general(const uint8_t* __rest
 }  // namespace fg
 
 namespace {
+constexpr uint32_t kGelfMaxTile = 40960;
+// what the fast form asks of launch_geometry: its class bitmaps and the per-item / per-line arrays, which grow with the lines per group
+fg::PlanFormat gelf_format(uint32_t max_lines) {
+    return fg::PlanFormat().lines(max_lines).classes(fg::GelfFormat::kClasses).lds_for(fg::gelf_extra_lds);
+}
+
 // the fast-form kernel with a register window of NB KiB (the bytes of the NEXT group, prefetched while this one is decoded)
 template <int NB>
-int launch_gelf_fast(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, uint64_t avg_len,
-                     hipStream_t stream, uint32_t max_lines, fg::FrameArgs fr, const fg_launch_opts& lo, fg::TicketSlot* tk) {
+int launch_gelf_fast(const uint8_t* d_bytes, const uint64_t* d_offsets, const fg::DecodeCall& c, uint64_t avg_len, uint32_t max_lines) {
+    const fg_launch_opts& lo = *c.lo;
+    const auto generic = fg::kernels(fg::k_gelf<NB, false>, FG_PROF_TWIN(fg::k_gelf<NB, true>), "gelf");
+    auto go = [&](auto k, const fg::LaunchPlan& p, const fg::DevTables& tt, const fg::FrameArgs& fr, unsigned long long* prof) {
+        hipLaunchKernelGGL(k, dim3(p.blocks), dim3(fg::kWave), p.lds, c.stream, d_bytes, d_offsets, c.n, tt, p.tile, p.L, p.chunk, prof,
+                           (uint64_t*)nullptr, fr);
+    };
     fg::LaunchPlan p;
-    if (fg::plan_launch(fg::k_gelf<NB, false>, n, avg_len, 0u, 40960u, 0u, &p, lo, fg::PlanFormat().lines(max_lines).classes(fg::GelfFormat::kClasses).lds_for(fg::gelf_extra_lds)))
-        return -1;
-    dim3 grid(p.blocks), block(fg::kWave);
-    fg::DevTables tt = *t;
+    if (fg::plan_launch(generic.run, c.n, avg_len, 0u, kGelfMaxTile, 0u, &p, lo, gelf_format(max_lines))) return -1;
 #if defined(FG_PROF_BUILD)
     if (getenv("FG_PLAN")) fprintf(stderr, "gelf plan: L %u tile %u lds %u blocks %u window %d KiB\n", p.L, p.tile, p.lds, p.blocks, NB);
 #endif
     if constexpr (NB == 3) {
         if (p.tile == 4096u && p.L == 8u && !fg::prof_requested() && !(lo.flags & FG_LO_GELF_GENERIC)) {
             // the geometry of ~300-byte GELF (the BASELINE corpus): constants (every LDS address an immediate)
-            if (!lo.tile_cap && 8u * avg_len * 17u / 16u + 256u <= 3072u) {
+            if (fg::gelf_const_3k(avg_len, lo)) {
                 // ... and when the average group of eight fits 3 KiB, a tile of exactly the register window: 6.3 KiB of LDS and 96
                 // registers (two spilled) let twenty waves share a CU (4 KiB tiles: 8 040 B, and only eighteen fit -- 1481 vs
                 // 1422 M lines/s at sixteen, profiles/r04s_sweep_cfg3.log)
@@ -783,39 +791,19 @@ int launch_gelf_fast(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t
                 // (chunks of 64 lines = eight tiles, drawn by ticket: 4 M lines 1878-1886 M lines/s against 1805-1813 at 128, 1866-1870 at 48 / 96;
                 //  16 M lines 2051 against 2012 at 128 and 2003 at 256 -- one box, alternated, profiles/r05u_chunk_taper_sweep.log;
                 //  tickets from four chunks per wave on: at three -- 1 M lines -- one share per wave is as fast, profiles/r05v_policy_ab.log)
-                if (fg::plan_launch(fg::k_gelf<NB, false, 5, 3072u, 8u>, n, avg_len, 0u, 40960u, 0u, &p, lo3,
-                                    fg::PlanFormat().lines(max_lines).classes(fg::GelfFormat::kClasses).lds_for(fg::gelf_extra_lds).chunk(64u).tickets_from(4u)) ||
+                const auto k3 = fg::kernels(fg::k_gelf<NB, false, 5, 3072u, 8u>, nullptr, "gelf");
+                if (fg::plan_launch(k3.run, c.n, avg_len, 0u, kGelfMaxTile, 0u, &p, lo3, gelf_format(max_lines).chunk(64u).tickets_from(4u)) ||
                     p.tile != 3072u || p.L != 8u)
                     return -1;
-                fg::take_tickets(&fr, tk, p);
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, lo, tt.shares);
-                hipLaunchKernelGGL((fg::k_gelf<NB, false, 5, 3072u, 8u>), dim3(p.blocks), block, p.lds, stream, d_bytes, d_offsets, n, tt,
-                                   p.tile, p.L, p.chunk, (unsigned long long*)nullptr, (uint64_t*)nullptr, fr);
-                return 0;
+                return fg::launch_planned(k3, p, c, go);
             }
-            fg::take_tickets(&fr, tk, p);
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, lo, tt.shares);
-            hipLaunchKernelGGL((fg::k_gelf<NB, false, 4, 4096u, 8u>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L,
-                               p.chunk, (unsigned long long*)nullptr, (uint64_t*)nullptr, fr);
-            return 0;
+            // (the 4 KiB constants run on the plan made above: its grid is the occupancy of the GENERIC instantiation of this window,
+            //  the one place where the kernel planned for and the kernel launched differ)
+            return fg::launch_planned(fg::kernels(fg::k_gelf<NB, false, 4, 4096u, 8u>, nullptr, "gelf"), p, c, go);
         }
     }
-#if defined(FG_PROF_BUILD)
-    if (fg::prof_requested()) {
-        fg::ProfRun pr;
-        if (!pr.begin(stream)) return -1;
-        tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, lo, tt.shares);
-        hipLaunchKernelGGL((fg::k_gelf<NB, true>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk, pr.d,
-                           (uint64_t*)nullptr, fr);
-        pr.end(stream, "gelf", p);
-        return 0;
-    }
-#endif
-    fg::take_tickets(&fr, tk, p);
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, lo, tt.shares);
-    hipLaunchKernelGGL((fg::k_gelf<NB, false>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk,
-                       (unsigned long long*)nullptr, (uint64_t*)nullptr, fr);
-    return 0;
+    // (the measurement twin draws no tickets: its chunks go round-robin)
+    return fg::launch_planned(generic, p, c, go, /*prof_tickets=*/false);
 }
 }  // namespace
 
@@ -828,40 +816,36 @@ extern "C" int fg_launch_gelf(const uint8_t* d_bytes, const uint64_t* d_offsets,
     (void)stash;
     (void)stash_blocks;
     if (n == 0) return 0;
-    fg::LaunchPlan p;
     // The fast form keeps its records in registers and writes entries straight to the table: what it needs in LDS is the tile,
     // four class bitmaps and the per-item / per-line arrays, which grow with the lines per group.  Take the largest power of two
     // whose LDS still lets sixteen waves share a CU (measured on the 307-byte corpus, M lines/s: 8 lines per group 1050,
-    // 16: 677, 32: 803, 64: 398, 4: 436).  No global stash, no cap on the grid.
+    // 16: 677, 32: 803, 64: 398, 4: 436).  No global stash, no cap on the grid.  (Arithmetic alone: the kernel is picked behind it.)
     uint32_t max_lines = fg::kGelfLines;
     uint32_t lds_budget = 10u * 1024u;  // sixteen waves per CU
     if (lo.gelf_lds_budget) lds_budget = lo.gelf_lds_budget;  // tuning
+    auto geometry = [&]() { return fg::launch_geometry(n, avg_len, 0u, kGelfMaxTile, lo, gelf_format(max_lines)); };
     if (lo.lines_per_group) max_lines = lo.lines_per_group;
     else {
         while (max_lines > 4u) {
-            if (fg::plan_launch(fg::k_gelf<2, false>, n, avg_len, 0u, 40960u, 0u, &p, lo, fg::PlanFormat().lines(max_lines).classes(fg::GelfFormat::kClasses).lds_for(fg::gelf_extra_lds)))
-                return -1;
-            if (p.L < max_lines) max_lines = p.L;  // (the geometry already settled on fewer lines)
-            if (p.lds <= lds_budget) break;
+            const fg::LaunchGeometry geo = geometry();
+            if (geo.L < max_lines) max_lines = geo.L;  // (the geometry already settled on fewer lines)
+            if (geo.lds <= lds_budget) break;
             max_lines >>= 1;
         }
     }
-    if (fg::plan_launch(fg::k_gelf<2, false>, n, avg_len, 0u, 40960u, 0u, &p, lo, fg::PlanFormat().lines(max_lines).classes(fg::GelfFormat::kClasses).lds_for(fg::gelf_extra_lds)))
-        return -1;
+    const uint32_t lines = geometry().L;
     // The register window should hold the whole average group: what lies beyond it is staged by plain loads whose latency
     // nothing hides (and four chunks at a time).  1 KiB of window = 4 registers.
-    uint64_t want = ((uint64_t)p.L * avg_len * 17u / 16u + 128u + 1023u) / 1024u;
+    uint64_t want = ((uint64_t)lines * avg_len * 17u / 16u + 128u + 1023u) / 1024u;
     if (lo.gelf_window_kib) want = lo.gelf_window_kib;  // tuning
-    const fg::FrameArgs fr{strip, line_bad};
-    const dim3 block(fg::kWave);
+    const fg::DecodeCall c{n, t, stream, fg::FrameArgs{strip, line_bad}, lop, tk};
     int rc;
-    if (want <= 2) rc = launch_gelf_fast<2>(d_bytes, d_offsets, n, t, avg_len, stream, p.L, fr, lo, tk);
-    else if (want == 3) rc = launch_gelf_fast<3>(d_bytes, d_offsets, n, t, avg_len, stream, p.L, fr, lo, tk);
-    else if (want == 4) rc = launch_gelf_fast<4>(d_bytes, d_offsets, n, t, avg_len, stream, p.L, fr, lo, tk);
-    else if (want == 5) rc = launch_gelf_fast<5>(d_bytes, d_offsets, n, t, avg_len, stream, p.L, fr, lo, tk);
-    else rc = launch_gelf_fast<6>(d_bytes, d_offsets, n, t, avg_len, stream, p.L, fr, lo, tk);
-    if (rc) return rc;
-    if (hipGetLastError() != hipSuccess) return -1;
+    if (want <= 2) rc = launch_gelf_fast<2>(d_bytes, d_offsets, c, avg_len, lines);
+    else if (want == 3) rc = launch_gelf_fast<3>(d_bytes, d_offsets, c, avg_len, lines);
+    else if (want == 4) rc = launch_gelf_fast<4>(d_bytes, d_offsets, c, avg_len, lines);
+    else if (want == 5) rc = launch_gelf_fast<5>(d_bytes, d_offsets, c, avg_len, lines);
+    else rc = launch_gelf_fast<6>(d_bytes, d_offsets, c, avg_len, lines);
+    if (rc) return -1;
     // pending lines (a frame flagged as invalid UTF-8 never is: the pipeline has overwritten its status) -- unless the caller runs the
     // exact form ONCE for all the slices of a batch (fg_launch_gelf_general over all rows: the kernel is a chain of dependent steps,
     // ~170 us however few lines a slice hands it -- a quarter of the GPU time of a sliced host path, profiles/r04g2_probe_frame_gelf.log)
@@ -878,9 +862,8 @@ extern "C" int fg_launch_gelf_general(const uint8_t* d_bytes, const uint64_t* d_
 extern "C" int fg_launch_gelf_general_dev(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, hipStream_t stream,
                                           uint32_t strip, const uint8_t* line_bad, const unsigned long long* n_dev) {
     if (n == 0) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        return -1;
+    const int cus = fg::device_cus();
+    if (cus < 1) return -1;
     // the span: as long as it can be with a span for every wave of the grid (n / 1024 lines, a multiple of 64 in 64 .. 4096)
     uint64_t gblocks = (uint64_t)cus * 8u;
     uint32_t span = fg::kGeneralSpan;
@@ -902,23 +885,11 @@ constexpr int kGelfFusedMinW = 3;
 extern "C" int fg_launch_gelf_fused(const uint8_t* d_bytes, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom* g, hipStream_t stream,
                                     uint32_t strip, int final_, uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts* lo,
                                     unsigned long long** d_total) {
-    if (nbytes == 0 || !g->ok) return -1;
-    const uint32_t base_lds = g->tile + 64u + (g->tile / 16u + 16u) * 2u * fg::GelfFormat::kClasses + fg::gelf_extra_lds(g->tile, g->L);
-    fg::FusedArgs fa{};
-    uint32_t lds = 0, blocks = 0;
-    const uint32_t delim = strip == FG_FRAME_LINE ? 0x0Au : 0u;
     const bool konst = g->variant == 1u && g->tile == 3072u && g->L == 8u;
-    const int prc = konst ? fg::fused_prepare(fg::k_gelf_fused<3, kGelfFusedMinW, 3072u, 8u>, *g, base_lds, nbytes, final_, delim, d_offsets, cap, scratch, 0u, *lo, stream,
-                                              &fa, &lds, &blocks)
-                          : fg::fused_prepare(fg::k_gelf_fused<6, 4>, *g, base_lds, nbytes, final_, delim, d_offsets, cap, scratch, 0u, *lo, stream, &fa, &lds,
-                                              &blocks);
-    if (prc) return -1;
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, blocks, nbytes / (g->S / g->L ? g->S / g->L : 1u) + 1u, *lo, tt.shares);
-    *d_total = fa.total;
-    if (konst)
-        hipLaunchKernelGGL((fg::k_gelf_fused<3, kGelfFusedMinW, 3072u, 8u>), dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, fa, strip);
-    else
-        hipLaunchKernelGGL((fg::k_gelf_fused<6, 4>), dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, fa, strip);
-    return (int)hipGetLastError();
+    const auto kernel = konst ? fg::k_gelf_fused<3, kGelfFusedMinW, 3072u, 8u> : fg::k_gelf_fused<6, 4>;
+    return fg::launch_fused(kernel, fg::FusedCall{nbytes, t, g, stream, strip, final_, d_offsets, cap, scratch, lo, d_total},
+                            fg::tile_lds(g->tile, fg::GelfFormat::kClasses) + fg::gelf_extra_lds(g->tile, g->L), 0u,
+                            [&](auto k, uint32_t blocks, uint32_t lds, const fg::DevTables& tt, const fg::FusedArgs& fa) {
+                                hipLaunchKernelGGL(k, dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, fa, strip);
+                            });
 }

@@ -883,65 +883,41 @@ __global__ __launch_bounds__(kWave, 2) void k_ltsv_fused(const uint8_t* __restri
 
 }  // namespace fg
 
+namespace {
+template <bool HEAD>
+auto ltsv_kernels(const char* name) {
+    return fg::kernels(fg::k_ltsv<fg::kComputeBoundWindow, false, HEAD>, FG_PROF_TWIN(fg::k_ltsv<fg::kComputeBoundWindow, true, HEAD>), name);
+}
+}  // namespace
+
 extern "C" int fg_launch_ltsv(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t,
                               const fg::LtsvDevCfg* cfg, uint64_t avg_len, hipStream_t stream, uint64_t* stash,
                               uint32_t stash_blocks, uint32_t strip, const uint8_t* line_bad, const fg_launch_opts* lo, fg::TicketSlot* tk) {
     if (n == 0) return 0;
-    fg::LaunchPlan p;
     // long lines: only the head of every line is staged, the rest is scanned for a TAB (LtsvFormatT<true>)
-    const bool head = (lo->flags & FG_LO_FORCE_HEAD) || (avg_len >= 768u && !(lo->flags & FG_LO_NO_HEAD));
+    const bool head = fg::pick_variant(avg_len, lo->flags).head;
+    const auto ks = head ? ltsv_kernels<true>("ltsv (head)") : ltsv_kernels<false>("ltsv");
     const uint64_t plan_len = head ? (avg_len < fg::LtsvFormatT<true>::kHeadBytes ? avg_len : fg::LtsvFormatT<true>::kHeadBytes) : avg_len;
-    if (head ? fg::plan_launch(fg::k_ltsv<fg::kComputeBoundWindow, false, true>, n, plan_len, fg::kLtsvExtraLds, 57344u, stash ? stash_blocks : 0u, &p, *lo)
-             // (whole lines staged: chunks of 128 lines -- 3.78 vs 3.67 G lines/s with the pipeline's 256, alternated on one box,
-             //  profiles/r04z3_sweep_ltsv.log)
-             : fg::plan_launch(fg::k_ltsv<fg::kComputeBoundWindow, false>, n, plan_len, fg::kLtsvExtraLds, 57344u, stash ? stash_blocks : 0u, &p, *lo,
-                               fg::PlanFormat().chunk(128u)))
-        return -1;
+    // (whole lines staged: chunks of 128 lines -- 3.78 vs 3.67 G lines/s with the pipeline's 256, alternated on one box,
+    //  profiles/r04z3_sweep_ltsv.log)
+    const fg::PlanFormat pf = head ? fg::PlanFormat() : fg::PlanFormat().chunk(128u);
+    const uint32_t sb = stash ? stash_blocks : 0u;
     if (stash_blocks == 0) stash = nullptr;
-    dim3 grid(p.blocks), block(fg::kWave);
-    fg::FrameArgs fr{strip, line_bad};
-    fg::take_tickets(&fr, tk, p);
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, *lo, tt.shares);
-#if defined(FG_PROF_BUILD)
-    if (fg::prof_requested()) {
-        fg::ProfRun pr;
-        if (!pr.begin(stream)) return -1;
-        if (head)
-            hipLaunchKernelGGL((fg::k_ltsv<fg::kComputeBoundWindow, true, true>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, *cfg, p.tile,
-                               p.L, p.chunk, pr.d, stash, fr);
-        else
-            hipLaunchKernelGGL((fg::k_ltsv<fg::kComputeBoundWindow, true>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, *cfg, p.tile,
-                               p.L, p.chunk, pr.d, stash, fr);
-        pr.end(stream, head ? "ltsv (head)" : "ltsv", p);
-        return (int)hipGetLastError();
-    }
-#endif
-    if (head)
-        hipLaunchKernelGGL((fg::k_ltsv<fg::kComputeBoundWindow, false, true>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, *cfg, p.tile,
-                           p.L, p.chunk, (unsigned long long*)nullptr, stash, fr);
-    else
-        hipLaunchKernelGGL((fg::k_ltsv<fg::kComputeBoundWindow, false>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, *cfg, p.tile,
-                           p.L, p.chunk, (unsigned long long*)nullptr, stash, fr);
-    return (int)hipGetLastError();
+    return fg::plan_and_launch(ks, fg::DecodeCall{n, t, stream, fg::FrameArgs{strip, line_bad}, lo, tk}, plan_len, fg::kLtsvExtraLds, fg::kMaxTile, sb, pf,
+                               [&](auto k, const fg::LaunchPlan& p, const fg::DevTables& tt, const fg::FrameArgs& fr, unsigned long long* prof) {
+                                   hipLaunchKernelGGL(k, dim3(p.blocks), dim3(fg::kWave), p.lds, stream, d_bytes, d_offsets, n, tt, *cfg, p.tile, p.L,
+                                                      p.chunk, prof, stash, fr);
+                               });
 }
 
 // The fused launch (fg_fused.hpp): frame + decode of a raw stream chunk in one kernel (see fg_launch_rfc5424_fused).
 extern "C" int fg_launch_ltsv_fused(const uint8_t* d_bytes, uint64_t nbytes, const fg::DevTables* t, const fg::LtsvDevCfg* cfg, const fg::FusedGeom* g,
                                     hipStream_t stream, uint64_t* stash, uint32_t stash_blocks, uint32_t strip, int final_, uint64_t* d_offsets,
                                     uint64_t cap, uint8_t* scratch, const fg_launch_opts* lo, unsigned long long** d_total) {
-    if (nbytes == 0 || !g->ok) return -1;
-    const uint32_t base_lds = g->tile + 64u + (g->tile / 16u + 16u) * 2u + fg::kLtsvExtraLds;
-    fg::FusedArgs fa{};
-    uint32_t lds = 0, blocks = 0;
     if (stash_blocks == 0) stash = nullptr;
-    const uint32_t delim = strip == FG_FRAME_LINE ? 0x0Au : 0u;
-    if (fg::fused_prepare(fg::k_ltsv_fused<fg::kComputeBoundWindow>, *g, base_lds, nbytes, final_, delim, d_offsets, cap, scratch, stash ? stash_blocks : 0u, *lo,
-                          stream, &fa, &lds, &blocks))
-        return -1;
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, blocks, nbytes / (g->S / g->L ? g->S / g->L : 1u) + 1u, *lo, tt.shares);
-    *d_total = fa.total;
-    hipLaunchKernelGGL((fg::k_ltsv_fused<fg::kComputeBoundWindow>), dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, *cfg, g->tile, g->L, stash, fa, strip);
-    return (int)hipGetLastError();
+    return fg::launch_fused(fg::k_ltsv_fused<fg::kComputeBoundWindow>, fg::FusedCall{nbytes, t, g, stream, strip, final_, d_offsets, cap, scratch, lo, d_total},
+                            fg::tile_lds(g->tile) + fg::kLtsvExtraLds, stash ? stash_blocks : 0u,
+                            [&](auto k, uint32_t blocks, uint32_t lds, const fg::DevTables& tt, const fg::FusedArgs& fa) {
+                                hipLaunchKernelGGL(k, dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, *cfg, g->tile, g->L, stash, fa, strip);
+                            });
 }

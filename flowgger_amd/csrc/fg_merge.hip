@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/fg_hip.h"
+#include "fg_cus.hpp"
 
 namespace fg {
 
@@ -151,9 +152,8 @@ extern "C" int fg_launch_merge_device(const fg_tables* parts, uint32_t g, const 
         return (int)hipGetLastError();
     }
     if (nb > 0x7FFFFFFFull) return -1;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        return -1;
+    const int cus = fg::device_cus();
+    if (cus < 1) return -1;
     auto blocks_for = [&](uint64_t items) {
         uint64_t b = (items + 255u) / 256u;
         const uint64_t cap = (uint64_t)cus * 16u;

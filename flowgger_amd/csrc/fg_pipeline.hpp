@@ -737,29 +737,19 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
 }  // namespace fg
 
 // ---------------------------------------------------------------------------------------------
-// Host side: launch geometry shared by the three launchers
+// Host side: plan and launch, shared by the launchers.  The geometry itself -- lines per group, tile, LDS, which instantiation -- is
+// arithmetic and lives in fg_plan_policy.hpp (launch_geometry, pick_variant); what needs the device is here.
 // ---------------------------------------------------------------------------------------------
 #include <cstdio>
 #include <cstdlib>
 
+#include "fg_cus.hpp"
+
 namespace fg {
-constexpr int kWindowKiB = 20;  // register prefetch window per wave (NB): 80 VGPRs
 // The LTSV / GELF tokenisers are compute-bound (hundreds of instructions per line) and register
 // hungry: they keep only a token window (the rest of a group is staged by the plain tail loop,
 // ~2 us of exposed latency against a group time of tens of us) and get the registers instead.
 constexpr int kComputeBoundWindow = 2;
-
-struct LaunchPlan {
-    uint32_t L = 64;      // lines per group
-    uint32_t tile = 0;    // LDS tile bytes (multiple of 1024)
-    uint32_t lds = 0;     // dynamic LDS bytes per workgroup = tile + 64 + bitmap + extra
-    uint64_t groups = 0;  // an estimate (the waves cut their ranges into groups themselves)
-    uint64_t chunk = 256; // lines a wave takes at a time (the first by block index, the rest by ticket)
-    uint64_t chunks = 0;  // ceil(n / chunk) >= blocks
-    bool tickets = false; // chunks beyond a wave's first are drawn from the launch's ticket counter (else: round-robin)
-    uint32_t taper[3] = {kNoTaper, kNoTaper, kNoTaper};  // ticket launches: where the chunks shrink (fg_plan_policy.hpp)
-    uint32_t blocks = 0;  // persistent grid
-};
 
 // The launch's ticket counter into the kernel's arguments; the host's copy of the counter moves on by what the launch will draw
 // (every wave draws until its first ticket beyond the last chunk: chunks - blocks good ones + blocks bad ones = chunks).
@@ -772,92 +762,21 @@ inline void take_tickets(FrameArgs* fr, TicketSlot* tk, const LaunchPlan& p) {
     *tk->h_val += (uint32_t)p.chunks;
 }
 
-// Lines per group L and the LDS tile: the largest power of two L <= 64 whose average group
-// (+6.25 % + 256 B) fits the register prefetch window, so that a whole group is prefetched.
-// Lines longer than the window get L = 1 and a tile of up to `max_tile` (the part beyond the
-// window is staged by the tail loop); anything that still does not fit is parsed from global
-// memory.  fg_launch_opts (fg_set_launch_opts: tuning, parity sweeps) overrides tile / lines per group / waves per CU; the
-// library itself reads no environment variable.
-// What a format says about its own launch, by NAME (twelve positional arguments ending `64, 1, nullptr, nullptr, 0u, 0u, 20u, 0u`
-// were one swapped literal away from a silent performance regression): PlanFormat().classes(2).extra_tile(f).tile(12288).chunk(128) ...
-struct PlanFormat {
-    uint32_t max_lines = 64;        // lines a group holds at most (the wave width, or the format's cap)
-    uint32_t n_classes = 1;         // stage-A class bitmaps kept in LDS
-    uint32_t (*extra_for)(uint32_t tile, uint32_t lines) = nullptr;  // LDS that grows with the tile and the lines per group (per-item arrays)
-    uint32_t (*extra_tile)(uint32_t tile) = nullptr;                 // LDS that grows with the tile only
-    uint32_t default_tile = 0;      // a cap on the tile the format gets by default (its LDS beyond the tile grows with it)
-    uint32_t default_chunk = 0;     // lines a wave takes at a time under ticket dispatch (0: 256 / 512 by the lines a tile holds)
-    uint32_t ticket_from = 2;       // chunks of that size per wave from which chunks are drawn by ticket
-    uint32_t taper = 1;             // levels of the taper at the end of a ticket launch
-    PlanFormat& lines(uint32_t v) { max_lines = v; return *this; }
-    PlanFormat& classes(uint32_t v) { n_classes = v; return *this; }
-    PlanFormat& lds_for(uint32_t (*f)(uint32_t, uint32_t)) { extra_for = f; return *this; }
-    PlanFormat& lds_tile(uint32_t (*f)(uint32_t)) { extra_tile = f; return *this; }
-    PlanFormat& tile(uint32_t v) { default_tile = v; return *this; }
-    PlanFormat& chunk(uint32_t v) { default_chunk = v; return *this; }
-    PlanFormat& tickets_from(uint32_t v) { ticket_from = v; return *this; }
-    PlanFormat& taper_levels(uint32_t v) { taper = v; return *this; }
-};
+// The geometry of a launch (launch_geometry) and its grid: what the occupancy of `kernel` at that LDS allows on this device, capped by
+// the estimate of the groups, the caller's stash and fg_launch_opts.waves_per_cu -- then how the batch is cut into chunks (plan_chunks).
 template <class K>
 inline int plan_launch(K kernel, uint64_t n, uint64_t avg_len, uint32_t extra_lds, uint32_t max_tile, uint32_t stash_blocks, LaunchPlan* p,
                        const fg_launch_opts& lo, const PlanFormat& pf = PlanFormat()) {
-    const uint32_t max_lines = pf.max_lines, n_classes = pf.n_classes, default_tile = pf.default_tile, default_chunk = pf.default_chunk;
-    const uint32_t ticket_from = pf.ticket_from, taper = pf.taper;
-    uint32_t (*const extra_for)(uint32_t, uint32_t) = pf.extra_for;
-    uint32_t (*const extra_tile)(uint32_t) = pf.extra_tile;
-    const uint64_t window = (uint64_t)kWindowKiB * 1024u;
-    // (+6.25 % + 256 B over the average group: a few sigma for the corpora at hand; a longer group just takes
-    //  another pass over a restaged tile, while every KiB of LDS saved is occupancy)
-    auto tile_for = [&](uint32_t l) { return (((uint64_t)l * avg_len * 17u / 16u + 256u) + 1023u) / 1024u * 1024u; };
-    auto clamp = [&](uint64_t v) { return (uint32_t)(v < 4096u ? 4096u : v > max_tile ? max_tile : v); };
-    uint32_t L = max_lines;
-    // (up to two 1-KiB rows beyond the window are tolerated: the plain tail loop stages them; measured on
-    //  the 554-byte structured-data corpus L = 32 at 6 waves/CU beats L = 16 at 8 by 30 %)
-    while (L > 1 && tile_for(L) > window + 2048u) L >>= 1;
-    uint32_t tile = clamp(tile_for(L));
-    if (lo.lines_per_group >= 1 && lo.lines_per_group <= max_lines) {
-        L = lo.lines_per_group;
-        tile = clamp(tile_for(L));
-    }
-    // (default_tile: a format whose LDS beyond the tile grows with it caps the tile it gets by default)
-    if (default_tile && tile > default_tile && !(lo.lines_per_group >= 1 && lo.lines_per_group <= max_lines)) tile = default_tile;
-    if (lo.tile_cap >= 1024 && lo.tile_cap <= max_tile) tile = (lo.tile_cap + 1023u) / 1024u * 1024u;
-    // Groups are cut BY BYTES (persistent_loop): L is only the cap on the lines of a group.  A format without per-line LDS arrays
-    // takes the full wave width -- however long the lines, a group then holds as many as fit the tile; the tile of long lines
-    // (fewer than 16 average lines in the window) is raised to what eight waves per CU leave each other anyway.
-    if (!extra_for && !(lo.lines_per_group >= 1 && lo.lines_per_group <= max_lines)) {
-        if (L <= 16u && !(lo.tile_cap >= 1024 && lo.tile_cap <= max_tile) && tile < 18432u && max_tile >= 18432u && !default_tile) tile = 18432u;
-        L = max_lines;
-    }
-    p->L = L;
-    p->tile = tile;
-    // (extra_for: LDS a format needs as a function of the tile and the lines per group, e.g. per-item arrays)
-    p->lds = tile + 64u + (tile / 16u + 16u) * 2u * (n_classes ? n_classes : 1u) + extra_lds + (extra_for ? extra_for(tile, L) : 0u) +
-             (extra_tile ? extra_tile(tile) : 0u);
-    {   // an estimate (the waves cut their ranges themselves): by lines and by bytes
-        const uint64_t by_lines = (n + L - 1) / L, by_bytes = (n * avg_len + tile - 1) / tile;
-        p->groups = by_lines > by_bytes ? by_lines : by_bytes;
-    }
-    int dev = 0, cus = 0;  // (per call: a process may drive several devices)
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        return -1;
+    static_cast<LaunchGeometry&>(*p) = launch_geometry(n, avg_len, extra_lds, max_tile, lo, pf);
+    const int cus = device_cus();
+    if (cus < 1) return -1;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, p->lds) != hipSuccess || per_cu < 1) per_cu = 1;
     if (lo.waves_per_cu > 0 && per_cu > (int)lo.waves_per_cu) per_cu = (int)lo.waves_per_cu;
     uint64_t blocks = (uint64_t)per_cu * (uint64_t)cus;
     if (blocks > p->groups) blocks = p->groups;
     if (stash_blocks && blocks > stash_blocks) blocks = stash_blocks;
-    // 256 lines per chunk (four groups of 64 short lines: the HBM-bound configuration keeps its sweep tight) -- 512 when a group
-    // holds fewer than L average lines, so that the short group at the end of every chunk stays a few per cent (same-box sweep,
-    // tools/sweep.py, 4 M lines: cfg4 1058 / 1150 / 974 M lines/s at 256 / 512 / 1024 -- the grid's 1792 waves need a few rounds
-    // of chunks each to finish together)
-    // (default_chunk: a format's own choice -- fg_rfc5424.hip, fg_gelf.hip, fg_ltsv.hip: each from a same-box sweep under ticket dispatch)
-    const uint64_t full = default_chunk ? default_chunk : (avg_len ? (uint64_t)p->tile / avg_len : p->L) >= p->L ? 256u : 512u;
-    // lines an average group holds (groups are cut by bytes): the unit chunks are made of
-    const uint64_t g = avg_len ? ((uint64_t)p->tile * 16u) / (avg_len * 17u) : p->L;
-    // how the batch is cut into chunks, and whether chunks are drawn by ticket: pure arithmetic, fg_plan_policy.hpp (CPU-tested)
-    const ChunkPlan cp = plan_chunks(n, blocks, p->L, g, full, ticket_from, lo, taper);
+    const ChunkPlan cp = plan_chunks(n, blocks, p->L, p->g, p->full, pf.ticket_from, lo, pf.taper);
     p->chunk = cp.chunk;
     p->chunks = cp.chunks;
     p->tickets = cp.tickets;
@@ -871,8 +790,10 @@ inline int plan_launch(K kernel, uint64_t n, uint64_t avg_len, uint32_t extra_ld
 // (FG_ABLATE: ablation flags).  The product library has neither the instantiations nor any read of the environment.
 #if defined(FG_PROF_BUILD)
 inline bool prof_requested() { return getenv("FG_PROF") != nullptr; }
+#define FG_PROF_TWIN(...) (__VA_ARGS__)
 #else
 constexpr bool prof_requested() { return false; }
+#define FG_PROF_TWIN(...) nullptr
 #endif
 struct ProfRun {
     unsigned long long* d = nullptr;
@@ -903,4 +824,53 @@ struct ProfRun {
         }
     }
 };
+
+// The instantiation a launcher has picked, named ONCE: the kernel the product runs -- the function plan_launch asks the occupancy of
+// and the function that is launched -- and its PROF = true twin (the same signature; FG_PROF_TWIN(k<.., true, ..>): null in the
+// product build, which does not compile it), with the name the measurement build prints.
+template <class K>
+struct Kernels {
+    K run, prof;
+    const char* name;
+};
+template <class K>
+inline Kernels<K> kernels(K run, typename SameAs<K>::type prof, const char* name) { return Kernels<K>{run, prof, name}; }
+
+// What a decode launcher was handed and passes on
+struct DecodeCall {
+    uint64_t n;
+    const DevTables* t;
+    hipStream_t stream;
+    FrameArgs fr;
+    const fg_launch_opts* lo;
+    TicketSlot* tk;
+};
+// A planned launch: tickets, the entry chunk of THIS grid, the launch -- go(kernel, plan, tables, frame args, prof words) puts the
+// format's own arguments around them -- and the launch's error.  Measurement build under FG_PROF: the twin, bracketed by a ProfRun
+// (prof_tickets = false: that launch draws no tickets and runs its chunks round-robin).
+template <class K, class Go>
+inline int launch_planned(const Kernels<K>& k, const LaunchPlan& p, const DecodeCall& c, Go go, bool prof_tickets = true) {
+    const bool prof = k.prof != nullptr && prof_requested();
+    FrameArgs fr = c.fr;
+    if (!prof || prof_tickets) take_tickets(&fr, c.tk, p);
+    DevTables tt = *c.t;
+    tt.alloc_chunk = entry_chunk(tt.ent_cap, p.blocks, c.n, *c.lo, tt.shares);
+    if (prof) {
+        ProfRun pr;
+        if (!pr.begin(c.stream)) return -1;
+        go(k.prof, p, tt, fr, pr.d);
+        pr.end(c.stream, k.name, p);
+    } else {
+        go(k.run, p, tt, fr, (unsigned long long*)nullptr);
+    }
+    return (int)hipGetLastError();
+}
+// ... behind its plan (plan_launch's arguments from avg_len on)
+template <class K, class Go>
+inline int plan_and_launch(const Kernels<K>& k, const DecodeCall& c, uint64_t avg_len, uint32_t extra_lds, uint32_t max_tile, uint32_t stash_blocks,
+                           const PlanFormat& pf, Go go) {
+    LaunchPlan p;
+    if (plan_launch(k.run, c.n, avg_len, extra_lds, max_tile, stash_blocks, &p, *c.lo, pf)) return -1;
+    return launch_planned(k, p, c, go);
+}
 }  // namespace fg

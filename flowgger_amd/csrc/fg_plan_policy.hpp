@@ -1,6 +1,8 @@
-// fg_plan_policy.hpp -- the HOST-side policies of a decode launch that are pure arithmetic: how the lines of a batch are cut into chunks
-// (and whether chunks beyond a wave's first are drawn from the launch's ticket counter), and how many entry slots a wave reserves at a
-// time.  No HIP dependency: plan_launch (fg_pipeline.hpp) calls these, and tests/test_plan_policy_cpu.py sweeps them on the CPU.
+// fg_plan_policy.hpp -- the HOST-side policies of a decode launch that are pure arithmetic: which kernel instantiation a batch gets
+// (pick_variant), lines per group, LDS tile and dynamic LDS (launch_geometry), how the lines of a batch are cut into chunks (and whether
+// chunks beyond a wave's first are drawn from the launch's ticket counter), and how many entry slots a wave reserves at a time.
+// No HIP dependency: plan_launch (fg_pipeline.hpp) adds the device's answers -- compute units, occupancy -- and the launchers and
+// fg_fused_plan.hpp call these; tests/test_plan_policy_cpu.py checks them on the CPU.
 #pragma once
 #include <stdint.h>
 
@@ -142,6 +144,135 @@ inline ChunkPlan plan_chunks(uint64_t n, uint64_t blocks, uint32_t L, uint64_t g
     }
     p.blocks = (uint32_t)(blocks > p.chunks ? p.chunks : blocks);
     p.tickets = tickets;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Launch geometry: lines per group, LDS tile, dynamic LDS -- and which kernel instantiation a batch gets
+// ---------------------------------------------------------------------------------------------
+constexpr int kWindowKiB = 20;  // register prefetch window per wave (NB): 80 VGPRs
+constexpr uint32_t kMaxTile = 57344;  // the largest LDS tile a launch takes (fg_launch_opts.tile_cap beyond it is ignored)
+
+// dynamic LDS of a streaming kernel without a format's own block: the tile, the 64-byte pad behind it, `classes` bitmaps (persistent_loop)
+constexpr uint32_t tile_lds(uint32_t tile, uint32_t classes = 1) { return tile + 64u + (tile / 16u + 16u) * 2u * classes; }
+
+// The default tile of the short-line whole-line RFC5424 launch: the largest multiple of 1 KiB whose LDS (tile + 64 + one bitmap) leaves
+// eight waves per CU -- what the kernel's registers allow -- room in the CU's 160 KiB.
+constexpr uint32_t kShortLineTile = 17408;
+static_assert(tile_lds(kShortLineTile) <= 160u * 1024u / 8u, "eight waves per CU");
+static_assert(tile_lds(kShortLineTile + 1024u) > 160u * 1024u / 8u, "the largest such tile");
+
+// The instantiation of a batch by its average line length (RFC5424; LTSV takes `head` alone), with the tuning flags that force either way.
+//   head:  long lines -- only the head of every line is staged (persistent_loop<..., HEAD>): the message is never looked into
+//   pairs: lines long enough to carry structured data -- the instantiation with the pair-parallel walk (its LDS scratch costs the
+//          headline configuration -- 254-byte lines without structured data -- a wave per CU, so short lines keep the kernel they had)
+constexpr uint64_t kHeadFromLen = 768, kPairsFromLen = 320;
+struct Variant { bool head, pairs; };
+inline Variant pick_variant(uint64_t avg_len, uint32_t flags) {
+    return Variant{(flags & FG_LO_FORCE_HEAD) || (avg_len >= kHeadFromLen && !(flags & FG_LO_NO_HEAD)),
+                   (flags & FG_LO_SD_PAIRS) || (avg_len >= kPairsFromLen && !(flags & FG_LO_SD_WALK))};
+}
+// GELF: the average group of eight lines (+6.25 % + 256 B) fits a tile of exactly the 3 KiB register window ...
+inline bool gelf_group_fits_3k(uint64_t avg_len) { return 8u * avg_len * 17u / 16u + 256u <= 3072u; }
+// ... and the launch takes the instantiation with that geometry as constants (the caller has settled on eight lines to the group)
+inline bool gelf_const_3k(uint64_t avg_len, const fg_launch_opts& lo) {
+    return gelf_group_fits_3k(avg_len) && !lo.tile_cap && !(lo.flags & FG_LO_GELF_GENERIC);
+}
+
+// What a format says about its own launch, by NAME (twelve positional arguments ending `64, 1, nullptr, nullptr, 0u, 0u, 20u, 0u`
+// were one swapped literal away from a silent performance regression): PlanFormat().classes(2).lds_tile(f).tile(12288).chunk(128) ...
+struct PlanFormat {
+    uint32_t max_lines = 64;        // lines a group holds at most (the wave width, or the format's cap)
+    uint32_t n_classes = 1;         // stage-A class bitmaps kept in LDS
+    uint32_t (*extra_for)(uint32_t tile, uint32_t lines) = nullptr;  // LDS that grows with the tile and the lines per group (per-item arrays)
+    uint32_t (*extra_tile)(uint32_t tile) = nullptr;                 // LDS that grows with the tile only
+    uint32_t default_tile = 0;      // a cap on the tile the format gets by default (its LDS beyond the tile grows with it)
+    uint32_t default_chunk = 0;     // lines a wave takes at a time under ticket dispatch (0: 256 / 512 by the lines a tile holds)
+    uint32_t ticket_from = 2;       // chunks of that size per wave from which chunks are drawn by ticket
+    uint32_t taper = 1;             // levels of the taper at the end of a ticket launch
+    PlanFormat& lines(uint32_t v) { max_lines = v; return *this; }
+    PlanFormat& classes(uint32_t v) { n_classes = v; return *this; }
+    PlanFormat& lds_for(uint32_t (*f)(uint32_t, uint32_t)) { extra_for = f; return *this; }
+    PlanFormat& lds_tile(uint32_t (*f)(uint32_t)) { extra_tile = f; return *this; }
+    PlanFormat& tile(uint32_t v) { default_tile = v; return *this; }
+    PlanFormat& chunk(uint32_t v) { default_chunk = v; return *this; }
+    PlanFormat& tickets_from(uint32_t v) { ticket_from = v; return *this; }
+    PlanFormat& taper_levels(uint32_t v) { taper = v; return *this; }
+};
+// The RFC5424 launch without the pair-parallel walk (whole lines or heads): tickets from 20 chunks per wave on (the HBM-bound kernel
+// pays for the first round's burst, plan_chunks) and, for short lines, a tile of at most kShortLineTile -- the whole-line kernel takes
+// 209 VGPRs, two waves per SIMD, and with the 18 KiB tile that 64 lines of 254 B ask for, LDS -- 20.8 KiB per wave -- cut that to SEVEN
+// waves per CU; 17 KiB is 19.7 KiB of LDS, eight.  cfg2, one box, alternated: 15.13-15.73 G lines/s at 18 KiB, 15.89-16.91 at 17 KiB,
+// 14.76-15.11 at 16 KiB, where groups are cut short by bytes.
+inline PlanFormat rfc5424_walk_format(uint64_t avg_len) {
+    return PlanFormat().tickets_from(20u).taper_levels(0u).tile(avg_len < kPairsFromLen ? kShortLineTile : 0u);
+}
+
+struct LaunchGeometry {
+    uint32_t L = 64;      // lines per group
+    uint32_t tile = 0;    // LDS tile bytes (multiple of 1024)
+    uint32_t lds = 0;     // dynamic LDS bytes per workgroup = tile + 64 + bitmap + extra
+    uint64_t groups = 0;  // an estimate (the waves cut their ranges into groups themselves)
+    uint64_t full = 256;  // plan_chunks' `full`: the format's chunk for large batches
+    uint64_t g = 64;      // plan_chunks' `g`: lines an average group holds
+};
+struct LaunchPlan : LaunchGeometry {
+    uint64_t chunk = 256; // lines a wave takes at a time (the first by block index, the rest by ticket)
+    uint64_t chunks = 0;  // ceil(n / chunk) >= blocks
+    bool tickets = false; // chunks beyond a wave's first are drawn from the launch's ticket counter (else: round-robin)
+    uint32_t taper[3] = {kNoTaper, kNoTaper, kNoTaper};  // ticket launches: where the chunks shrink
+    uint32_t blocks = 0;  // persistent grid
+};
+
+// Lines per group L and the LDS tile: the largest power of two L <= 64 whose average group
+// (+6.25 % + 256 B) fits the register prefetch window, so that a whole group is prefetched.
+// Lines longer than the window get L = 1 and a tile of up to `max_tile` (the part beyond the
+// window is staged by the tail loop); anything that still does not fit is parsed from global
+// memory.  fg_launch_opts (fg_set_launch_opts: tuning, parity sweeps) overrides tile / lines per group / waves per CU; the
+// library itself reads no environment variable.
+inline LaunchGeometry launch_geometry(uint64_t n, uint64_t avg_len, uint32_t extra_lds, uint32_t max_tile, const fg_launch_opts& lo,
+                                      const PlanFormat& pf = PlanFormat()) {
+    const uint64_t window = (uint64_t)kWindowKiB * 1024u;
+    // (+6.25 % + 256 B over the average group: a few sigma for the corpora at hand; a longer group just takes
+    //  another pass over a restaged tile, while every KiB of LDS saved is occupancy)
+    auto tile_for = [&](uint32_t l) { return (((uint64_t)l * avg_len * 17u / 16u + 256u) + 1023u) / 1024u * 1024u; };
+    auto clamp = [&](uint64_t v) { return (uint32_t)(v < 4096u ? 4096u : v > max_tile ? max_tile : v); };
+    const bool named_lines = lo.lines_per_group >= 1 && lo.lines_per_group <= pf.max_lines;
+    const bool named_tile = lo.tile_cap >= 1024 && lo.tile_cap <= max_tile;
+    LaunchGeometry p;
+    uint32_t L = pf.max_lines;
+    // (up to two 1-KiB rows beyond the window are tolerated: the plain tail loop stages them; measured on
+    //  the 554-byte structured-data corpus L = 32 at 6 waves/CU beats L = 16 at 8 by 30 %)
+    while (L > 1 && tile_for(L) > window + 2048u) L >>= 1;
+    if (named_lines) L = lo.lines_per_group;
+    uint32_t tile = clamp(tile_for(L));
+    // (default_tile: a format whose LDS beyond the tile grows with it caps the tile it gets by default)
+    if (pf.default_tile && tile > pf.default_tile && !named_lines) tile = pf.default_tile;
+    if (named_tile) tile = (lo.tile_cap + 1023u) / 1024u * 1024u;
+    // Groups are cut BY BYTES (persistent_loop): L is only the cap on the lines of a group.  A format without per-line LDS arrays
+    // takes the full wave width -- however long the lines, a group then holds as many as fit the tile; the tile of long lines
+    // (fewer than 16 average lines in the window) is raised to what eight waves per CU leave each other anyway.
+    if (!pf.extra_for && !named_lines) {
+        if (L <= 16u && !named_tile && tile < 18432u && max_tile >= 18432u && !pf.default_tile) tile = 18432u;
+        L = pf.max_lines;
+    }
+    p.L = L;
+    p.tile = tile;
+    // (extra_for: LDS a format needs as a function of the tile and the lines per group, e.g. per-item arrays)
+    p.lds = tile_lds(tile, pf.n_classes ? pf.n_classes : 1u) + extra_lds + (pf.extra_for ? pf.extra_for(tile, L) : 0u) +
+            (pf.extra_tile ? pf.extra_tile(tile) : 0u);
+    {   // an estimate (the waves cut their ranges themselves): by lines and by bytes
+        const uint64_t by_lines = (n + L - 1) / L, by_bytes = (n * avg_len + tile - 1) / tile;
+        p.groups = by_lines > by_bytes ? by_lines : by_bytes;
+    }
+    // 256 lines per chunk (four groups of 64 short lines: the HBM-bound configuration keeps its sweep tight) -- 512 when a group
+    // holds fewer than L average lines, so that the short group at the end of every chunk stays a few per cent (same-box sweep,
+    // tools/sweep.py, 4 M lines: cfg4 1058 / 1150 / 974 M lines/s at 256 / 512 / 1024 -- the grid's 1792 waves need a few rounds
+    // of chunks each to finish together)
+    // (default_chunk: a format's own choice -- fg_rfc5424.hip, fg_gelf.hip, fg_ltsv.hip: each from a same-box sweep under ticket dispatch)
+    p.full = pf.default_chunk ? pf.default_chunk : (avg_len ? (uint64_t)tile / avg_len : L) >= L ? 256u : 512u;
+    // lines an average group holds (groups are cut by bytes): the unit chunks are made of
+    p.g = avg_len ? ((uint64_t)tile * 16u) / (avg_len * 17u) : L;
     return p;
 }
 

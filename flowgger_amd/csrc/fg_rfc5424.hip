@@ -1120,11 +1120,12 @@ extern "C" uint64_t fg_stash_bytes(uint32_t blocks) {
     return (uint64_t)blocks * fg::kStashEntries * fg::kStashWords * fg::kWave * sizeof(uint64_t);
 }
 
-// The default tile of the short-line whole-line launch: the largest multiple of 1 KiB whose LDS (tile + 64 + one bitmap) leaves eight
-// waves per CU -- what the kernel's registers allow -- room in the CU's 160 KiB.
-constexpr uint32_t kShortLineTile = 17408;
-static_assert(kShortLineTile + 64u + (kShortLineTile / 16u + 16u) * 2u <= 160u * 1024u / 8u, "eight waves per CU");
-static_assert(kShortLineTile + 1024u + 64u + ((kShortLineTile + 1024u) / 16u + 16u) * 2u > 160u * 1024u / 8u, "the largest such tile");
+namespace {
+template <bool HEAD, bool SDX>
+auto rfc5424_kernels(const char* name) {
+    return fg::kernels(fg::k_rfc5424<fg::kWindowKiB, false, HEAD, SDX>, FG_PROF_TWIN(fg::k_rfc5424<fg::kWindowKiB, true, HEAD, SDX>), name);
+}
+}  // namespace
 
 // host-side launcher (called from fg_capi.cpp).  stash: device scratch of fg_stash_bytes(stash_blocks)
 // bytes (or NULL: SD lines are then parsed twice); the persistent grid is capped at stash_blocks.
@@ -1132,75 +1133,32 @@ extern "C" int fg_launch_rfc5424(const uint8_t* d_bytes, const uint64_t* d_offse
                                  uint64_t avg_len, hipStream_t stream, uint64_t* stash, uint32_t stash_blocks, uint32_t strip,
                                  const uint8_t* line_bad, const fg_launch_opts* lo, fg::TicketSlot* tk) {
     if (n == 0) return 0;
-    fg::LaunchPlan p;
-    // long lines: only the head of every line is staged (persistent_loop<..., HEAD>): the message is never looked into
-    const bool head = (lo->flags & FG_LO_FORCE_HEAD) || (avg_len >= 768u && !(lo->flags & FG_LO_NO_HEAD));
-    // lines long enough to carry structured data: the instantiation with the pair-parallel walk (its LDS scratch costs the headline
-    // configuration -- 254-byte lines without structured data -- a wave per CU, so short lines keep the kernel they had)
-    const bool sdx = (lo->flags & FG_LO_SD_PAIRS) || (avg_len >= 320u && !(lo->flags & FG_LO_SD_WALK));
-    const uint64_t plan_len = head ? (avg_len < fg::kHeadCap ? avg_len : fg::kHeadCap) : avg_len;
+    const fg::Variant v = fg::pick_variant(avg_len, lo->flags);
+    const auto ks = v.pairs ? (v.head ? rfc5424_kernels<true, true>("rfc5424 (head, pairs)") : rfc5424_kernels<false, true>("rfc5424 (pairs)"))
+                            : (v.head ? rfc5424_kernels<true, false>("rfc5424 (head)") : rfc5424_kernels<false, false>("rfc5424"));
+    // (default tile from the same-box sweeps, profiles/r04g_sweep_*: 12 KiB -- eight waves per CU -- for whole lines and for heads)
+    // (THREE waves per SIMD -- the compiler fits the whole-line instantiation into 168 registers without a spill under
+    //  __launch_bounds__(64, 3) -- with the 8 KiB tile and window that twelve waves per CU leave each other: 1.64-1.71 G lines/s
+    //  against 1.98-2.08 at 4-16 M lines, 9 KiB / eleven waves 1.71-1.78: fourteen lines to the group instead of twenty-one, and a
+    //  group's cost is mostly fixed -- profiles/r05x_sd_three_waves_ab.log)
+    // (chunks of 128 lines, drawn by ticket from two per wave on: round 4's 1024 was the round-robin form's optimum; under tickets,
+    //  one box, alternated -- profiles/r05u_chunk_taper_sweep.log -- 4 M lines: 1879-1905 M lines/s as one share per wave, 1990 in
+    //  chunks of 128, 1938-1967 at 256 / 512; 16 M lines: 2008-2013 at 1024, 2074-2082 at 128 .. 512; the long-tail corpus 1349 -> 1396.
+    //  From FOUR chunks per wave on: at 1 M lines -- 3.8 per wave -- one share per wave measured 1716-1743 M lines/s, tickets
+    //  1638-1663; at 2 M lines 1804-1844 against 1845-1873, at 16 M 1880 against 2075: profiles/r05v_policy_ab.log)
+    const fg::PlanFormat pf = v.pairs ? fg::PlanFormat().classes(2u).lds_tile(fg::sd2::extra_bytes).tile(12288u).chunk(128u).tickets_from(4u)
+                              : v.head ? fg::PlanFormat()
+                                       : fg::rfc5424_walk_format(avg_len);
+    // (pair-parallel walk: tiles of at most 36 KiB: with the two bitmaps and the walk's scratch -- 0.57 x the tile -- that is 58 KiB of LDS per wave)
+    const uint32_t max_tile = v.pairs ? 36864u : fg::kMaxTile;
+    const uint64_t plan_len = v.head ? (avg_len < fg::kHeadCap ? avg_len : fg::kHeadCap) : avg_len;
     const uint32_t sb = stash ? stash_blocks : 0u;
-    int prc;
-    if (sdx)
-        // (default tile from the same-box sweeps, profiles/r04g_sweep_*: 12 KiB -- eight waves per CU -- for whole lines and for heads)
-        // (tiles of at most 36 KiB: with the two bitmaps and the walk's scratch -- 0.57 x the tile -- that is 58 KiB of LDS per wave)
-        // (THREE waves per SIMD -- the compiler fits the whole-line instantiation into 168 registers without a spill under
-        //  __launch_bounds__(64, 3) -- with the 8 KiB tile and window that twelve waves per CU leave each other: 1.64-1.71 G lines/s
-        //  against 1.98-2.08 at 4-16 M lines, 9 KiB / eleven waves 1.71-1.78: fourteen lines to the group instead of twenty-one, and a
-        //  group's cost is mostly fixed -- profiles/r05x_sd_three_waves_ab.log)
-        // (chunks of 128 lines, drawn by ticket from two per wave on: round 4's 1024 was the round-robin form's optimum; under tickets,
-        //  one box, alternated -- profiles/r05u_chunk_taper_sweep.log -- 4 M lines: 1879-1905 M lines/s as one share per wave, 1990 in
-        //  chunks of 128, 1938-1967 at 256 / 512; 16 M lines: 2008-2013 at 1024, 2074-2082 at 128 .. 512; the long-tail corpus 1349 -> 1396.
-        //  From FOUR chunks per wave on: at 1 M lines -- 3.8 per wave -- one share per wave measured 1716-1743 M lines/s, tickets
-        //  1638-1663; at 2 M lines 1804-1844 against 1845-1873, at 16 M 1880 against 2075: profiles/r05v_policy_ab.log)
-        prc = head ? fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false, true, true>, n, plan_len, 0u, 36864u, sb, &p, *lo,
-                                     fg::PlanFormat().classes(2u).lds_tile(fg::sd2::extra_bytes).tile(12288u).chunk(128u).tickets_from(4u))
-                   : fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false, false, true>, n, plan_len, 0u, 36864u, sb, &p, *lo,
-                                     fg::PlanFormat().classes(2u).lds_tile(fg::sd2::extra_bytes).tile(12288u).chunk(128u).tickets_from(4u));
-    else
-        // (tickets from 20 chunks per wave on: the HBM-bound kernel pays for the first round's burst, fg_pipeline.hpp plan_launch)
-        // (short lines: a tile of at most kShortLineTile -- the whole-line kernel takes 209 VGPRs, two waves per SIMD, and with the
-        //  18 KiB tile that 64 lines of 254 B ask for, LDS -- 20.8 KiB per wave -- cut that to SEVEN waves per CU; 17 KiB is 19.7 KiB
-        //  of LDS, eight.  cfg2, one box, alternated: 15.13-15.73 G lines/s at 18 KiB, 15.89-16.91 at 17 KiB, 14.76-15.11 at 16 KiB,
-        //  where groups are cut short by bytes)
-        prc = head ? fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false, true>, n, plan_len, 0u, 57344u, sb, &p, *lo)
-                   : fg::plan_launch(fg::k_rfc5424<fg::kWindowKiB, false>, n, plan_len, 0u, 57344u, sb, &p, *lo,
-                                     fg::PlanFormat().tickets_from(20u).taper_levels(0u).tile(avg_len < 320u ? kShortLineTile : 0u));
-    if (prc) return -1;
     if (stash_blocks == 0) stash = nullptr;
-    dim3 grid(p.blocks), block(fg::kWave);
-    fg::FrameArgs fr{strip, line_bad};
-    fg::take_tickets(&fr, tk, p);
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, p.blocks, n, *lo, tt.shares);
-    unsigned long long* const no_prof = nullptr;
-#define FG_LAUNCH_5424(PROF_, HEAD_, SDX_, prof_ptr)                                                                                       \
-    hipLaunchKernelGGL((fg::k_rfc5424<fg::kWindowKiB, PROF_, HEAD_, SDX_>), grid, block, p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, \
-                       p.chunk, prof_ptr, stash, fr)
-#if defined(FG_PROF_BUILD)
-    if (fg::prof_requested()) {
-        fg::ProfRun pr;
-        if (!pr.begin(stream)) return -1;
-        if (sdx) {
-            if (head) FG_LAUNCH_5424(true, true, true, pr.d);
-            else FG_LAUNCH_5424(true, false, true, pr.d);
-        } else {
-            if (head) FG_LAUNCH_5424(true, true, false, pr.d);
-            else FG_LAUNCH_5424(true, false, false, pr.d);
-        }
-        pr.end(stream, head ? (sdx ? "rfc5424 (head, pairs)" : "rfc5424 (head)") : (sdx ? "rfc5424 (pairs)" : "rfc5424"), p);
-        return (int)hipGetLastError();
-    }
-#endif
-    if (sdx) {
-        if (head) FG_LAUNCH_5424(false, true, true, no_prof);
-        else FG_LAUNCH_5424(false, false, true, no_prof);
-    } else {
-        if (head) FG_LAUNCH_5424(false, true, false, no_prof);
-        else FG_LAUNCH_5424(false, false, false, no_prof);
-    }
-#undef FG_LAUNCH_5424
-    return (int)hipGetLastError();
+    return fg::plan_and_launch(ks, fg::DecodeCall{n, t, stream, fg::FrameArgs{strip, line_bad}, lo, tk}, plan_len, 0u, max_tile, sb, pf,
+                               [&](auto k, const fg::LaunchPlan& p, const fg::DevTables& tt, const fg::FrameArgs& fr, unsigned long long* prof) {
+                                   hipLaunchKernelGGL(k, dim3(p.blocks), dim3(fg::kWave), p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk,
+                                                      prof, stash, fr);
+                               });
 }
 
 // (register windows of exactly the tile's rows -- 16 KiB, 12 KiB for the pair-parallel kernel --: the 20 KiB of the plain kernels would
@@ -1210,24 +1168,12 @@ extern "C" int fg_launch_rfc5424(const uint8_t* d_bytes, const uint64_t* d_offse
 extern "C" int fg_launch_rfc5424_fused(const uint8_t* d_bytes, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom* g, hipStream_t stream,
                                        uint64_t* stash, uint32_t stash_blocks, uint32_t strip, int final_, uint64_t* d_offsets, uint64_t cap,
                                        uint8_t* scratch, const fg_launch_opts* lo, unsigned long long** d_total) {
-    if (nbytes == 0 || !g->ok) return -1;
     const bool sdx = g->variant == 1u;
-    const uint32_t base_lds = g->tile + 64u + (g->tile / 16u + 16u) * 2u * (sdx ? 2u : 1u) + (sdx ? fg::sd2::extra_bytes(g->tile) : 0u);
-    fg::FusedArgs fa{};
-    uint32_t lds = 0, blocks = 0;
+    const auto kernel = sdx ? fg::k_rfc5424_fused<12, true> : fg::k_rfc5424_fused<16, false>;
+    const uint32_t base_lds = fg::tile_lds(g->tile, sdx ? 2u : 1u) + (sdx ? fg::sd2::extra_bytes(g->tile) : 0u);
     if (stash_blocks == 0) stash = nullptr;
-    const uint32_t delim = strip == FG_FRAME_LINE ? 0x0Au : 0u;
-    const int prc = sdx ? fg::fused_prepare(fg::k_rfc5424_fused<12, true>, *g, base_lds, nbytes, final_, delim, d_offsets, cap, scratch,
-                                            stash ? stash_blocks : 0u, *lo, stream, &fa, &lds, &blocks)
-                        : fg::fused_prepare(fg::k_rfc5424_fused<16, false>, *g, base_lds, nbytes, final_, delim, d_offsets, cap, scratch,
-                                            stash ? stash_blocks : 0u, *lo, stream, &fa, &lds, &blocks);
-    if (prc) return -1;
-    fg::DevTables tt = *t;
-    tt.alloc_chunk = fg::entry_chunk(tt.ent_cap, blocks, nbytes / (g->S / g->L ? g->S / g->L : 1u) + 1u, *lo, tt.shares);
-    *d_total = fa.total;
-    if (sdx)
-        hipLaunchKernelGGL((fg::k_rfc5424_fused<12, true>), dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, stash, fa, strip);
-    else
-        hipLaunchKernelGGL((fg::k_rfc5424_fused<16, false>), dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, stash, fa, strip);
-    return (int)hipGetLastError();
+    return fg::launch_fused(kernel, fg::FusedCall{nbytes, t, g, stream, strip, final_, d_offsets, cap, scratch, lo, d_total}, base_lds, stash ? stash_blocks : 0u,
+                            [&](auto k, uint32_t blocks, uint32_t lds, const fg::DevTables& tt, const fg::FusedArgs& fa) {
+                                hipLaunchKernelGGL(k, dim3(blocks), dim3(fg::kWave), lds, stream, d_bytes, tt, g->tile, g->L, stash, fa, strip);
+                            });
 }

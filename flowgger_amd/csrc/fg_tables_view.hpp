@@ -28,7 +28,7 @@ struct DevTables {
     uint32_t* pending;
     uint32_t epoch;
     // entry slots a wave reserves from ent_used at a time (wv::wave_alloc): 0 = exactly what each request needs.  Set by the kernel
-    // launchers from the table, the grid and the lines of THIS launch (fg::entry_chunk, fg_pipeline.hpp).
+    // launchers from the table, the grid and the lines of THIS launch (fg::entry_chunk, fg_plan_policy.hpp).
     uint32_t alloc_chunk;
     // launches that reserve entry slots from this table (host side only: the sliced host paths decode one batch as many launches;
     // fg::entry_chunk divides the table's budget by it).  0 / 1 = this launch alone.

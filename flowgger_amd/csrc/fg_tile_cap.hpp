@@ -1,5 +1,5 @@
 // fg_tile_cap.hpp -- the one piece of LAUNCH GEOMETRY the host side picks itself (the RFC3164 decoder's and the encoders' LDS tile; the
-// streaming decoders plan theirs in fg_pipeline.hpp plan_launch).  Its own header so that a measured figure of those kernels
+// streaming decoders plan theirs in fg_plan_policy.hpp launch_geometry).  Its own header so that a measured figure of those kernels
 // (profiles/traffic.json, flowgger_amd/build.py source_hash) is keyed on this file and the kernel sources, not on the host pipelines.
 // Included by fg_ctx.hpp (needs fg_ctx and up()).
 #pragma once

@@ -28,8 +28,9 @@ WAVE = 64  # lines a group holds at most
 
 
 def planned_chunks(n, nbytes, cus, tile_cap=0, chunk_lines=0, static_chunks=False):
-    """(chunk, chunks, blocks) of the short-line RFC5424 launch at ONE wave per CU, restated from fg_launch_rfc5424 / plan_launch
-    (fg_pipeline.hpp) around the library's own fg::plan_chunks (tests/native/plan_host.cpp).  One wave per CU only: there the grid
+    """(chunk, chunks, blocks) of the short-line RFC5424 launch at ONE wave per CU, from the library's own host arithmetic
+    (fg_plan_policy.hpp through tests/native/plan_host.cpp): the launch's geometry as fg_launch_rfc5424 asks for it, the grid that
+    plan_launch (fg_pipeline.hpp) caps by the groups, then fg::plan_chunks.  One wave per CU only: there the grid
     does not depend on what the occupancy query answers.  The tests assert on it that a wave really runs the loop they are about --
     a batch this size that the plan cut into one group per wave would pass without ever reaching the prefetch."""
     deps = [PLAN_SRC, ROOT / "flowgger_amd/csrc/fg_plan_policy.hpp", ROOT / "include/fg_hip.h"]
@@ -38,16 +39,16 @@ def planned_chunks(n, nbytes, cus, tile_cap=0, chunk_lines=0, static_chunks=Fals
     lib = C.CDLL(str(PLAN_LIB))
     u64, u32 = C.c_uint64, C.c_uint32
     lib.fgp_plan_chunks.argtypes = [u64, u64, u32, u64, u64, u32, u32, u32, u32, C.POINTER(u64)]
+    lib.fgp_rfc5424_walk_geometry.argtypes = [u64, u64, u32, u32, C.POINTER(u64)]
+    lib.fgp_pick_variant.argtypes = [u64, u32]
     avg = (nbytes + n - 1) // n
-    assert avg < 320  # the short-line whole-line kernel: k_rfc5424<20, false, false, false>
-    tile = min(max((WAVE * avg * 17 // 16 + 256 + 1023) // 1024 * 1024, 4096), 17408)
-    if tile_cap:
-        tile = (tile_cap + 1023) // 1024 * 1024
-    groups = max((n + WAVE - 1) // WAVE, (n * avg + tile - 1) // tile)
-    full = 256 if tile // avg >= WAVE else 512
+    assert lib.fgp_pick_variant(avg, 0) == 0  # the short-line whole-line kernel: k_rfc5424<20, false, false, false>
+    geo = (u64 * 8)()
+    lib.fgp_rfc5424_walk_geometry(n, avg, tile_cap, 0, geo)
+    lines, groups, full, g, ticket_from, taper = (int(geo[k]) for k in (0, 3, 4, 5, 6, 7))
+    assert lines == WAVE
     out = (u64 * 7)()
-    lib.fgp_plan_chunks(n, min(cus, groups), WAVE, tile * 16 // (avg * 17), full, 20, L.FG_LO_STATIC_CHUNKS if static_chunks else 0,
-                        chunk_lines, 0, out)
+    lib.fgp_plan_chunks(n, min(cus, groups), lines, g, full, ticket_from, L.FG_LO_STATIC_CHUNKS if static_chunks else 0, chunk_lines, taper, out)
     return int(out[0]), int(out[1]), int(out[2])
 
 

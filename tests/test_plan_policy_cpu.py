@@ -30,6 +30,11 @@ def plan():
     lib.fgp_entry_chunk_shared.restype = u32
     lib_holder.append(lib)
     lib.fgp_chunk_range.argtypes = [u64, u64, u32, u32, u32, u64, C.POINTER(u64)]
+    lib.fgp_launch_geometry.argtypes = [u64, u64, u32, u32, u32, u32, u32, u32, u32, u32, C.c_int, C.POINTER(u64)]
+    lib.fgp_rfc5424_walk_geometry.argtypes = [u64, u64, u32, u32, C.POINTER(u64)]
+    lib.fgp_pick_variant.argtypes = [u64, u32]
+    lib.fgp_pick_variant.restype = u32
+    lib.fgp_gelf_const_3k.argtypes = [u64, u32, u32]
 
     def chunks(n, blocks, L_=64, g=64, full=256, ticket_from=2, flags=0, chunk_lines=0, taper=False, levels=1):
         out = (u64 * 7)()
@@ -176,3 +181,56 @@ def test_slices_that_share_a_table_never_strand_more_than_a_quarter_of_it(plan):
                     assert c == 0 or c >= 256
     # ... and a launch alone keeps the round-5 rule
     assert shared(400_000_000, 2048, 125_000_000, 0, 1) == 4096
+
+
+def geometry(n, avg, max_tile=57344, tile_cap=0, lines_per_group=0, max_lines=64, classes=1, default_tile=0, default_chunk=0, per_line=False,
+             extra_lds=0):
+    """(L, tile, lds) of fg::launch_geometry for a format given by plain numbers"""
+    out = (u64 * 6)()
+    lib_holder[0].fgp_launch_geometry(n, avg, extra_lds, max_tile, tile_cap, lines_per_group, max_lines, classes, default_tile, default_chunk,
+                                      int(per_line), out)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def test_launch_geometry_by_hand(plan):
+    """fg::launch_geometry: every figure below is worked out by hand from the rule (the average group + 6.25 % + 256 B, rounded up to a
+    KiB, in 4 KiB .. max_tile; LDS = tile + 64 + (tile / 16 + 16) * 2 per class bitmap)."""
+    out = (u64 * 8)()
+    lib_holder[0].fgp_rfc5424_walk_geometry(1_000_000, 254, 0, 0, out)
+    # the headline corpus: 64 x 254 x 17 / 16 + 256 = 17 528 -> 18 KiB, capped at the short-line tile: 17 408 + 64 + 1104 x 2
+    assert tuple(int(x) for x in out[:3]) == (64, 17408, 19680) and int(out[6]) == 20 and int(out[7]) == 0
+    assert lib_holder[0].fgp_short_line_tile() == 17408
+    assert geometry(1_000_000, 254) == (64, 18432, 18432 + 64 + (18432 // 16 + 16) * 2)            # ... without default_tile
+    assert geometry(1_000_000, 254, default_tile=17408) == (64, 17408, 19680)
+    # GELF, eight lines to the group: 8 x 307 x 17 / 16 + 256 = 2865 -> 3 KiB -> the 4 KiB floor; per-line arrays: no widening
+    assert geometry(1_000_000, 307, max_tile=40960, max_lines=8, classes=4, per_line=True)[:2] == (8, 4096)
+    # fg_launch_opts.tile_cap rounds up to a KiB and wins over default_tile (and is ignored outside 1 KiB .. max_tile)
+    assert geometry(1_000_000, 254, tile_cap=20000, default_tile=17408)[:2] == (64, 20480)
+    assert geometry(1_000_000, 254, tile_cap=1000, default_tile=17408)[:2] == (64, 17408)
+    assert geometry(1_000_000, 254, tile_cap=57345, default_tile=17408)[:2] == (64, 17408)
+    # 2000-byte lines: 8 to the window (8 x 2000 x 17 / 16 + 256 = 17 256 -> 17 KiB); a format without per-line arrays takes the full
+    # wave and 18 KiB instead -- unless the caller names the lines per group
+    assert geometry(1_000_000, 2000)[:2] == (64, 18432)
+    assert geometry(1_000_000, 2000, lines_per_group=8)[:2] == (8, 17408)
+    assert geometry(1_000_000, 2000, per_line=True)[:2] == (8, 17408)
+
+
+def test_variant_choice_at_every_boundary(plan):
+    pick = lib_holder[0].fgp_pick_variant
+    HEAD, PAIRS = 1, 2
+    assert [pick(a, 0) for a in (319, 320, 767, 768)] == [0, PAIRS, PAIRS, HEAD | PAIRS]
+    for a in (319, 320):
+        assert pick(a, L.FG_LO_SD_PAIRS) == PAIRS and pick(a, L.FG_LO_SD_WALK) == 0
+        assert pick(a, L.FG_LO_SD_PAIRS | L.FG_LO_SD_WALK) == PAIRS, "the forcing flag wins"
+    for a in (767, 768):
+        assert pick(a, L.FG_LO_FORCE_HEAD) & HEAD and not pick(a, L.FG_LO_NO_HEAD) & HEAD
+        assert pick(a, L.FG_LO_FORCE_HEAD | L.FG_LO_NO_HEAD) & HEAD, "the forcing flag wins"
+        assert pick(a, L.FG_LO_FORCE_HEAD) & PAIRS and pick(a, L.FG_LO_NO_HEAD) & PAIRS, "the two choices are independent"
+    assert pick(100, L.FG_LO_FORCE_HEAD | L.FG_LO_SD_PAIRS) == HEAD | PAIRS and pick(5000, L.FG_LO_NO_HEAD | L.FG_LO_SD_WALK) == 0
+
+
+def test_gelf_constant_geometry_predicate(plan):
+    const3k = lib_holder[0].fgp_gelf_const_3k
+    # 8 x avg x 17 / 16 + 256 <= 3072: 136 x 331 / 16 = 2813, 136 x 332 / 16 = 2822 against 2816
+    assert const3k(331, 0, 0) == 1 and const3k(332, 0, 0) == 0
+    assert const3k(331, 3072, 0) == 0 and const3k(331, 0, L.FG_LO_GELF_GENERIC) == 0
