@@ -160,7 +160,8 @@ extern "C" int fg_launch_merge_device(const fg_tables* parts, uint32_t g, const 
         if (b > cap) b = cap;
         return (uint32_t)(b ? b : 1u);
     };
-    // (rows no index names keep whatever the table held: the counts of such rows must not reach the scan)
+    // (rows no index names keep whatever the table held in their copied columns: the counts of such rows must not reach the scan.  They
+    //  come back with ent_count 0 -- and ent_first 0, which k_merge_entries writes for every row without entries)
     (void)hipMemsetAsync(out->ent_count, 0, n * 4u, stream);
     hipLaunchKernelGGL(fg::k_merge_rows, dim3(blocks_for(max_rows), g), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(fg::k_merge_block_sums, dim3((uint32_t)nb), dim3(64), 0, stream, a);

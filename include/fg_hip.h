@@ -771,7 +771,12 @@ int fg_gather_size(const fg_tables* parts, uint32_t g, uint64_t* n_rows, uint64_
  * decoders' waves reserved but never used -- they lie between the slices of a decoder's own table -- do not cross the link.
  * Asynchronous on `stream`; the parts' entry counters are read on the device.  out->n must be the sum of the
  * parts' rows and out->ent_cap at least the sum of their ent_cap (checked); out->ent_used receives the merged entry count;
- * d_src_part (device, may be NULL) as src_part of fg_merge_tables.  The indices are the caller's contract (every position once). */
+ * d_src_part (device, may be NULL) as src_part of fg_merge_tables.  The indices are the caller's contract (every position once) and
+ * are not checked on the device.  What the kernels do with indices outside it (tests/merge_model.py): an index >= out->n is skipped;
+ * a position NO index names comes back with ent_count = 0 AND ent_first = 0 and owns no entries, its other eight columns and its
+ * d_src_part byte keep what they held; a row whose slice does not lie inside [0, min(*ent_used, ent_cap)) of its part (a row of a
+ * table that overflowed) keeps its columns and owns no entries; nothing is stored at or behind out->ent_cap, whatever ent_used
+ * reports.  A position named TWICE is undefined (two rows race for one set of columns; the entry copy may read outside a part). */
 int fg_merge_tables_device(fg_ctx* ctx, const fg_tables* parts, uint32_t g, const uint64_t* const* d_index, const fg_tables* out,
                            uint8_t* d_src_part, void* stream);
 int fg_gather_tables(const fg_tables* parts, uint32_t g, fg_tables* out);

@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from flowgger_amd.tables import DeviceTables
+from flowgger_amd.tables import DeviceTables, HostTables
 
 
 def host_path_blob(dec, data, offsets):
@@ -48,3 +48,17 @@ def first_diff(blob_a, offs_a, blob_b, offs_b, lines=None):
 def assert_same(blob, offs, oblob, ooffs, lines=None):
     same = np.array_equal(offs, ooffs) and np.array_equal(blob, oblob)
     assert same, first_diff(blob, offs, oblob, ooffs, lines)
+
+
+def rows_of_part(got: HostTables, rows: np.ndarray) -> HostTables:
+    """The rows of one sub-batch taken back out of a merged table at their arrival positions (the merged entry columns whole:
+    ent_first points into them)."""
+    arrays = {}
+    for name, a in got.a.items():
+        if name in ("meta", "ts", "ent_first", "ent_count"):
+            arrays[name] = np.ascontiguousarray(a[rows])
+        elif name in ("hostname", "appname", "procid", "msgid", "msg", "full_msg"):
+            arrays[name] = np.ascontiguousarray(a.reshape(-1, 2)[rows]).reshape(-1)
+        else:
+            arrays[name] = a  # the merged entry columns, whole: ent_first points into them
+    return HostTables(len(rows), got.ent_cap, arrays)

@@ -13,7 +13,7 @@ import pytest
 
 from flowgger_amd import GelfDecoder, LTSVDecoder, RFC3164Decoder, RFC5424Decoder, synth
 from flowgger_amd import _lib as L
-from gpu_util import assert_same, device_path
+from gpu_util import assert_same, device_path, rows_of_part
 
 pytestmark = pytest.mark.gpu
 
@@ -168,7 +168,6 @@ def test_device_merge_equals_the_oracle_in_arrival_order(oracle):
     serialise to the canonical Records the oracle decodes from that sub-batch's lines, in order."""
     import torch
     from flowgger_amd import shard
-    from flowgger_amd.tables import HostTables
 
     n = 60_000
     tag, (la, ia), (lb, ib) = synth.mixed_cfg5(n)
@@ -191,15 +190,7 @@ def test_device_merge_equals_the_oracle_in_arrival_order(oracle):
         data, offsets, lines = packs[k]
         rows = ix.astype(np.int64)
         assert np.array_equal(np.flatnonzero(src == k), np.sort(rows))
-        arrays = {}
-        for name, a in got.a.items():
-            if name in ("meta", "ts", "ent_first", "ent_count"):
-                arrays[name] = np.ascontiguousarray(a[rows])
-            elif name in ("hostname", "appname", "procid", "msgid", "msg", "full_msg"):
-                arrays[name] = np.ascontiguousarray(a.reshape(-1, 2)[rows]).reshape(-1)
-            else:
-                arrays[name] = a  # the merged entry columns, whole: ent_first points into them
-        sub = HostTables(len(rows), got.ent_cap, arrays)
+        sub = rows_of_part(got, rows)
         blob, offs = sub.serialize(dec.fmt, data, offsets, cfg=dec._cfg)
         oblob, ooffs = oracle.decode_batch(dec.fmt, data, offsets, cfg)
         assert_same(blob, offs, oblob, ooffs, lines)
