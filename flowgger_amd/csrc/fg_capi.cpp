@@ -492,6 +492,48 @@ int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
     return FG_OK;
 }
 
+// ... for the chunks of n_segs connections at once (a SyslenSplitter per connection: input/tcp/tcp_input.rs:39-47)
+int fg_frame_syslen_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs,
+                                 uint8_t* d_packed, uint64_t* d_offsets, uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames,
+                                 uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop, uint64_t* n_frames,
+                                 uint64_t* payload_bytes, void* stream) {
+    if (!ctx || !d_packed || !d_offsets || !n_frames || !payload_bytes || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (cap_frames && (!d_frame_starts || !d_bad_utf8)) return FG_ERR_ARG;
+    if (n_segs ? (!d_seg_starts || !d_seg_first || !d_seg_consumed || !d_seg_stop) : nbytes != 0) return FG_ERR_ARG;
+    if (((uintptr_t)d_bytes & 15u) != 0 || ((uintptr_t)d_packed & 15u) != 0) return FG_ERR_ARG;
+    *n_frames = 0;
+    *payload_bytes = 0;
+    if (!fg_launch_syslen_multi || !fg_syslen_multi_scratch_bytes || !fg_syslen_max_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    if (nbytes > fg_syslen_max_bytes()) return FG_ERR_UNSUPPORTED;  // (the scratch keeps positions as 32-bit words)
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (nbytes == 0) {  // no frames: every segment is empty and CLEAN
+        FG_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s));
+        if (n_segs) {
+            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
+            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
+            FG_HIP(ctx, hipMemsetAsync(d_seg_stop, FG_SYSLEN_CLEAN, n_segs, s));
+        }
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    if (n_segs > (1ull << 24)) return FG_ERR_UNSUPPORTED;  // (node numbers are 32-bit words)
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_syslen_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
+    uint32_t* d_hdr = nullptr;
+    FG_LAUNCH(ctx, fg_launch_syslen_multi(d_bytes, nbytes, d_seg_starts, n_segs, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8,
+                                           cap_frames, d_seg_first, d_seg_consumed, d_seg_stop, &d_hdr, s));
+    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (hdr[0] != 0 || hdr[5] != 1) return FG_ERR_UNSUPPORTED;  // declined: more speculative chains than the kernels track
+    *n_frames = hdr[2];
+    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
+    *payload_bytes = hdr[4];
+    ctx->last_syslen_payload = hdr[4];
+    return FG_OK;
+}
+
 // replaces the walk of capnp::serialize::read_message over the segment tables in CapnpSplitter::run (splitter/capnp_splitter.rs:24-46)
 int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint64_t* d_offsets, uint64_t cap_frames,
                           uint64_t* n_frames, uint64_t* consumed, int* stop_reason, void* stream) {

@@ -94,6 +94,15 @@ extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t n_seg
 extern "C" int fg_launch_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, const uint64_t* d_seg_starts, const uint8_t* d_seg_final,
                                      uint64_t n_segs, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first,
                                      uint64_t* d_seg_consumed, uint64_t** d_result, hipStream_t stream, int classic) __attribute__((weak));
+// the segmented octet-counted framer (fg_syslen_multi.hip): *d_hdr_out = its result words in device memory (fg::syslen H_DECLINE,
+// H_NFRAMES, H_TOTAL, H_DONE).  (WEAK references, as fg_launch_syslen above: without the kernels fg_frame_syslen_multi_device answers
+// FG_ERR_UNSUPPORTED and fg_frame_decode_syslen_multi_batch takes its host hop.  The product library always has them: build.py checks
+// the link.)
+extern "C" uint64_t fg_syslen_multi_scratch_bytes(uint64_t nbytes, uint64_t n_segs) __attribute__((weak));
+extern "C" int fg_launch_syslen_multi(const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs, uint8_t* scratch,
+                                      uint8_t* d_packed, uint64_t* d_offsets, uint64_t* d_starts, uint8_t* d_bad, uint64_t cap,
+                                      uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop, uint32_t** d_hdr_out,
+                                      hipStream_t stream) __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,

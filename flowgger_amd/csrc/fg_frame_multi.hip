@@ -164,6 +164,12 @@ extern "C" int fg_launch_frame_classic_scan(const uint8_t* d_bytes, uint64_t nby
 extern "C" int fg_launch_frame_classic_emit(uint64_t nbytes, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_bad, uint64_t cap,
                                             uint64_t** d_total_out, hipStream_t stream);
 
+// k_seg_clamp for another unit (fg_syslen_multi.hip): c has n_segs + 1 entries
+extern "C" int fg_launch_seg_clamp(const uint64_t* d_seg_starts, uint64_t n_segs, uint64_t nbytes, uint64_t* d_c, hipStream_t stream) {
+    hipLaunchKernelGGL(fg::k_seg_clamp, dim3(1), dim3(1024), 0, stream, d_seg_starts, n_segs, nbytes, d_c);
+    return (int)hipGetLastError();
+}
+
 // scratch: the framing's own (fg_frame_scratch_bytes), then the clamped segment starts (n_segs + 1 u64), then the two result words
 static inline uint64_t multi_frame_part(uint64_t nbytes) { return (fg_frame_scratch_bytes(nbytes) + 255u) & ~255ull; }
 extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t n_segs) {

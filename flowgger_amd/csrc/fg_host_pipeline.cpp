@@ -1154,6 +1154,129 @@ extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framin
     return rc;
 }
 
+// The OCTET-COUNTED chunks of many connections in one buffer (a SyslenSplitter per connection, syslen_splitter.rs:42-57): upload once,
+// frame + pack every segment as its own stream on the device, decode the packed payloads (FG_FRAME_NONE, with the UTF-8 flags).  When the
+// device framer declines (fg_frame_syslen_multi_device: FG_ERR_UNSUPPORTED) or a segment meets a prefix beyond the device parser's
+// bound, the whole buffer is hopped on the host, segment by segment, and the packed batch is uploaded: the same results either way
+// (the two simplifications of syslen_stage hold here too).
+extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
+                                                  uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts,
+                                                  const uint64_t** out_seg_first, const uint64_t** out_seg_consumed,
+                                                  const uint8_t** out_seg_stop, uint64_t* n_frames) {
+    if (!ctx || !out || !out_frame_starts || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_frames || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF && fmt != FG_RFC3164) return FG_ERR_ARG;
+    if (n_segs && !seg_starts) return FG_ERR_ARG;
+    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
+    for (uint64_t k = 0; k < n_segs; ++k)
+        if (seg_starts[k] > seg_starts[k + 1]) return FG_ERR_ARG;
+    *n_frames = 0;
+    *out = fg_tables{};
+    *out_frame_starts = nullptr;
+    *out_seg_first = nullptr;
+    *out_seg_consumed = nullptr;
+    *out_seg_stop = nullptr;
+    ctx->last_host_path = 0;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    // seg_starts | seg_first | seg_consumed | seg_stop on the device; seg_first | seg_consumed | seg_stop | frame starts in the pinned mirror
+    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_stop = o_cons + up(n_segs * 8 + 8, 256);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_stop + up(n_segs + 1, 256))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
+    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
+    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
+    uint8_t* const d_stop = ctx->d_ms + o_stop;
+    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+    auto ensure = [&](uint64_t cap) -> int {
+        int r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_sl_starts, &ctx->d_sl_starts_cap, (cap + 2) * 8)) != FG_OK) return r;
+        return grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1);
+    };
+    // 1. frame + pack: capacity from the frames per byte this ctx last saw, exact on retry (as syslen_stage)
+    uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 1024, n = 0, payload = 0;
+    for (;;) {
+        if ((rc = ensure(cap)) != FG_OK) return rc;
+        rc = fg_frame_syslen_multi_device(ctx, ctx->d_bytes, nbytes, d_starts, n_segs, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts, ctx->d_bad, cap,
+                                          d_first, d_cons, d_stop, &n, &payload, FG_STREAM_OWN);
+        if (rc != FG_ERR_ENT_OVERFLOW) break;
+        cap = n + 16;
+    }
+    if (rc != FG_OK && rc != FG_ERR_UNSUPPORTED) return rc;
+    const uint64_t h_cons = o_first, h_stop = h_cons + up(n_segs * 8 + 8, 256), h_fs = h_stop + up(n_segs + 1, 256);
+    auto mirror = [&](uint64_t frames) -> int { return grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_fs + up((frames + 1) * 8, 256)); };
+    bool device = rc == FG_OK;
+    if (device) {
+        if ((rc = mirror(n)) != FG_OK) return rc;
+        uint8_t* const h = ctx->h_ms;
+        if (n_segs) {
+            FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
+            FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
+            FG_HIP(ctx, hipMemcpyAsync(h + h_stop, d_stop, n_segs, hipMemcpyDeviceToHost, s));
+        } else {
+            memset(h, 0, 8);
+        }
+        if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_fs, ctx->d_sl_starts, n * 8, hipMemcpyDeviceToHost, s));
+        // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        for (uint64_t k = 0; k < n_segs && device; ++k) device = h[h_stop + k] != FG_SYSLEN_LONG_PREFIX;
+    }
+    if (!device) {
+        // the host hop (what syslen_stage does for one chunk), segment by segment: prefixes of any length
+        namespace sl = fg::syslen;
+        std::vector<uint64_t> starts, offs{0}, first{0}, cons;
+        std::vector<uint8_t> packed, bad, stop;
+        for (uint64_t k = 0; k < n_segs; ++k) {
+            const uint64_t at = seg_starts[k];
+            const uint8_t* const seg = bytes + at;
+            uint64_t consumed = 0;
+            stop.push_back((uint8_t)sl::host_walk(seg, seg_starts[k + 1] - at, ~0ull, &consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
+                const uint8_t* b = seg + pos + plen;
+                bool err = false;
+                for (uint64_t i = 0; i <= len && !err; ++i)
+                    err = sl::utf8_err_at(i < len ? b[i] : 0u, i >= 1 ? b[i - 1] : 0u, i >= 2 ? b[i - 2] : 0u, i >= 3 ? b[i - 3] : 0u);
+                starts.push_back(at + pos);
+                packed.insert(packed.end(), b, b + len);
+                offs.push_back(packed.size());
+                bad.push_back(err ? 1 : 0);
+            }));
+            cons.push_back(consumed);
+            first.push_back(starts.size());
+        }
+        n = starts.size();
+        payload = packed.size();
+        if ((rc = ensure(n)) != FG_OK || (rc = mirror(n)) != FG_OK) return rc;
+        uint8_t* const h = ctx->h_ms;
+        memcpy(h, first.data(), (n_segs + 1) * 8);
+        if (n_segs) memcpy(h + h_cons, cons.data(), n_segs * 8);
+        if (n_segs) memcpy(h + h_stop, stop.data(), n_segs);
+        if (n) memcpy(h + h_fs, starts.data(), n * 8);
+        if (payload) FG_HIP(ctx, hipMemcpyAsync(ctx->d_sl_packed, packed.data(), payload, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, bad.data(), n, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));  // (the vectors go out of scope)
+    }
+    if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
+    uint8_t* const h = ctx->h_ms;
+    *n_frames = n;
+    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
+    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
+    *out_seg_stop = h + h_stop;
+    *out_frame_starts = reinterpret_cast<const uint64_t*>(h + h_fs);
+    ctx->last_host_path = device ? FG_PATH_FRAME_SYSLEN_MULTI_DEVICE : FG_PATH_FRAME_SYSLEN_MULTI_HOST;
+    if (n == 0) return FG_OK;
+    // 2. decode the packed payloads (a flagged payload -> FG_ST_BAD_UTF8, not decoded)
+    rc = decode_stage_to_host(ctx, fmt, FG_FRAME_NONE, payload, n, ctx->d_bad, ctx->d_sl_packed, out);
+    if (rc != FG_OK) ctx->last_host_path = 0;
+    return rc;
+}
+
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB
 // on the ctx's two streams, so that the upload of slice k+1 and the (2-3x larger) download of slice k's messages share the
 // full-duplex link, and the kernels hide behind both.  The host only waits for one small number per slice (its encoded size:

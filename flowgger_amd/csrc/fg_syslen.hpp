@@ -95,8 +95,23 @@ FG_WV void load16u(const uint8_t* p, uint32_t q[4]) { __builtin_memcpy(q, p, 16)
 constexpr uint32_t kLdsBytes = (kTile + kLook) / 4u + 8u;  // the tile, its look-ahead, padding for Bytes::byte
 constexpr uint32_t kLdsWords = kLdsBytes + kRawExits + 4u;
 
+// How far the frame that starts at a position may reach.  One stream: the chunk's end, wherever the position is.  (The segmented
+// framer, fg_syslen_multi.hpp, instantiates the stages below with the end of the SEGMENT that holds the position, and gives the
+// segments' starts nodes of their own instead of the inbox entry of position 0.)
+struct Whole {
+    static constexpr bool kSegmented = false;
+    uint64_t nbytes;
+    struct Tile {
+        uint64_t lim;
+        FG_WV uint64_t limit(uint64_t) const { return lim; }
+    };
+    FG_WV Tile tile(uint64_t) const { return Tile{nbytes}; }
+    FG_WV uint64_t limit(uint64_t) const { return nbytes; }
+};
+
 // ---- 1: resolve + route.  All 64 lanes; `lds` = kLdsWords dwords. ------------------------------------------------------------
-FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+template <class Span>
+FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds, const Span& span) {
     uint32_t* w = lds;
     uint32_t* raw = lds + kLdsBytes;
     uint32_t* ctr = raw + kRawExits;
@@ -112,18 +127,21 @@ FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, c
     wv::sync();
     const wv::Bytes tb{w};
     auto get = [&](uint64_t p) { return tb.byte((uint32_t)(p - base)); };
+    const typename Span::Tile here = span.tile(base);
     // the candidates that leave the tile.  Positions are dealt out INTERLEAVED (lane l looks at 64 j + l): the 64 lanes of a step read
     // 16 consecutive dwords of the tile, four lanes each -- no LDS bank is asked twice
     for (uint32_t j = 0; j < kTile / wv::kLanes; ++j) {
         const uint32_t i = j * wv::kLanes + l;
         const uint32_t c = tb.byte(i);
         if (base + i >= nbytes || !(c == '+' || (c >= '0' && c <= '9'))) continue;
-        const Prefix pr = parse_prefix(get, base + i, nbytes);
+        const uint64_t lim = here.limit(base + i);
+        const Prefix pr = parse_prefix(get, base + i, lim);
         if (pr.st != ST_VALID || (uint64_t)i + pr.plen + pr.len < kTile) continue;
+        if (Span::kSegmented && base + i + pr.plen + pr.len == lim) continue;  // (ends on its segment's end: the end of a chain, no exit)
         const uint32_t k = wv::lds_add(&ctr[0], 1u);
         if (k < kRawExits) raw[k] = (uint32_t)(base + i + pr.plen + pr.len);
     }
-    if (tile == 0 && l == 0) {  // the stream's own start
+    if (!Span::kSegmented && tile == 0 && l == 0) {  // the stream's own start
         sc.inbox_pos[0] = 0u;
         g_add32(&sc.inbox_cnt[0], 1u);
     }
@@ -141,7 +159,7 @@ FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, c
         if (!uniq) continue;
         if (wv::lds_add(&ctr[1], 1u) >= kExits) continue;
         // (one global read: an exit that does not land on a candidate ends there -- the node that takes it finds out by itself)
-        if (x >= nbytes || parse_prefix(gget, x, nbytes).st != ST_VALID) continue;
+        if (x >= nbytes || parse_prefix(gget, x, span.limit(x)).st != ST_VALID) continue;
         const uint32_t t2 = x / kTile;
         const uint32_t slot = g_add32(&sc.inbox_cnt[t2], 1u);
         if (slot < kInbox) sc.inbox_pos[(uint64_t)t2 * kInbox + slot] = x;
@@ -149,6 +167,9 @@ FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, c
     }
     wv::sync();
     if (l == 0 && ctr[1] > kExits) g_or32(&sc.hdr[H_DECLINE], 1u);
+}
+FG_WV void resolve_route(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+    resolve_route(bytes, nbytes, tile, sc, lds, Whole{nbytes});
 }
 
 // the lowest slot of tile t2's inbox that holds position x (duplicates -- two tiles with the same exit -- collapse onto it)
@@ -160,33 +181,29 @@ FG_WV uint32_t inbox_find(const Scratch& sc, uint32_t t2, uint32_t x) {
     return kNil;
 }
 
-// ---- 2: one lane per inbox entry (slot = lane < kInbox; no cross-lane primitive) ---------------------------------------------
-FG_WV void walk_node(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, uint32_t slot, const Scratch& sc) {
-    uint32_t n = sc.inbox_cnt[tile];
-    if (n > kInbox) n = kInbox;
-    if (slot >= n) return;
-    const uint32_t u = tile * kInbox + slot;
-    const uint32_t x = sc.inbox_pos[u];
+// ---- 2: one lane per node (no cross-lane primitive) ----------------------------------------------------------------------------
+// the chain from x through its tile, `lim` = where the bytes x may use end; the node u it makes.  root: u starts a true chain.
+FG_WV void walk_chain(const uint8_t* bytes, uint64_t lim, uint32_t tile, uint32_t u, uint32_t x, bool live, bool root, const Scratch& sc) {
     uint32_t next = kNil, term = kNil, frames = 0, pbytes = 0;
     uint64_t pos = x;
-    if (inbox_find(sc, tile, x) == u) {  // (a duplicate is nobody's successor: it stays an empty node)
+    if (live) {
         const uint64_t end = (uint64_t)(tile + 1u) * kTile;
         auto gget = [&](uint64_t p) { return (uint32_t)bytes[p]; };
         for (uint32_t hop = 0; hop <= kTile / 2u && pos < end; ++hop) {  // (a frame is two bytes at least)
-            const Prefix pr = parse_prefix(gget, pos, nbytes);
+            const Prefix pr = parse_prefix(gget, pos, lim);
             if (pr.st != ST_VALID) { term = pr.st; break; }
             ++frames;
             pbytes += (uint32_t)pr.len;
             pos += pr.plen + pr.len;
         }
         if (term == kNil) {
-            if (pos >= nbytes) term = ST_CLEAN;
+            if (pos >= lim) term = ST_CLEAN;
             else {
                 next = inbox_find(sc, (uint32_t)(pos / kTile), (uint32_t)pos);
-                if (next == kNil) term = parse_prefix(gget, pos, nbytes).st;  // (never ST_VALID unless an inbox ran over: declined then)
+                if (next == kNil) term = parse_prefix(gget, pos, lim).st;  // (never ST_VALID unless an inbox ran over: declined then)
             }
         }
-        if (u == 0) { sc.mk_stamp[0] = 1u; sc.mk_f[0] = 0u; sc.mk_b[0] = 0u; }
+        if (root) { sc.mk_stamp[u] = 1u; sc.mk_f[u] = 0u; sc.mk_b[u] = 0u; }
     }
     sc.nd_exit[u] = (uint32_t)pos;
     sc.nd_term[u] = term;
@@ -194,13 +211,20 @@ FG_WV void walk_node(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, uint3
     sc.jf[0][u] = frames;
     sc.jb[0][u] = pbytes;
 }
-
-// ---- 3: round r = 1 .. rounds of the ranking, one thread per node -------------------------------------------------------------
-FG_WV void jump_round(uint32_t tile, uint32_t slot, uint32_t r, const Scratch& sc) {
+// one lane per inbox entry (slot = lane < kInbox)
+FG_WV void walk_node(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, uint32_t slot, const Scratch& sc) {
     uint32_t n = sc.inbox_cnt[tile];
     if (n > kInbox) n = kInbox;
     if (slot >= n) return;
-    const uint32_t u = tile * kInbox + slot, a = (r - 1u) & 1u, b = r & 1u;
+    const uint32_t u = tile * kInbox + slot;
+    const uint32_t x = sc.inbox_pos[u];
+    // (a duplicate is nobody's successor: it stays an empty node)
+    walk_chain(bytes, nbytes, tile, u, x, inbox_find(sc, tile, x) == u, u == 0, sc);
+}
+
+// ---- 3: round r = 1 .. rounds of the ranking, one thread per node -------------------------------------------------------------
+FG_WV void jump_node(uint32_t u, uint32_t r, const Scratch& sc) {
+    const uint32_t a = (r - 1u) & 1u, b = r & 1u;
     const uint32_t nx = sc.jn[a][u], f = sc.jf[a][u], pb = sc.jb[a][u];
     const uint32_t stamp = sc.mk_stamp[u];
     if (nx == kNil) {
@@ -215,6 +239,11 @@ FG_WV void jump_round(uint32_t tile, uint32_t slot, uint32_t r, const Scratch& s
     sc.jn[b][u] = sc.jn[a][nx];
     sc.jf[b][u] = f + sc.jf[a][nx];
     sc.jb[b][u] = pb + sc.jb[a][nx];
+}
+FG_WV void jump_round(uint32_t tile, uint32_t slot, uint32_t r, const Scratch& sc) {
+    uint32_t n = sc.inbox_cnt[tile];
+    if (n > kInbox) n = kInbox;
+    if (slot < n) jump_node(tile * kInbox + slot, r, sc);
 }
 
 // ---- 4: emit + pack.  All 64 lanes; `lds` = 4 * 64 + 4 dwords. ------------------------------------------------------------------
@@ -259,23 +288,16 @@ FG_WV bool copy_check(const uint8_t* src, uint8_t* dst, uint32_t len) {
     return bad;
 }
 
-FG_WV void emit_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint8_t* packed, uint64_t* offsets,
-                     uint64_t* starts, uint8_t* bad, uint64_t cap, uint32_t* lds) {
+// the frames of one chain from `pos` to the end of its tile (`end`) or of the chain: starts, offsets, payloads, flags from frame index
+// `frame` and packed offset `pb` on.  lim as walk_chain.  Wave-uniform arguments.
+FG_WV void emit_chain(const uint8_t* bytes, uint64_t lim, uint64_t end, uint64_t pos, uint32_t frame, uint32_t pb, uint8_t* packed,
+                      uint64_t* offsets, uint64_t* starts, uint8_t* bad, uint64_t cap, uint32_t* lds) {
     uint32_t* f_pos = lds;  // a strip of up to 64 frames: start, prefix length, payload length, packed offset
     uint32_t* f_plen = lds + 64;
     uint32_t* f_len = lds + 128;
     uint32_t* f_dst = lds + 192;
     uint32_t* st = lds + 256;  // [0] frames in the strip, [1] where the walk stands, [2] ST_* that ended it or kNil
     const uint32_t l = wv::lane();
-    if (sc.hdr[H_DECLINE] != 0u) return;  // (nothing is valid: write nothing)
-    uint32_t n = sc.inbox_cnt[tile];
-    if (n > kInbox) n = kInbox;
-    const uint64_t mine = wv::ballot(l < n && sc.mk_stamp[(uint64_t)tile * kInbox + (l < n ? l : 0u)] != 0u);
-    if (mine == 0ull) return;  // the chain does not enter this tile
-    const uint32_t u = tile * kInbox + wv::ctz64(mine);
-    uint32_t frame = sc.mk_f[u], pb = sc.mk_b[u];
-    const uint64_t end = (uint64_t)(tile + 1u) * kTile;
-    uint64_t pos = sc.inbox_pos[u];
     auto gget = [&](uint64_t p) { return (uint32_t)bytes[p]; };
     for (uint32_t strip = 0; strip <= kTile / 128u; ++strip) {
         if (l == 0) {
@@ -283,7 +305,7 @@ FG_WV void emit_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const
             uint64_t p = pos;
             uint32_t d = pb;
             while (k < 64u && p < end) {
-                const Prefix pr = parse_prefix(gget, p, nbytes);
+                const Prefix pr = parse_prefix(gget, p, lim);
                 if (pr.st != ST_VALID) { term = pr.st; break; }
                 f_pos[k] = (uint32_t)p; f_plen[k] = pr.plen; f_len[k] = (uint32_t)pr.len; f_dst[k] = d;
                 d += (uint32_t)pr.len;
@@ -309,6 +331,23 @@ FG_WV void emit_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const
         wv::sync();
         if (term != kNil || pos >= end || k < 64u) break;
     }
+}
+// the marked entry of a tile's inbox (the one place where a true chain enters it), or kNil
+FG_WV uint32_t marked_entry(uint32_t tile, const Scratch& sc) {
+    const uint32_t l = wv::lane();
+    uint32_t n = sc.inbox_cnt[tile];
+    if (n > kInbox) n = kInbox;
+    const uint64_t mine = wv::ballot(l < n && sc.mk_stamp[(uint64_t)tile * kInbox + (l < n ? l : 0u)] != 0u);
+    return mine == 0ull ? kNil : tile * kInbox + wv::ctz64(mine);
+}
+
+FG_WV void emit_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint8_t* packed, uint64_t* offsets,
+                     uint64_t* starts, uint8_t* bad, uint64_t cap, uint32_t* lds) {
+    const uint32_t l = wv::lane();
+    if (sc.hdr[H_DECLINE] != 0u) return;  // (nothing is valid: write nothing)
+    const uint32_t u = marked_entry(tile, sc);
+    if (u == kNil) return;  // the chain does not enter this tile
+    emit_chain(bytes, nbytes, (uint64_t)(tile + 1u) * kTile, sc.inbox_pos[u], sc.mk_f[u], sc.mk_b[u], packed, offsets, starts, bad, cap, lds);
     // the node that ends the chain reports for the stream
     if (l == 0 && sc.nd_term[u] != kNil) {
         const uint32_t total_f = sc.mk_f[u] + sc.jf[0][u], total_b = sc.mk_b[u] + sc.jb[0][u];

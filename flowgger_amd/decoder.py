@@ -332,6 +332,62 @@ class Decoder:
         seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
         return (HostTables.from_struct(st) if ns else None), offsets, kinds, seg_first, seg_cons
 
+    def frame_syslen_multi_device(self, d_bytes, d_seg_starts, cap_frames: Optional[int] = None, stream=None):
+        """fg_frame_syslen_multi_device: d_bytes holds the octet-counted chunks of K connections back to back (segment k =
+        d_bytes[seg_starts[k]:seg_starts[k + 1]], torch int64 / uint64 [K + 1]); every segment is walked as a stream of its own (a
+        SyslenSplitter per connection, tcp_input.rs:39-47), FRAMED AND PACKED in buffer order.  Returns (d_packed uint8, d_offsets
+        int64[n + 1] into d_packed, d_frame_starts int64[n] into d_bytes, d_bad uint8[n], n, d_seg_first int64[K + 1], d_seg_consumed
+        int64[K], d_seg_stop uint8[K] (FG_SYSLEN_*), payload_bytes).  FgError(FG_ERR_UNSUPPORTED) when the device path declines the
+        buffer: frame it on the host.  d_bytes as frame_syslen_device wants it."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        dev = d_bytes.device
+        nbytes, K = d_bytes.numel(), d_seg_starts.numel() - 1
+        cap = cap_frames if cap_frames is not None else nbytes // 32 + 16
+        d_packed = torch.empty((nbytes + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+        d_first = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
+        d_stop = torch.empty(max(K, 1), dtype=torch.uint8, device=dev)
+        while True:
+            d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            d_starts = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            d_bad = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            n, payload = C.c_uint64(), C.c_uint64()
+            rc = L.lib().fg_frame_syslen_multi_device(self._ctx, d_bytes.data_ptr(), nbytes, d_seg_starts.data_ptr(), K, d_packed.data_ptr(),
+                                                      d_offsets.data_ptr(), d_starts.data_ptr(), d_bad.data_ptr(), cap, d_first.data_ptr(),
+                                                      d_cons.data_ptr(), d_stop.data_ptr(), C.byref(n), C.byref(payload),
+                                                      C.c_void_p(stream.cuda_stream))
+            if rc == L.FG_ERR_ENT_OVERFLOW and cap_frames is None:
+                cap = int(n.value) + 16
+                continue
+            L.check(rc, "fg_frame_syslen_multi_device")
+            k = int(n.value)
+            return d_packed, d_offsets[:k + 1], d_starts[:k], d_bad[:k], k, d_first, d_cons[:K], d_stop[:K], int(payload.value)
+
+    def frame_decode_syslen_multi(self, raw: Union[bytes, np.ndarray], seg_starts):
+        """fg_frame_decode_syslen_multi_batch: the octet-counted chunks of K connections back to back in, tables out.  Returns
+        (HostTables or None, frame_starts uint64[n], seg_first uint64[K + 1], seg_consumed uint64[K], seg_stop uint8[K]); frame i
+        starts with its "<len> " prefix at raw[frame_starts[i]], the tables' spans are relative to its payload, and a payload that is
+        not valid UTF-8 has status FG_ST_BAD_UTF8.  last_host_path() says whether the device framed the buffer or the host hopped it."""
+        buf = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, np.uint8)
+        starts = np.ascontiguousarray(seg_starts, np.uint64)
+        K = len(starts) - 1
+        st = L.fg_tables()
+        fs, first, cons, stop = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = C.c_uint64()
+        L.check(L.lib().fg_frame_decode_syslen_multi_batch(self._ctx, self.fmt, buf.ctypes.data if buf.size else None, buf.size,
+                                                           starts.ctypes.data, K, C.byref(st), C.byref(fs), C.byref(first), C.byref(cons),
+                                                           C.byref(stop), C.byref(n)), "fg_frame_decode_syslen_multi_batch")
+        nf = int(n.value)
+        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+        frame_starts = np.ctypeslib.as_array(C.cast(fs, u64p), (nf,)).copy() if nf else np.zeros(0, np.uint64)
+        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
+        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
+        seg_stop = np.ctypeslib.as_array(C.cast(stop, u8p), (K,)).copy() if K else np.zeros(0, np.uint8)
+        return (HostTables.from_struct(st) if nf else None), frame_starts, seg_first, seg_cons, seg_stop
+
     # -- the UDP input (input/udp_input.rs:100-143) -------------------------------------------------------
     def udp_decode_packed(self, data: np.ndarray, offsets: np.ndarray, max_inflated: Optional[int] = None):
         """Datagrams back to back in, tables out (fg_udp_decode_batch: upload, inflate / copy + UTF-8 on the GPU, decode).  Returns
@@ -543,6 +599,130 @@ class MultiStreamSplitter:
                             continue
                         r = DecodeError(f"{r}: [{text}]")
                     res.append(r)
+            out.append((c, res))
+        return out
+
+
+SYSLEN_BAD_LENGTH = "Can't read message's length"                       # syslen_splitter.rs:45-46
+SYSLEN_SHORT_READ = "failed to fill whole buffer"                        # read_exact's UnexpectedEof, printed with `{}` (:27-30)
+SYSLEN_PANIC = "thread panicked: called `Result::unwrap()` on an `Err` value: FromUtf8Error (syslen_splitter.rs:32)"
+
+
+class MultiSyslenSplitter:
+    """MultiStreamSplitter for OCTET-COUNTED connections (input.framing = "syslen": tcpco / tlsco inputs): parks the chunks of many
+    connections and hands them to the GPU together -- one fg_frame_decode_syslen_multi_batch call walks every connection's bytes as its
+    own stream and decodes the payloads.  Per connection the output is what SyslenSplitter::run (splitter/syslen_splitter.rs:17-57)
+    produces for the bytes pushed so far: a Record per frame that decodes, DecodeError("<decoder's error>: [<trimmed payload>]") per
+    frame that does not; the bytes behind the last whole frame are carried over to the connection's next chunk.  A length that cannot
+    be read ends the connection with DecodeError("Can't read message's length"), the first payload that is not valid UTF-8 with the
+    reference's panic text (its `unwrap()`): later pushes raise.  close(conn) is its EOF: "Can't read message's length" with nothing
+    carried, else what the reference reports for an EOF inside a length or a payload."""
+
+    def __init__(self, decoder: Decoder, policy: Optional[FlushPolicy] = None):
+        self.decoder, self.policy = decoder, policy or FlushPolicy()
+        self._carry: dict = {}
+        self._pending: dict = {}
+        self._closed: set = set()   # close() seen, EOF not reported yet
+        self._over: set = set()     # the connection ended: by its EOF, a bad length or an invalid payload
+        self._bytes = 0
+        self._first_at: Optional[float] = None
+
+    def push(self, conn_id, chunk: bytes) -> list:
+        """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
+        import time
+
+        if conn_id in self._closed or conn_id in self._over:
+            raise ValueError("push after the connection ended")
+        if chunk:
+            self._pending.setdefault(conn_id, []).append(bytes(chunk))
+            self._bytes += len(chunk)
+            if self._first_at is None:
+                self._first_at = time.monotonic()
+        due = self._bytes >= self.policy.max_bytes or (
+            self._first_at is not None and (time.monotonic() - self._first_at) * 1e3 >= self.policy.max_latency_ms)
+        return self.flush() if due else []
+
+    def close(self, conn_id) -> None:
+        """the connection's EOF, reported at the next flush"""
+        if conn_id not in self._over:
+            self._closed.add(conn_id)
+            self._pending.setdefault(conn_id, [])
+
+    def pending_bytes(self) -> int:
+        return self._bytes
+
+    def _decode_error(self, r: DecodeError, payload: bytes) -> DecodeError:
+        return DecodeError(f"{r}: [{payload.decode('utf-8').strip(_RUST_WS)}]")
+
+    def _eof(self, tail: bytes) -> list:
+        """what SyslenSplitter::run reports when the stream ends with `tail` behind the last whole frame (fg_decoder.hpp's Syslen
+        branch: read_until drops the last byte of a length that no ' ' follows)"""
+        sp = tail.find(b" ")
+        if sp >= 0:  # a whole prefix (a bad one ended the connection before): EOF inside its payload
+            return [DecodeError(SYSLEN_SHORT_READ)]
+        num = tail[:-1]
+        body = num[1:] if num[:1] == b"+" else num
+        if len(tail) <= 1 or not body or not body.isdigit() or int(body) >= 1 << 64:
+            return [DecodeError(SYSLEN_BAD_LENGTH)]
+        if int(body) != 0:
+            return [DecodeError(SYSLEN_SHORT_READ)]
+        r = self.decoder.decode_batch([b""])[0]  # "0?" + EOF: an empty message is handled, then the next read_msglen sees Ok(0)
+        return [self._decode_error(r, b"") if isinstance(r, DecodeError) else r, DecodeError(SYSLEN_BAD_LENGTH)]
+
+    def flush(self) -> list:
+        """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
+        conns = list(self._pending)
+        segs = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
+        self._pending, self._bytes, self._first_at = {}, 0, None
+        if not conns:
+            return []
+        raw = b"".join(segs)
+        starts = np.zeros(len(segs) + 1, np.uint64)
+        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
+        tab, fstart, first, cons, stop = self.decoder.frame_decode_syslen_multi(raw, starts)
+        fmt = self.decoder.fmt
+        payloads = []
+        for a in fstart:
+            sp = raw.index(b" ", int(a))
+            payloads.append(raw[sp + 1:sp + 1 + int(raw[int(a):sp])])
+        can, coffs = b"", None
+        if tab is not None:
+            data, offsets = pack_lines(payloads)
+            data = np.concatenate([data, np.zeros(32, np.uint8)])
+            if fmt == L.FG_LTSV and bool(((tab.a["meta"][:tab.n] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
+                import sys
+
+                from .tables import tables_stdout
+
+                text = tables_stdout(tab, fmt, data, offsets)  # (the decoder's stdout side effect, ltsv_decoder.rs:99)
+                if text:
+                    sys.stdout.write(text.decode("utf-8", "replace"))
+            blob, coffs = tab.serialize(fmt, data, offsets, cfg=self.decoder._cfg)
+            can = blob.tobytes()
+            status = tab.a["meta"][:tab.n] & 0xFF
+        out = []
+        for k, c in enumerate(conns):
+            res: list = []
+            over = False
+            for i in range(int(first[k]), int(first[k + 1])):
+                if status[i] == L.FG_ST_BAD_UTF8:  # the reference's unwrap(): this connection's thread ends here
+                    res.append(DecodeError(SYSLEN_PANIC))
+                    over = True
+                    break
+                r = parse_canonical(can[int(coffs[i]):int(coffs[i + 1])])
+                res.append(self._decode_error(r, payloads[i]) if isinstance(r, DecodeError) else r)
+            if not over and stop[k] == L.FG_SYSLEN_BAD_LEN:
+                res.append(DecodeError(SYSLEN_BAD_LENGTH))
+                over = True
+            tail = segs[k][int(cons[k]):]
+            if not over and c in self._closed:
+                res += self._eof(tail) if tail else [DecodeError(SYSLEN_BAD_LENGTH)]
+                over = True
+            self._closed.discard(c)
+            if over:
+                self._over.add(c)
+            elif tail:
+                self._carry[c] = tail
             out.append((c, res))
         return out
 

@@ -346,7 +346,8 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
  *                  needs NO alignment.  A list that does not tile is clamped (each value into [its predecessor, nbytes], the first
  *                  to 0, the last to nbytes): the results are then those of the clamped list, and memory safety never depends on it.
  *   d_seg_final    n_segs bytes (device) or NULL = all zero: nonzero = connection k ended with this chunk
- *   framing        FG_FRAME_LINE or FG_FRAME_NUL (FG_ERR_ARG otherwise: FG_FRAME_SYSLEN / FG_FRAME_CAPNP keep their own entry points)
+ *   framing        FG_FRAME_LINE or FG_FRAME_NUL (FG_ERR_ARG otherwise: FG_FRAME_SYSLEN has fg_frame_syslen_multi_device, FG_FRAME_CAPNP
+ *                  its single-stream entry point)
  * Every segment is framed as if it were the whole stream.  The output is a list of SLOTS that tile the buffer, in buffer order:
  *   d_offsets      out, cap_slots + 1 entries: slot i = [offsets[i], offsets[i + 1]), terminator included.  A nonempty segment has
  *                  one slot per delimiter in it and one more when its last byte is no delimiter (its tail); an empty one has none
@@ -420,6 +421,37 @@ int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, cons
 int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint8_t* d_packed, uint64_t* d_offsets,
                            uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames, uint64_t* n_frames, uint64_t* consumed,
                            int* stop_reason, void* stream);
+/* GPU FRAMING OF THE OCTET-COUNTED CHUNKS OF MANY CONNECTIONS IN ONE LAUNCH (additive under the same FG_ABI_VERSION).  The reference
+ * gives every connection a SyslenSplitter of its own (input/tcp/tcp_input.rs:39-47, tcpco_input.rs, tlsco_input.rs,
+ * splitter/syslen_splitter.rs:10-57); this call replaces read_msglen + read_exact + String::from_utf8 for K connections at once.
+ *   d_bytes, d_seg_starts, n_segs   as fg_frame_multi_device: the segments tile the buffer, a start needs no alignment, empty segments
+ *                   are allowed, and the list is clamped on the device (memory safety never depends on it).  There is no seg_final: a
+ *                   frame needs its whole payload whether or not the connection ended, and what a tail means at the end of a stream
+ *                   is the caller's business, as for fg_frame_syslen_device
+ * Every segment is walked as if it were the whole chunk.  A neighbouring segment's bytes never complete a prefix or a payload: a prefix
+ * that meets its segment's end without a ' ' is a TAIL, so is a payload that would run past it (whatever the buffer holds there), and
+ * a segment that begins with ' ' or a non-digit is a BAD_LEN whatever digits the segment before ended on.  A UTF-8 sequence cut off by
+ * the end of a payload is invalid in that payload, whatever byte follows.  The frames come out in buffer order, FRAMED AND PACKED as
+ * fg_frame_syslen_device writes them:
+ *   d_packed        out: the payloads back to back, capacity nbytes rounded up to 16, plus 16; 16-byte aligned
+ *   d_offsets       out, cap_frames + 1 entries INTO d_packed, the FG_FRAME_NONE convention
+ *   d_frame_starts  out, cap_frames entries INTO d_bytes: where the prefix of frame i starts.  The frames no longer tile the buffer:
+ *                   frame i ends at start + FG_SYSLEN_PREFIX_LEN + (offsets[i + 1] - offsets[i])
+ *   d_bad_utf8      out, cap_frames bytes, as fg_frame_syslen_device
+ *   d_seg_first     out, n_segs + 1 entries: the frames of segment k are [seg_first[k], seg_first[k + 1]); seg_first[n_segs] = *n_frames
+ *   d_seg_consumed  out, n_segs entries: the bytes of segment k that its frames cover
+ *   d_seg_stop      out, n_segs bytes: an fg_syslen_stop -- how the chain of segment k ended at seg_starts[k] + seg_consumed[k].  A stop
+ *                   in one segment changes nothing in any other; an empty segment is CLEAN with no frames
+ *   n_frames, payload_bytes   out (host): the frames and the bytes packed; the call synchronises the stream
+ * With n_segs == 1 the frames, offsets, starts, flags, consumed and stop are those of fg_frame_syslen_device on the same bytes.
+ * Returns FG_ERR_ENT_OVERFLOW when cap_frames is too small (*n_frames holds the need; NOTHING is written to the frame outputs and the
+ * per-segment outputs), FG_ERR_UNSUPPORTED when the launch DECLINES (as fg_frame_syslen_device: nothing is valid, frame on the host;
+ * segment starts inside one tile never cause it -- they do not go through the tiles' inboxes) or nbytes exceeds the single-stream
+ * framer's bound or n_segs 2^24. */
+int fg_frame_syslen_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs,
+                                 uint8_t* d_packed, uint64_t* d_offsets, uint64_t* d_frame_starts, uint8_t* d_bad_utf8, uint64_t cap_frames,
+                                 uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop, uint64_t* n_frames,
+                                 uint64_t* payload_bytes, void* stream);
 /* GPU FRAMING of a CAP'N PROTO stream (input.format = "capnp"; replaces the walk of capnp::serialize::read_message over the segment
  * tables in CapnpSplitter::run, splitter/capnp_splitter.rs:24-46, for a chunk of the stream that lies in device-addressable memory
  * and starts at a message).  At a message start p: fewer than 8 bytes left is a TAIL; segs = u32le(p) + 1, 512 or more stops with
@@ -547,6 +579,23 @@ int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, 
                                 fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
                                 const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, uint64_t* n_slots);
 
+/* HOST-BUFFER decode of the OCTET-COUNTED chunks of many connections: one call uploads the buffer, frames and packs every segment as
+ * its own stream (fg_frame_syslen_multi_device, whose contract this shares) and decodes the packed payloads (FG_FRAME_NONE, with the
+ * UTF-8 flags).  fmt: FG_RFC5424, FG_LTSV, FG_GELF or FG_RFC3164 (FG_CAPNP: FG_ERR_ARG).  The tiling of seg_starts IS checked here
+ * (FG_ERR_ARG).
+ *   out               tables in ctx-owned pinned host memory, *n_frames rows; a payload that is not valid UTF-8 has status
+ *                     FG_ST_BAD_UTF8; spans are relative to each frame's PAYLOAD start (as FG_FRAME_SYSLEN in fg_frame_decode_batch):
+ *                     (*out_frame_starts)[i] + FG_SYSLEN_PREFIX_LEN
+ *   out_frame_starts  *n_frames entries into `bytes`
+ *   out_seg_first     n_segs + 1 entries;  out_seg_consumed: n_segs entries;  out_seg_stop: n_segs bytes (fg_syslen_stop)
+ * When the device framer declines, or any segment stops with FG_SYSLEN_LONG_PREFIX, the whole buffer is hopped on the host, segment by
+ * segment, with prefixes of any length: the same results (and no LONG_PREFIX).  fg_last_host_path says
+ * FG_PATH_FRAME_SYSLEN_MULTI_DEVICE or FG_PATH_FRAME_SYSLEN_MULTI_HOST.  Everything returned is ctx-owned and stays valid until the
+ * next call on this ctx.  Out of scope here: slicing over streams, the fused launch, fg_transcode_batch for segmented input. */
+int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
+                                       uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts, const uint64_t** out_seg_first,
+                                       const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop, uint64_t* n_frames);
+
 /* HOST-BUFFER UDP decode: upload the datagrams, fg_udp_unpack_device, decode -- the whole of handle_record_maybe_compressed for a
  * batch.  `bytes` / `offsets` pinned or pageable.  `out`: tables in ctx-owned pinned host memory, n rows; a dropped datagram has
  * status FG_ST_BAD_UTF8 and (*udp_status)[i] says why.  *out_lines / *out_line_offsets (n + 1 entries): the payloads as decoded, in
@@ -569,7 +618,9 @@ enum {
     FG_PATH_FRAME_SYSLEN_HOST = 7, /* ... the device framer declined the chunk: the prefixes were hopped on the host */
     FG_PATH_FRAME_CAPNP_DEVICE = 8, /* fg_frame_decode_batch / fg_transcode_batch, FG_FRAME_CAPNP: framed by the device where the chunk lies */
     FG_PATH_FRAME_CAPNP_HOST = 9,  /* ... the device framer declined the chunk: the segment tables were walked on the host */
-    FG_PATH_FRAME_MULTI = 10       /* fg_frame_decode_multi_batch: upload, segmented framing, decode */
+    FG_PATH_FRAME_MULTI = 10,      /* fg_frame_decode_multi_batch: upload, segmented framing, decode */
+    FG_PATH_FRAME_SYSLEN_MULTI_DEVICE = 11, /* fg_frame_decode_syslen_multi_batch: every segment framed + packed by the device */
+    FG_PATH_FRAME_SYSLEN_MULTI_HOST = 12    /* ... the device framer declined the buffer: the segments were hopped on the host */
 };
 int fg_last_host_path(const fg_ctx* ctx);
 /* How the chain of segment tables of the last FG_FRAME_CAPNP call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an

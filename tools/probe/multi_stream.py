@@ -11,7 +11,12 @@ Per cell: the canonical Record bytes of A's rows and of B's FRAME rows are asser
 spaced ones beyond); then windows of at least --window seconds, the sides alternated within one process, --rounds rounds; median and
 spread (min .. max) of lines/s end to end.  Framing alone: device time between two events around fg_frame_multi_device (K segments)
 and around fg_frame_device (the same bytes as one stream), both HBM-resident, median of 15 -- what the boundary handling costs.
-(fg_set_timing covers the decode launches only, so events around the calls stand in for it.)  One JSON line at the end."""
+(fg_set_timing covers the decode launches only, so events around the calls stand in for it.)  One JSON line at the end.
+    --syslen   octet-counted chunks instead ("<len> <line>\\n" frames, a connection's chunk ends inside a frame), HBM-resident: the time
+               between two events around ONE fg_frame_syslen_multi_device call against K fg_frame_syslen_device calls on the same bytes
+               (every chunk 16-byte aligned in a buffer of its own; each call synchronises, as it must to return its counts), for
+               --syslen-cells K:chunk,...; and one stream (--syslen-one bytes) with n_segs == 1 against the single-stream call -- what
+               the segment lookup costs when it finds nothing.  Median (min .. max) of 9 after 3 warm-up runs."""
 import argparse
 import ctypes as C
 import json
@@ -167,16 +172,86 @@ def frame_only(dec, chunks, dev):
     return multi, single
 
 
+def syslen_chunks(lines, K, chunk):
+    """K chunks of about `chunk` bytes: whole frames, then the first half of the next one"""
+    out, i = [], 0
+    for _ in range(K):
+        buf = bytearray()
+        while True:
+            ln = lines[i % len(lines)]
+            i += 1
+            f = b"%d %s\n" % (len(ln) + 1, ln)
+            if len(buf) + len(f) > chunk:
+                buf += f[:max(1, min(len(f) // 2, chunk - len(buf)))]
+                break
+            buf += f
+        out.append(bytes(buf))
+    return out
+
+
+def syslen_mode(dec, lines, dev, cells, one_bytes):
+    def to_dev(raw):
+        host = np.zeros(((len(raw) + 15) & ~15) + 16, np.uint8)
+        host[:len(raw)] = np.frombuffer(raw, np.uint8)
+        return torch.from_numpy(host).to(dev)[:len(raw)]
+
+    s = torch.cuda.current_stream(dev)
+
+    def timed(fn):
+        ts = []
+        for i in range(12):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize(dev)
+            if i >= 3:
+                ts.append(a.elapsed_time(b) * 1e3)
+        return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+    rows = []
+    for K, chunk in cells:
+        chunks = syslen_chunks(lines, K, chunk)
+        raw = b"".join(chunks)
+        starts = np.zeros(K + 1, np.int64)
+        starts[1:] = np.cumsum([len(c) for c in chunks])
+        d_bytes, d_starts, d_each = to_dev(raw), torch.from_numpy(starts).to(dev), [to_dev(c) for c in chunks]
+        cap = len(raw) // 32 + K + 1024
+        n_multi = dec.frame_syslen_multi_device(d_bytes, d_starts, cap_frames=cap)[4]
+        n_each = sum(dec.frame_syslen_device(d, False, cap_frames=len(c) // 32 + 64)[4] for d, c in zip(d_each, chunks))
+        assert n_multi == n_each, (n_multi, n_each)
+        multi = timed(lambda: dec.frame_syslen_multi_device(d_bytes, d_starts, cap_frames=cap))
+        each = timed(lambda: [dec.frame_syslen_device(d, False, cap_frames=len(c) // 32 + 64) for d, c in zip(d_each, chunks)])
+        rows.append({"K": K, "chunk": chunk, "bytes": len(raw), "frames": n_multi, "multi_us": multi, "k_calls_us": each})
+        print(f"syslen K={K:5d} chunk={chunk:8d} total={len(raw) / 2**20:7.2f} MiB frames={n_multi}  one launch {multi['median']:.0f} us "
+              f"({multi['min']:.0f}..{multi['max']:.0f})  K calls {each['median']:.0f} us ({each['min']:.0f}..{each['max']:.0f})", flush=True)
+    raw = syslen_chunks(lines, 1, one_bytes)[0]
+    d_bytes, d_starts = to_dev(raw), torch.tensor([0, len(raw)], dtype=torch.int64, device=dev)
+    cap = len(raw) // 32 + 1024
+    multi = timed(lambda: dec.frame_syslen_multi_device(d_bytes, d_starts, cap_frames=cap))
+    single = timed(lambda: dec.frame_syslen_device(d_bytes, False, cap_frames=cap))
+    print(f"syslen one stream {len(raw) / 2**20:.2f} MiB  n_segs == 1 {multi['median']:.0f} us ({multi['min']:.0f}..{multi['max']:.0f})  "
+          f"single-stream call {single['median']:.0f} us ({single['min']:.0f}..{single['max']:.0f})", flush=True)
+    print(json.dumps({"probe": "multi_stream_syslen", "cells": rows, "one_stream": {"bytes": len(raw), "multi_us": multi, "single_us": single}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--cells", default=",".join(f"{k}:{c}" for k in (16, 256, 4096) for c in (4 << 10, 64 << 10, 1 << 20)))
     ap.add_argument("--lines", type=int, default=200_000)
+    ap.add_argument("--syslen", action="store_true")
+    ap.add_argument("--syslen-cells", default="64:131072,4096:2048")
+    ap.add_argument("--syslen-one", type=int, default=8 << 20)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     dec = RFC5424Decoder()
     lines = synth.rfc5424_lines(args.lines, cfg=2)
+    if args.syslen:
+        lines = [ln if isinstance(ln, bytes) else ln.encode() for ln in lines]
+        syslen_mode(dec, lines, dev, [tuple(int(x) for x in c.split(":")) for c in args.syslen_cells.split(",")], args.syslen_one)
+        return
     results = []
     for cell in args.cells.split(","):
         K0, chunk = (int(x) for x in cell.split(":"))
