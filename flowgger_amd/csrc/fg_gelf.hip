@@ -830,7 +830,9 @@ extern "C" int fg_launch_gelf(const uint8_t* d_bytes, const uint64_t* d_offsets,
             const fg::LaunchGeometry geo = geometry();
             if (geo.L < max_lines) max_lines = geo.L;  // (the geometry already settled on fewer lines)
             if (geo.lds <= lds_budget) break;
-            max_lines >>= 1;
+            // (lines so long that the geometry settled on ONE per group -- an average above ~10 KiB -- stay at one: halving it to
+            //  zero made launch_geometry divide by zero lines per group)
+            if (max_lines > 1u) max_lines >>= 1;
         }
     }
     const uint32_t lines = geometry().L;

@@ -59,6 +59,38 @@ uint32_t byte_walk(const uint8_t* ln, uint32_t pos, uint32_t len, uint32_t* msg_
 
 extern "C" const char* fgs2_last_error() { return g_err.c_str(); }
 
+// find_escaped16 on n (16-bit backslash mask, carry-in) pairs (unit test hook)
+extern "C" void fgs2_find_escaped16(const uint32_t* bs, const uint32_t* cin, uint32_t* out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = sd2::find_escaped16(bs[i], cin[i]);
+}
+// classify_tile alone over `span` bytes (a multiple of 16) staged at a tile's start: the real-quote and backslash masks of every
+// 16-byte chunk.  Returns 1 when the tile bails (a chunk of sixteen backslashes), -1 on an error.
+extern "C" int fgs2_classify(const uint8_t* bytes, uint32_t span, uint16_t* q16, uint16_t* b16) {
+    try {
+        if (span == 0 || span % 16u != 0 || span > 57344u) throw std::runtime_error("bad span");
+        const uint32_t tile_cap = (span + 1023u) & ~1023u;
+        const uint32_t stride16 = tile_cap / 16u + 16u;
+        const size_t lds_bytes = tile_cap + 64u + (size_t)stride16 * 2u * 2u + sd2::extra_bytes(tile_cap);
+        std::vector<uint64_t> lds64(lds_bytes / 8 + 2);
+        uint8_t* smem = reinterpret_cast<uint8_t*>(lds64.data());
+        memset(smem, 0xA5, lds_bytes);
+        memcpy(smem, bytes, span);
+        uint16_t* bm16 = reinterpret_cast<uint16_t*>(smem + tile_cap + 64u);
+        sd2::Lds lds = sd2::carve(smem, bm16, tile_cap, smem + tile_cap + 64u + (size_t)stride16 * 2u * 2u);
+        bool bailed = false;
+        emu::run_wave([&]() {
+            const bool chain = sd2::classify_tile(lds, span);
+            if (wv::lane() == 0u) bailed = chain;
+        });
+        memcpy(q16, lds.bmQ, span / 16u * 2u);
+        memcpy(b16, lds.bmB, span / 16u * 2u);
+        return bailed ? 1 : 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 // For every line i = bytes[offsets[i], offsets[i+1]) whose structured data starts at line index sd_pos[i] (0 = the line has none):
 //   handled[i], status[i], msg_at[i], n_ent[i] from group_walk; its entries (through group_emit into a real entry table) as six
 //   uint32 per entry in ent[6 * (ent_first[i] + k)] = name_s, name_len, val_s, val_len, esc, sdid;

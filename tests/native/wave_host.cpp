@@ -53,9 +53,14 @@ extern "C" int fgw_gelf_decode_framed(const uint8_t* bytes, uint64_t nbytes, con
         const uint32_t L = lines_per_group;
         uint32_t ent_state[2] = {0u, 0u};
         const uint32_t alloc_chunk = 96u;  // small and odd-sized on purpose: chunk boundaries fall inside the test corpora
-        for (uint64_t g0 = 0; g0 < n; g0 += L) {
-            const uint32_t nl = (uint32_t)(g0 + L <= n ? L : n - g0);
+        uint32_t nl = 0;
+        for (uint64_t g0 = 0; g0 < n; g0 += nl) {
+            // the group: the leading lines that end inside the tile, at most L; the first one always goes (fg_pipeline.hpp, geometry)
+            const uint32_t avail = (uint32_t)(g0 + L <= n ? L : n - g0);
             const uint64_t a0 = offsets[g0] & ~15ull;
+            nl = 0;
+            while (nl < avail && offsets[g0 + nl + 1] - a0 <= tile_cap) ++nl;
+            if (nl == 0) nl = 1;
             const uint64_t want = offsets[g0 + nl] - a0;
             const uint32_t span = want > tile_cap ? tile_cap : (uint32_t)((want + 15ull) & ~15ull);
             // stage the tile: garbage beyond the span on purpose (the kernels must not depend on it)
@@ -127,6 +132,21 @@ extern "C" int fgw_gelf_decode_framed(const uint8_t* bytes, uint64_t nbytes, con
 extern "C" int fgw_gelf_decode(const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, uint64_t n, const fg_tables* tables,
                                uint32_t lines_per_group, uint32_t tile_cap, uint8_t* handled) {
     return fgw_gelf_decode_framed(bytes, nbytes, offsets, n, tables, lines_per_group, tile_cap, handled, FG_FRAME_NONE);
+}
+
+// find_escaped of the GELF word pass on n (backslash word, carry-in) pairs (unit test hook)
+extern "C" void fgw_find_escaped(const uint64_t* bs, const uint64_t* cin, uint64_t* out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = fg::gelf2::find_escaped(bs[i], cin[i]);
+}
+// ... on n consecutive words of ONE lane's range, the carry handed from word to word by the expression of decode_tile's word pass
+// (a word of 64 backslashes hands on 0: such a tile bails)
+extern "C" void fgw_find_escaped_chain(const uint64_t* bs, uint64_t cin, uint64_t* out, uint64_t n) {
+    using namespace fg;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t b = bs[i];
+        out[i] = gelf2::find_escaped(b, cin);
+        cin = b == ~0ull ? 0u : (wv::clz64(~b) & 1u);
+    }
 }
 
 // the register-resident number parser of the GELF fast form on ONE token (unit test hook): returns 1 = parsed (kind / bits as
