@@ -1,56 +1,110 @@
-// fg_frame_kernels.hpp -- device code shared by the two framing units, fg_frame.hip (one stream per launch) and fg_frame_multi.hip
-// (the chunks of many connections per launch), and by nothing else: the per-chunk UTF-8 rule, the mask layout (per 16-byte chunk one
-// word: delimiter mask | error mask << 16) and the body of the one-pass chained scan.  Include after fg_pipeline.hpp.
+// fg_frame_kernels.hpp -- what the two framing units share, fg_frame.hip (one stream per launch) and fg_frame_multi.hip (the chunks of
+// many connections per launch), and nobody else: the scan body (a 16 KiB block -> per 16-byte chunk one mask word: delimiter mask |
+// error mask << 16), the emit body (a lane's mask words -> offsets and bad-UTF-8 flags), the body of the one-pass chained scan built
+// from the two, and the layout of a launch's scratch.  The chunk classifier and the dword-parallel UTF-8 rule are fg_fuse.hpp's
+// (fuse::chunk_masks, the ones the fused decoders run; the scalar form of the rule is fg_utf8.hpp).  Include after fg_pipeline.hpp.
 #pragma once
+#include "fg_fuse.hpp"
 
 namespace fg {
 
 constexpr uint32_t kFrameBlock = 16384;  // bytes per wave-block
 constexpr uint32_t kFrameRows = kFrameBlock / (16 * kWave);  // 16
 
-// bit7 flags, per byte of a dword
-__device__ __forceinline__ uint32_t f_cont(uint32_t b) { return b & ~(b << 1) & 0x80808080u; }          // 80..BF
-__device__ __forceinline__ uint32_t f_ge_c0(uint32_t b) { return b & (b << 1) & 0x80808080u; }          // C0..FF
-__device__ __forceinline__ uint32_t f_ge_e0(uint32_t b) { return b & (b << 1) & (b << 2) & 0x80808080u; }
-__device__ __forceinline__ uint32_t f_ge_f0(uint32_t b) { return b & (b << 1) & (b << 2) & (b << 3) & 0x80808080u; }
-__device__ __forceinline__ uint32_t f_eq_hi(uint32_t b, uint32_t pat) {  // byte == pat's byte (pat bytes >= 0x80)
-    uint32_t y = b ^ pat;                                                // zero byte <=> equal
-    return ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;
-}
-// UTF-8 errors of the four bytes in `b`, given the previous dword `p` (bytes just before b):
-// bit7 of byte i set <=> the sequence rules are violated AT byte i.
-__device__ __forceinline__ uint32_t utf8_err_flags(uint32_t b, uint32_t p) {
-    const uint32_t p1 = __builtin_amdgcn_alignbyte(b, p, 3);  // byte i-1 for every i
-    const uint32_t p2 = __builtin_amdgcn_alignbyte(b, p, 2);
-    const uint32_t p3 = __builtin_amdgcn_alignbyte(b, p, 1);
-    // a continuation byte is due here: after a lead, or as the 3rd / 4th byte of a sequence whose
-    // earlier bytes WERE continuations (a sequence broken earlier was flagged there and expects
-    // nothing more -- so no expectation ever crosses an ASCII byte such as the frame terminator)
-    const uint32_t c1 = f_cont(p1), c2 = f_cont(p2);
-    const uint32_t must = f_ge_c0(p1) | (f_ge_e0(p2) & c1) | (f_ge_f0(p3) & c2 & c1);
-    uint32_t err = (f_cont(b) ^ must);                                   // missing or stray continuation
-    // bytes that never appear: C0, C1, F5..FF
-    const uint32_t y = (b & 0xFEFEFEFEu) ^ 0xC0C0C0C0u;
-    err |= ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;
-    err |= b & ((b & 0x7F7F7F7Fu) + 0x0B0B0B0Bu) & 0x80808080u;          // >= F5
-    // second-byte ranges: E0 A0..BF | ED 80..9F | F0 90..BF | F4 80..8F
-    const uint32_t b5 = b << 2, b4 = b << 3;                             // bit5 / bit4 of each byte moved to bit7
-    err |= f_eq_hi(p1, 0xE0E0E0E0u) & ~b5;
-    err |= f_eq_hi(p1, 0xEDEDEDEDu) & b5;
-    err |= f_eq_hi(p1, 0xF0F0F0F0u) & ~b5 & ~b4;
-    err |= f_eq_hi(p1, 0xF4F4F4F4u) & (b5 | b4);
-    return err & 0x80808080u;
+// ---- the scan body --------------------------------------------------------------------------------------------------------
+// The wave's 16 KiB block at `base` (a block AT or behind the stream's end is empty: it only carries the "cut off by the end" check)
+// through its sixteen rows, 16 B per lane and row: store(k, word) gets the mask word of chunk k * kWave + lane of the block; returns
+// the lane's delimiter count.  COPY: the stream is read where the caller has it -- pinned host memory, over the link, once -- and
+// written to its place in HBM on the way (copy_to + the same offsets).
+template <bool COPY, class Store>
+__device__ __forceinline__ uint32_t frame_scan_block(const uint8_t* __restrict__ bytes, uint64_t nbytes, uint32_t delim_pat, uint64_t base, uint32_t lane,
+                                                     uint8_t* __restrict__ copy_to, Store&& store) {
+    const uint64_t left = base < nbytes ? nbytes - base : 0ull;
+    const uint32_t span = left >= kFrameBlock ? kFrameBlock : (uint32_t)((left + 15u) & ~15ull);
+    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(bytes + (base < nbytes ? base : 0ull)), (short)0, (int)span, 0x00020000);
+    u32x4 v[kFrameRows];
+#pragma unroll
+    for (int k = 0; k < (int)kFrameRows; ++k)
+        v[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane * 16u + k * 1024u), 0, COPY ? FG_STREAM_AUX : 0);
+    if constexpr (COPY) {
+        __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(copy_to + (base < nbytes ? base : 0ull), (short)0, (int)span, 0x00020000);
+#pragma unroll
+        for (int k = 0; k < (int)kFrameRows; ++k) __builtin_amdgcn_raw_buffer_store_b128(v[k], dst, (int)(lane * 16u + k * 1024u), 0, 0);
+    }
+    uint32_t before = 0;  // the dword just before this block (row 0, lane 0 needs it)
+    if (base != 0 && base <= nbytes) before = *reinterpret_cast<const uint32_t*>(bytes + base - 4);
+    uint32_t count = 0;
+    uint32_t prev_row_last = before;
+    auto row = [&](int k, int32_t rem) {
+        // previous dword: lane-1's last dword; lane 0: last dword of the previous row / block.  It is the neighbour's RAW dword, although
+        // chunk_masks reads the bytes behind the stream's end as zeros: a chunk with bytes to zero has rem < 16, so the chunk behind
+        // it -- the only one this dword reaches -- lies past nbytes and gets 0 whatever pw holds.
+        uint32_t pw = __shfl_up(v[k][3], 1, kWave);
+        const uint32_t row_last = __shfl(v[k][3], kWave - 1, kWave);
+        if (lane == 0) pw = prev_row_last;
+        prev_row_last = row_last;
+        const uint32_t m = fuse::chunk_masks(v[k][0], v[k][1], v[k][2], v[k][3], pw, delim_pat, rem);
+        store(k, m);
+        count += (uint32_t)__builtin_popcount(m & 0xFFFFu);
+    };
+    // (wave-uniform) every chunk of the block lies inside the stream -- all blocks of a stream but its last one or two --: rem is the
+    // constant 16 and chunk_masks' end-of-stream handling folds away.  With a per-lane rem in every block the 25 GB scan took
+    // 6.77 ms instead of 6.24 (MI355X).
+    if (left >= kFrameBlock) {
+#pragma unroll
+        for (int k = 0; k < (int)kFrameRows; ++k) row(k, 16);
+    } else {
+        // bytes of a chunk inside the stream: rem of them; position rem (one past the end of the stream) may carry the "sequence cut
+        // off by the end" error bit; a chunk behind that position has nothing
+#pragma unroll
+        for (int k = 0; k < (int)kFrameRows; ++k) {
+            const uint64_t cpos = base + (uint64_t)(k * kWave + lane) * 16u;
+            row(k, cpos > nbytes ? -1 : nbytes - cpos >= 16u ? 16 : (int32_t)(nbytes - cpos));
+        }
+    }
+    return count;
 }
 
-// the chunk that holds the stream's end: its bytes behind position nv are the caller's memory, readable (nbytes rounded up to 16) and
-// nothing more -- read as zeros, so that the error bit AT position nv says "a sequence cut off by the end of the stream" and nothing else
-__device__ __forceinline__ uint4 zero_behind(uint4 q, uint32_t nv) {
-    if (nv < 16u) {
-        // dword d holds chunk bytes 4d .. 4d + 3:  nv >= 4d + 4 -> all four kept;  nv <= 4d -> none;  else its low nv - 4d bytes (1 .. 3)
-        auto keep = [&](uint32_t d) -> uint32_t { return nv >= 4u * d + 4u ? 0xFFFFFFFFu : nv <= 4u * d ? 0u : (1u << (8u * (nv - 4u * d))) - 1u; };
-        q.x &= keep(0u), q.y &= keep(1u), q.z &= keep(2u), q.w &= keep(3u);
+// ---- the emit body --------------------------------------------------------------------------------------------------------
+// A lane owns 16 consecutive chunks (256 bytes) of its block: their mask words src[0 .. 16) -> w; returns the lane's delimiter count,
+// *any_err = whether one of the words has an error bit
+__device__ __forceinline__ uint32_t frame_lane_words(const uint32_t* src, uint32_t (&w)[16], uint32_t* any_err) {
+    const uint4* src4 = reinterpret_cast<const uint4*>(src);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint4 m = src4[k];
+        w[4 * k] = m.x; w[4 * k + 1] = m.y; w[4 * k + 2] = m.z; w[4 * k + 3] = m.w;
     }
-    return q;
+    uint32_t mine = 0, err = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        mine += (uint32_t)__builtin_popcount(w[j] & 0xFFFFu);
+        err |= w[j] >> 16;
+    }
+    *any_err = err;
+    return mine;
+}
+// ... and from them offsets[rank + 1 ...] of the lane's delimiters and bad[frame] of its error positions, against cap.
+// rank: delimiters before the lane's first byte, which is stream position lane_base
+__device__ __forceinline__ void frame_emit_lane(const uint32_t (&w)[16], uint64_t rank, uint64_t lane_base, uint64_t* __restrict__ offsets,
+                                                uint8_t* __restrict__ bad, uint64_t cap) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        uint32_t dm = w[j] & 0xFFFFu, em = w[j] >> 16;
+        const uint64_t cpos = lane_base + (uint64_t)j * 16u;
+        while (em) {  // rare
+            const uint32_t b = (uint32_t)__builtin_ctz(em);
+            em &= em - 1u;
+            const uint64_t frame = rank + (uint32_t)__builtin_popcount(dm & ((1u << b) - 1u));
+            if (frame < cap) bad[frame] = 1;
+        }
+        while (dm) {
+            const uint32_t b = (uint32_t)__builtin_ctz(dm);
+            dm &= dm - 1u;
+            ++rank;
+            if (rank <= cap) offsets[rank] = cpos + b + 1u;
+        }
+    }
 }
 
 // ---- the one-pass form ----------------------------------------------------------------------------------------------------
@@ -90,41 +144,7 @@ __device__ __forceinline__ void frame_onepass(const uint8_t* __restrict__ bytes,
     const uint64_t tile = tile0 + blockIdx.x;
     const uint64_t blk = tile * kTileWaves + wv;  // this wave's 16 KiB block (may lie behind the stream: empty then)
     const uint64_t base = blk * kFrameBlock;
-    const uint64_t left = base < nbytes ? nbytes - base : 0ull;  // (a block AT the end only carries the "cut off by the end" check)
-    const uint32_t span = left >= kFrameBlock ? kFrameBlock : (uint32_t)((left + 15u) & ~15ull);
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(bytes + (base < nbytes ? base : 0ull)), (short)0, (int)span, 0x00020000);
-    u32x4 v[kFrameRows];
-#pragma unroll
-    for (int k = 0; k < (int)kFrameRows; ++k)
-        v[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane * 16u + k * 1024u), 0, COPY ? FG_STREAM_AUX : 0);
-    if constexpr (COPY) {
-        __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(copy_to + (base < nbytes ? base : 0ull), (short)0, (int)span, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < (int)kFrameRows; ++k) __builtin_amdgcn_raw_buffer_store_b128(v[k], dst, (int)(lane * 16u + k * 1024u), 0, 0);
-    }
-    uint32_t before = 0;  // the dword just before this block (row 0, lane 0 needs it)
-    if (base != 0 && base <= nbytes) before = *reinterpret_cast<const uint32_t*>(bytes + base - 4);
-    uint32_t count = 0;
-    uint32_t prev_row_last = before;
-#pragma unroll
-    for (int k = 0; k < (int)kFrameRows; ++k) {
-        const uint64_t cpos = base + (uint64_t)(k * kWave + lane) * 16u;
-        const uint32_t nv = cpos >= nbytes ? 0u : (nbytes - cpos >= 16u ? 16u : (uint32_t)(nbytes - cpos));
-        const uint4 q = zero_behind(make_uint4(v[k][0], v[k][1], v[k][2], v[k][3]), nv);
-        const uint32_t dm = mask16_eq(q, delim_pat) & ((1u << nv) - 1u);
-        uint32_t pw = __shfl_up(q.w, 1, kWave);
-        const uint32_t row_last = __shfl(q.w, kWave - 1, kWave);
-        if (lane == 0) pw = prev_row_last;
-        prev_row_last = row_last;
-        uint32_t em = 0;
-        if (((q.x | q.y | q.z | q.w | pw) & 0x80808080u) != 0u) {
-            em = gather16(utf8_err_flags(q.x, pw), utf8_err_flags(q.y, q.x), utf8_err_flags(q.z, q.y), utf8_err_flags(q.w, q.z));
-            em &= nv >= 16u ? 0xFFFFu : ((2u << nv) - 1u);  // keep position nv itself (zero_behind: "not a continuation")
-            if (cpos > nbytes) em = 0;
-        }
-        m_lds[wv][k * kWave + lane] = dm | (em << 16);
-        count += (uint32_t)__builtin_popcount(dm);
-    }
+    uint32_t count = frame_scan_block<COPY>(bytes, nbytes, delim_pat, base, lane, copy_to, [&](int k, uint32_t m) { m_lds[wv][k * kWave + lane] = m; });
     if constexpr (SEG::kSegmented) {
         // segment boundaries that touch this block: its masks are patched where they lie, before anything is counted from them
         __syncthreads();
@@ -154,21 +174,8 @@ __device__ __forceinline__ void frame_onepass(const uint8_t* __restrict__ bytes,
     const bool stall = (whole & kSelfTestStall) != 0u && blockIdx.x == 1u;
     if (threadIdx.x == 0 && !stall) __hip_atomic_store(desc + tile, (tile == 0 ? kDescP : kDescA) | (uint64_t)tile_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // a lane now owns 16 consecutive chunks (256 bytes) of its wave's block: rank of its first delimiter inside the tile
-    uint32_t w[16];
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(m_lds[wv] + lane * 16u);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint4 m = src[k];
-            w[4 * k] = m.x; w[4 * k + 1] = m.y; w[4 * k + 2] = m.z; w[4 * k + 3] = m.w;
-        }
-    }
-    uint32_t mine = 0, any_err = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        mine += (uint32_t)__builtin_popcount(w[j] & 0xFFFFu);
-        any_err |= w[j] >> 16;
-    }
+    uint32_t w[16], any_err;
+    const uint32_t mine = frame_lane_words(m_lds[wv] + lane * 16u, w, &any_err);
     uint32_t tot;
     const uint32_t ex = wave_exclusive_sum(mine, &tot);
     // ---- look-back (the tile's first wave): the delimiters of all tiles before this one ----
@@ -230,38 +237,43 @@ __device__ __forceinline__ void frame_onepass(const uint8_t* __restrict__ bytes,
     __syncthreads();
     if (s_abort) return;
     if (mine == 0 && any_err == 0) return;
-    uint64_t rank = s_prefix + wave_off + ex;  // delimiters before this lane's first byte
-    const uint64_t lane_base = base + (uint64_t)lane * 256u;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        uint32_t dm = w[j] & 0xFFFFu, em = w[j] >> 16;
-        const uint64_t cpos = lane_base + (uint64_t)j * 16u;
-        while (em) {  // rare
-            const uint32_t b = (uint32_t)__builtin_ctz(em);
-            em &= em - 1u;
-            const uint64_t frame = rank + (uint32_t)__builtin_popcount(dm & ((1u << b) - 1u));
-            if (frame < cap) bad[frame] = 1;
-        }
-        while (dm) {
-            const uint32_t b = (uint32_t)__builtin_ctz(dm);
-            dm &= dm - 1u;
-            ++rank;
-            if (rank <= cap) offsets[rank] = cpos + b + 1u;
-        }
-    }
+    frame_emit_lane(w, s_prefix + wave_off + ex, base + (uint64_t)lane * 256u, offsets, bad, cap);
 }
 
 }  // namespace fg
 
-// scratch of a launch: masks = ceil(nbytes / 16 KiB) * 1024 u32 (one-pass: the tile descriptors lie there), counts = nblk u32,
-// pref = (nblk + 1) u64, then the abort word.
 // blocks: one more than needed for the bytes when nbytes is a multiple of the block size, so
 // that position `nbytes` itself (where a sequence cut off by the end of the stream is flagged) is
 // always covered
 static inline uint64_t frame_blocks(uint64_t nbytes) { return nbytes / fg::kFrameBlock + 1; }
-static inline uint64_t* frame_pref(uint8_t* scratch, uint64_t nblk) {
-    return reinterpret_cast<uint64_t*>(scratch + nblk * 4096u + ((nblk * 4u + 255u) & ~255ull));
+// scratch of a launch over nblk blocks, and the only place that knows where its parts lie: the mask words (nblk * 1024 u32; the one-pass
+// form keeps its tile descriptors there, nblk u64 of them cleared), counts = nblk u32, pref = (nblk + 1) u64, then the abort word.
+struct FrameScratch {
+    uint32_t* masks;
+    uint64_t* desc;
+    uint32_t* counts;
+    uint64_t* pref;
+    uint32_t* abort_w;
+    static uint64_t pref_at(uint64_t nblk) { return nblk * 4096u + ((nblk * 4u + 255u) & ~255ull); }
+    static uint64_t bytes(uint64_t nblk) { return pref_at(nblk) + (nblk + 1u) * 8u + 256u; }
+    FrameScratch(uint8_t* scratch, uint64_t nblk)
+        : masks(reinterpret_cast<uint32_t*>(scratch)), desc(reinterpret_cast<uint64_t*>(scratch)),
+          counts(reinterpret_cast<uint32_t*>(scratch + nblk * 4096u)), pref(reinterpret_cast<uint64_t*>(scratch + pref_at(nblk))),
+          abort_w(reinterpret_cast<uint32_t*>(scratch + pref_at(nblk) + (nblk + 1u) * 8u + 64u)) {}
+};
+// what a one-pass launch over the blocks [.., blk1) expects cleared: the word of the range's total -- and, in front of the stream's
+// first launch, the descriptors of all its tiles and the abort word
+static inline void frame_onepass_reset(const FrameScratch& sc, uint64_t nblk, uint64_t blk1, bool first, hipStream_t stream) {
+    if (first) {
+        (void)hipMemsetAsync(sc.desc, 0, nblk * 8u, stream);
+        (void)hipMemsetAsync(sc.abort_w, 0, 4, stream);
+    }
+    (void)hipMemsetAsync(sc.pref + blk1, 0, 8, stream);
 }
-static inline uint32_t* frame_abort_word(uint8_t* scratch, uint64_t nblk) {
-    return reinterpret_cast<uint32_t*>(scratch + nblk * 4096u + ((nblk * 4u + 255u) & ~255ull) + (nblk + 1u) * 8u + 64u);
-}
+
+// fg_frame.hip's classic form in two halves, for the segmented framer, which edits the masks and the block counts between them
+// (declared here, where fg_frame.hip's definitions are held against them; fg_ctx.hpp has the launchers the host side calls)
+extern "C" int fg_launch_frame_classic_scan(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint32_t** d_masks,
+                                            uint32_t** d_counts, hipStream_t stream);
+extern "C" int fg_launch_frame_classic_emit(uint64_t nbytes, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_bad, uint64_t cap,
+                                            uint64_t** d_total_out, hipStream_t stream);

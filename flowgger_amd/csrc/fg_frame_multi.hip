@@ -6,7 +6,7 @@
 // The framing itself is fg_frame.hip's, in both its forms; a segment boundary is three patches to the mask words that scan computes
 // (fg_frame_multi.hpp has the logic and says why every bit has one owner):
 //   classic   k_frame_scan -> k_seg_patch (one lane per boundary: masks in HBM, block counts adjusted) -> k_frame_prefix -> k_frame_emit
-//   one-pass  k_frame_onepass_seg: fg_frame_kernels.hpp's body with a hook between "masks in LDS" and "count": a wave finds the boundaries
+//   one-pass  k_frame_onepass_seg: fg_frame_kernels.hpp's body (frame_onepass) with a hook between "masks in LDS" and "count": a wave finds the boundaries
 //             that touch its 16 KiB block by a binary search over the segment starts (none is the common case and costs that search),
 //             patches its masks where they lie and counts again.  Look-back, spin bound and abort word are the body's own.
 // Around them: k_seg_clamp (the segment starts as the kernels use them: non-decreasing, inside the buffer -- memory safety does not
@@ -158,12 +158,6 @@ __global__ __launch_bounds__(256) void k_seg_finish(const uint8_t* __restrict__ 
 
 }  // namespace fg
 
-extern "C" uint64_t fg_frame_scratch_bytes(uint64_t nbytes);
-extern "C" int fg_launch_frame_classic_scan(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint32_t** d_masks,
-                                            uint32_t** d_counts, hipStream_t stream);
-extern "C" int fg_launch_frame_classic_emit(uint64_t nbytes, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_bad, uint64_t cap,
-                                            uint64_t** d_total_out, hipStream_t stream);
-
 // k_seg_clamp for another unit (fg_syslen_multi.hip): c has n_segs + 1 entries
 extern "C" int fg_launch_seg_clamp(const uint64_t* d_seg_starts, uint64_t n_segs, uint64_t nbytes, uint64_t* d_c, hipStream_t stream) {
     hipLaunchKernelGGL(fg::k_seg_clamp, dim3(1), dim3(1024), 0, stream, d_seg_starts, n_segs, nbytes, d_c);
@@ -171,7 +165,7 @@ extern "C" int fg_launch_seg_clamp(const uint64_t* d_seg_starts, uint64_t n_segs
 }
 
 // scratch: the framing's own (fg_frame_scratch_bytes), then the clamped segment starts (n_segs + 1 u64), then the two result words
-static inline uint64_t multi_frame_part(uint64_t nbytes) { return (fg_frame_scratch_bytes(nbytes) + 255u) & ~255ull; }
+static inline uint64_t multi_frame_part(uint64_t nbytes) { return (FrameScratch::bytes(frame_blocks(nbytes)) + 255u) & ~255ull; }
 extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t n_segs) {
     return multi_frame_part(nbytes) + (((n_segs + 1u) * 8u + 255u) & ~255ull) + 256u;
 }
@@ -190,14 +184,11 @@ extern "C" int fg_launch_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, ui
     hipLaunchKernelGGL(fg::k_seg_clamp, dim3(1), dim3(1024), 0, stream, d_seg_starts, n_segs, nbytes, c);
     uint64_t* d_total = nullptr;
     if (!classic) {
-        uint64_t* desc = reinterpret_cast<uint64_t*>(scratch);
-        uint64_t* pref = frame_pref(scratch, nblk);
-        (void)hipMemsetAsync(desc, 0, nblk * 8u, stream);
-        (void)hipMemsetAsync(frame_abort_word(scratch, nblk), 0, 4, stream);
-        (void)hipMemsetAsync(pref + nblk, 0, 8, stream);
+        const FrameScratch sc(scratch, nblk);
+        frame_onepass_reset(sc, nblk, nblk, true, stream);
         hipLaunchKernelGGL(fg::k_frame_onepass_seg, dim3((uint32_t)((nblk + fg::kTileWaves - 1) / fg::kTileWaves)), dim3(fg::kWave * fg::kTileWaves), 0, stream,
-                           d_bytes, nbytes, delim * 0x01010101u, desc, pref, frame_abort_word(scratch, nblk), d_offsets, d_kind, cap, nblk, c, n_segs);
-        d_total = pref + nblk;
+                           d_bytes, nbytes, delim * 0x01010101u, sc.desc, sc.pref, sc.abort_w, d_offsets, d_kind, cap, nblk, c, n_segs);
+        d_total = sc.pref + nblk;
     } else {
         uint32_t *masks = nullptr, *counts = nullptr;
         int rc = fg_launch_frame_classic_scan(d_bytes, nbytes, delim, scratch, &masks, &counts, stream);

@@ -17,6 +17,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "fg_utf8.hpp"
+
 #if defined(__HIPCC__)
 #define FG_FM_FN __host__ __device__ __forceinline__
 #else
@@ -29,21 +31,9 @@ namespace fmulti {
 constexpr uint8_t kSlotFrame = 0, kSlotBadUtf8 = 1, kSlotCarry = 2;  // FG_SLOT_* of include/fg_hip.h
 constexpr uint64_t kNoBoundary = ~0ull;
 
-// The framing scan's UTF-8 rule (fg_frame_kernels.hpp utf8_err_flags) for ONE position: byte b, its predecessors p1 (nearest), p2, p3.
-FG_FM_FN bool utf8_err_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3) {
-    auto cont = [](uint32_t v) { return (v & 0xC0u) == 0x80u; };
-    const bool must = p1 >= 0xC0u || (p2 >= 0xE0u && cont(p1)) || (p3 >= 0xF0u && cont(p2) && cont(p1));
-    bool err = cont(b) != must;                              // missing or stray continuation
-    err |= b == 0xC0u || b == 0xC1u || b >= 0xF5u;           // bytes that never appear
-    const bool b5 = (b & 0x20u) != 0u, b4 = (b & 0x10u) != 0u;
-    err |= p1 == 0xE0u && !b5;                               // second-byte ranges: E0 A0..BF | ED 80..9F | F0 90..BF | F4 80..8F
-    err |= p1 == 0xEDu && b5;
-    err |= p1 == 0xF0u && !b5 && !b4;
-    err |= p1 == 0xF4u && (b5 || b4);
-    return err;
-}
-// ... for the position one past the end of a stream whose last bytes are p1, p2, p3: is a continuation still due?
-FG_FM_FN bool utf8_cut_off(uint32_t p1, uint32_t p2, uint32_t p3) { return utf8_err_at(0u, p1, p2, p3); }
+// (fg_utf8.hpp's rule under the names it had while a copy lived here: test hosts written against them keep compiling)
+FG_FM_FN bool utf8_err_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3) { return utf8::err_at(b, p1, p2, p3); }
+FG_FM_FN bool utf8_cut_off(uint32_t p1, uint32_t p2, uint32_t p3) { return utf8::cut_off(p1, p2, p3); }
 
 // seg_starts as the kernels use them: value k clamped into [value k - 1, nbytes], the first one 0 and the last one nbytes -- a list
 // that does not tile the buffer frames SOMETHING, and nothing is read or written out of bounds for it.
@@ -85,15 +75,15 @@ FG_FM_FN void patch_boundary(uint64_t p, uint64_t prev, uint64_t next, uint64_t 
         if (x > nbytes || x >= next) break;
         const uint32_t b = x < nbytes ? byte(x) : 0u;
         const uint32_t p1 = d >= 1u ? byte(x - 1u) : 0u, p2 = d >= 2u ? byte(x - 2u) : 0u;
-        bool e = utf8_err_at(b, p1, p2, 0u);
-        if (x + 1u == next) e |= utf8_cut_off(b, p1, p2);
+        bool e = utf8::err_at(b, p1, p2, 0u);
+        if (x + 1u == next) e |= utf8::cut_off(b, p1, p2);
         sink.put_err(x, e);
     }
     if (prev == 0 || p - prev >= 4u) {                                                        // (c), where p - 1 has no owner
         const uint32_t q1 = byte(p - 1u);
         const uint32_t q2 = p >= 2u && p - 2u >= prev ? byte(p - 2u) : 0u;
         const uint32_t q3 = p >= 3u && p - 3u >= prev ? byte(p - 3u) : 0u;
-        if (utf8_cut_off(q1, q2, q3)) sink.or_err(p - 1u);
+        if (utf8::cut_off(q1, q2, q3)) sink.or_err(p - 1u);
     }
 }
 

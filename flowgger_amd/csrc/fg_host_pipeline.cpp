@@ -530,13 +530,10 @@ static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int 
         std::vector<uint8_t> packed, bad;
         stop = (int)sl::host_walk(bytes, nbytes, ~0ull, consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
             const uint8_t* b = bytes + pos + plen;
-            bool err = false;
-            for (uint64_t i = 0; i <= len && !err; ++i)
-                err = sl::utf8_err_at(i < len ? b[i] : 0u, i >= 1 ? b[i - 1] : 0u, i >= 2 ? b[i - 2] : 0u, i >= 3 ? b[i - 3] : 0u);
             starts.push_back(pos);
             packed.insert(packed.end(), b, b + len);
             offs.push_back(packed.size());
-            bad.push_back(err ? 1 : 0);
+            bad.push_back(fg::utf8::payload_bad(b, len) ? 1 : 0);
         });
         starts.push_back(*consumed);
         n = starts.size() - 1;
@@ -1237,13 +1234,10 @@ extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, co
             uint64_t consumed = 0;
             stop.push_back((uint8_t)sl::host_walk(seg, seg_starts[k + 1] - at, ~0ull, &consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
                 const uint8_t* b = seg + pos + plen;
-                bool err = false;
-                for (uint64_t i = 0; i <= len && !err; ++i)
-                    err = sl::utf8_err_at(i < len ? b[i] : 0u, i >= 1 ? b[i - 1] : 0u, i >= 2 ? b[i - 2] : 0u, i >= 3 ? b[i - 3] : 0u);
                 starts.push_back(at + pos);
                 packed.insert(packed.end(), b, b + len);
                 offs.push_back(packed.size());
-                bad.push_back(err ? 1 : 0);
+                bad.push_back(fg::utf8::payload_bad(b, len) ? 1 : 0);
             }));
             cons.push_back(consumed);
             first.push_back(starts.size());

@@ -259,7 +259,7 @@ FG_WV bool copy_check(const uint8_t* src, uint8_t* dst, uint32_t len) {
         const uint32_t b = i < len ? src[i] : 0u;
         if (i < len) dst[i] = (uint8_t)b;
         const uint32_t p1 = i >= 1u ? src[i - 1u] : 0u;
-        if ((b | p1) & 0x80u) bad |= utf8_err_at(b, p1, i >= 2u ? src[i - 2u] : 0u, i >= 3u ? src[i - 3u] : 0u);
+        if ((b | p1) & 0x80u) bad |= utf8::err_at(b, p1, i >= 2u ? src[i - 2u] : 0u, i >= 3u ? src[i - 3u] : 0u);
     }
     for (uint32_t i = h + l * 16u; i < len; i += wv::kLanes * 16u) {
         const uint32_t nb = len - i >= 16u ? 16u : len - i;
@@ -280,7 +280,7 @@ FG_WV bool copy_check(const uint8_t* src, uint8_t* dst, uint32_t len) {
             const uint32_t upto = i + nb == len ? nb + 1u : nb;  // the lane of the payload's last bytes also looks at position len
             for (uint32_t k = 0; k < upto; ++k) {
                 const uint32_t b = k < nb ? (q[k >> 2] >> (8u * (k & 3u))) & 0xFFu : 0u;
-                bad |= utf8_err_at(b, p1, p2, p3);
+                bad |= utf8::err_at(b, p1, p2, p3);
                 p3 = p2; p2 = p1; p1 = b;
             }
         }

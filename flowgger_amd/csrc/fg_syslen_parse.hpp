@@ -1,8 +1,12 @@
-// fg_syslen_parse.hpp -- the length prefix of an octet-counted frame (read_msglen, src/flowgger/splitter/syslen_splitter.rs:17-25), the
-// position-based UTF-8 rule and the sequential walk over a chunk: what the device framer (fg_syslen.hpp), the host hop of the
-// host-buffer entry points (fg_host_pipeline.cpp) and the CPU suite share.  No HIP, no wave primitives.
+// fg_syslen_parse.hpp -- the length prefix of an octet-counted frame (read_msglen, src/flowgger/splitter/syslen_splitter.rs:17-25)
+// and the sequential walk over a chunk: what the device framer (fg_syslen.hpp), the host hop of the host-buffer entry points
+// (fg_host_pipeline.cpp) and the CPU suite share.  The position-based UTF-8 rule they judge payloads by is fg_utf8.hpp's: a sequence
+// cut off by the end of a payload shows at the position behind it -- under this framing the next prefix's byte or the chunk's end --,
+// so the callers ask for position `len` itself and flag the frame that ends there.  No HIP, no wave primitives.
 #pragma once
 #include <stdint.h>
+
+#include "fg_utf8.hpp"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -53,20 +57,8 @@ FG_SLH Prefix parse_prefix(Get get, uint64_t p, uint64_t nbytes, uint64_t bound 
     return r;
 }
 
-// UTF-8 well-formedness judged AT one byte from it and its three predecessors (0 before the payload): the rule of fg_frame.hip.
-// A sequence cut off by the end of a payload shows at the position behind it (b = 0): under this framing that byte is the next
-// prefix's or the chunk's end, so the caller asks for position `len` itself and flags the frame that ends there.
-FG_SLH bool utf8_err_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3) {
-    const bool c1 = (p1 & 0xC0u) == 0x80u, c2 = (p2 & 0xC0u) == 0x80u;
-    const bool must = p1 >= 0xC0u || (p2 >= 0xE0u && c1) || (p3 >= 0xF0u && c2 && c1);
-    bool err = ((b & 0xC0u) == 0x80u) != must;
-    err |= b == 0xC0u || b == 0xC1u || b >= 0xF5u;
-    err |= p1 == 0xE0u && !(b & 0x20u);
-    err |= p1 == 0xEDu && (b & 0x20u);
-    err |= p1 == 0xF0u && !(b & 0x30u);
-    err |= p1 == 0xF4u && (b & 0x30u);
-    return err;
-}
+// (the rule under the name it had while it lived here: test hosts written against that name keep compiling)
+FG_SLH bool utf8_err_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3) { return utf8::err_at(b, p1, p2, p3); }
 
 // The sequential walk (what the device logic must reproduce, and the host hop of the entry points that take host buffers): frames
 // into `starts` / `plens` while they fit `cap`; returns the stop reason.  bound as parse_prefix.

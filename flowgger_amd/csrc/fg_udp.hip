@@ -68,9 +68,8 @@ __global__ __launch_bounds__(64) void k_udp_write(const uint8_t* __restrict__ by
     }
 }
 
-// whether src[0 .. len) is NOT valid UTF-8, by the whole wave (to every lane that saw an offence); the rule of fg_frame.hip
+// whether src[0 .. len) is NOT valid UTF-8, by the whole wave (to every lane that saw an offence); the rule of fg_utf8.hpp
 FG_WV bool utf8_bad(const uint8_t* src, uint32_t len) {
-    using fg::syslen::utf8_err_at;
     const uint32_t l = wv::lane();
     bool bad = false;
     for (uint32_t i = l * 16u; i <= len; i += wv::kLanes * 16u) {  // (<=: the lane behind the last byte sees a sequence cut off there)
@@ -87,7 +86,7 @@ FG_WV bool utf8_bad(const uint8_t* src, uint32_t len) {
             const uint32_t upto = nb < 16u ? nb + 1u : (i + 16u == len ? 17u : 16u);  // position len itself (when len is a multiple of 16 the next lane, with nb == 0, judges it again: same verdict)
             for (uint32_t k = 0; k < upto; ++k) {
                 const uint32_t b = k < nb ? (q[k >> 2] >> (8u * (k & 3u))) & 0xFFu : 0u;
-                bad |= utf8_err_at(b, p1, p2, p3);
+                bad |= fg::utf8::err_at(b, p1, p2, p3);
                 p3 = p2; p2 = p1; p1 = b;
             }
         }

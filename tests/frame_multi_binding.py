@@ -13,7 +13,7 @@ from frame_multi_model import Slots
 HERE = Path(__file__).resolve().parent / "native"
 ROOT = HERE.parent.parent
 LIB = HERE / "libframe_multi_host.so"
-SRC = [HERE / "frame_multi_host.cpp", ROOT / "flowgger_amd" / "csrc" / "fg_frame_multi.hpp"]
+SRC = [HERE / "frame_multi_host.cpp", ROOT / "flowgger_amd" / "csrc" / "fg_frame_multi.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_utf8.hpp"]
 
 
 def build() -> Path:

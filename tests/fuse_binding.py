@@ -12,7 +12,7 @@ HERE = Path(__file__).resolve().parent / "native"
 ROOT = HERE.parent.parent
 LIB = HERE / "libfuse_host.so"
 SRC = [HERE / "fuse_host.cpp", HERE / "fg_wave_emu.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_fuse.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_wave.hpp",
-       ROOT / "flowgger_amd" / "csrc" / "fg_fused_plan.hpp"]
+       ROOT / "flowgger_amd" / "csrc" / "fg_fused_plan.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_utf8.hpp"]
 
 
 def build() -> Path:
@@ -60,3 +60,23 @@ class FuseHost:
         if r < 0:
             raise RuntimeError(self.lib.fgf_last_error().decode())
         return starts[:r], ends[:r], bad[:r], int(consumed.value), int(passes.value), int(scans.value)
+
+    def chunk_masks(self, chunk: bytes, pw: bytes, delim: int, rem: int) -> int:
+        """fuse::chunk_masks of one 16-byte chunk behind the dword pw: delimiter mask | UTF-8 error mask << 16"""
+        q = (C.c_uint32 * 4)(*np.frombuffer(chunk, "<u4"))
+        self.lib.fgf_chunk_masks.restype = C.c_uint32
+        return int(self.lib.fgf_chunk_masks(q, C.c_uint32(int.from_bytes(pw, "little")), C.c_uint32(delim), C.c_int32(rem)))
+
+    def scalar_bad4(self, alphabet: bytes) -> np.ndarray:
+        """the scalar rule's verdict (fg::utf8::payload_bad) on every four-byte string over the alphabet, in itertools.product order"""
+        out = np.zeros(len(alphabet) ** 4, np.uint8)
+        self.lib.fgf_scalar_bad4(C.c_char_p(alphabet), C.c_uint32(len(alphabet)), C.c_void_p(out.ctypes.data))
+        return out
+
+    def rule_sweep(self, alphabet: bytes, rems, delim: int):
+        """fgf_rule_sweep -> (triples that differ, the first one (string index, phase, rem, got, want), (triples, error bits, delimiter bits))"""
+        r = (C.c_int32 * len(rems))(*rems)
+        first, stats = (C.c_int64 * 5)(), (C.c_uint64 * 3)()
+        self.lib.fgf_rule_sweep.restype = C.c_uint64
+        wrong = self.lib.fgf_rule_sweep(C.c_char_p(alphabet), C.c_uint32(len(alphabet)), r, C.c_uint32(len(rems)), C.c_uint32(delim), first, stats)
+        return int(wrong), tuple(int(x) for x in first), tuple(int(x) for x in stats)

@@ -50,9 +50,8 @@ long fgm_frame(const uint8_t* bytes, uint64_t nbytes, uint32_t delim, const uint
     // the scan, unpatched
     std::vector<uint8_t> D(nbytes + 1, 0), E(nbytes + 1, 0);
     for (uint64_t x = 0; x <= nbytes; ++x) {
-        const uint32_t b = x < nbytes ? bytes[x] : 0u;
-        if (x < nbytes) D[x] = b == delim;
-        E[x] = utf8_err_at(b, x >= 1 ? bytes[x - 1] : 0u, x >= 2 ? bytes[x - 2] : 0u, x >= 3 ? bytes[x - 3] : 0u);
+        if (x < nbytes) D[x] = bytes[x] == delim;
+        E[x] = fg::utf8::err_at_pos(bytes, nbytes, x);
     }
     uint64_t new_delims = 0;
     if (nbytes && n_segs >= 2) {

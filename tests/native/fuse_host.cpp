@@ -2,7 +2,8 @@
 // kernels do -- stage [T * S - 16, T * S + S + look), per 16-byte chunk a delimiter | UTF-8 error word, count, list, lines, the tail that
 // runs past the staged range -- with the wave-level steps on the fiber emulation of a wavefront (tests/native/fg_wave_emu.hpp), and
 // hands back the frames it found: start, end (terminator included), UTF-8 verdict.  tests/test_fuse_cpu.py compares them with the
-// oracle's restatement of the splitters (fgo_frame).  Test infrastructure only.
+// oracle's restatement of the splitters (fgo_frame).  At the end: the chunk classifier by itself (fuse::chunk_masks) and its sweep against
+// the scalar form of the UTF-8 rule (fg_utf8.hpp) for tests/test_utf8_rule_cpu.py.  Test infrastructure only.
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../flowgger_amd/csrc/fg_fuse.hpp"
+#include "../../flowgger_amd/csrc/fg_utf8.hpp"
 
 namespace {
 using namespace fg;
@@ -151,4 +153,57 @@ extern "C" long fgf_frame(const uint8_t* bytes, uint64_t nbytes, uint32_t delim,
         g_err = e.what();
         return -1;
     }
+}
+
+// ---- the two forms of the UTF-8 rule (tests/test_utf8_rule_cpu.py) ---------------------------------------------------------------------
+extern "C" uint32_t fgf_chunk_masks(const uint32_t q[4], uint32_t pw, uint32_t delim, int32_t rem) {
+    return fuse::chunk_masks(q[0], q[1], q[2], q[3], pw, delim * 0x01010101u, rem);
+}
+// the scalar rule's verdict on every four-byte string over the alphabet a[0 .. na): out[((i0 * na + i1) * na + i2) * na + i3]
+extern "C" void fgf_scalar_bad4(const uint8_t* a, uint32_t na, uint8_t* out) {
+    for (uint32_t i = 0, n4 = na * na * na * na; i < n4; ++i) {
+        const uint8_t s[4] = {a[i / (na * na * na)], a[i / (na * na) % na], a[i / na % na], a[i % na]};
+        out[i] = utf8::payload_bad(s, 4) ? 1 : 0;
+    }
+}
+// chunk_masks against the scalar rule and a byte compare, position by position.  Every four-byte string s over the alphabet, at every
+// phase o = 0 .. 3: the predecessor dword and the chunk are s repeated, buf[i] = s[(i + o) % 4] for the twenty bytes pw | chunk -- s
+// itself starts at byte (4 - o) % 4 of the chunk and again in every dword behind it, and the predecessor dword is a rotation of s (a
+// string over the same alphabet).  For every rem of rems[0 .. nrems): bits at positions > rem must be clear, bytes at and behind rem
+// read as 0 (so the bit AT rem is the scalar rule with b = 0), rem = -1 gives nothing.  Returns the number of (s, o, rem) triples whose
+// word differs; the first such triple -> first[0 .. 5) = string index, o, rem, got, want; stats[0] = triples compared, stats[1] = error
+// bits expected in all, stats[2] = delimiter bits expected in all.
+extern "C" uint64_t fgf_rule_sweep(const uint8_t* a, uint32_t na, const int32_t* rems, uint32_t nrems, uint32_t delim, int64_t first[5],
+                                   uint64_t stats[3]) {
+    uint64_t wrong = 0;
+    stats[0] = stats[1] = stats[2] = 0;
+    for (uint32_t i = 0, n4 = na * na * na * na; i < n4; ++i) {
+        const uint8_t s[4] = {a[i / (na * na * na)], a[i / (na * na) % na], a[i / na % na], a[i % na]};
+        for (uint32_t o = 0; o < 4u; ++o) {
+            uint8_t buf[20];  // buf[4 + j] = chunk byte j
+            for (uint32_t k = 0; k < 20u; ++k) buf[k] = s[(k + o) % 4u];
+            uint32_t w[5];
+            memcpy(w, buf, 20);
+            // the scalar rule at chunk position j with the byte itself (full) and with the byte read as 0 (zero); the byte compare
+            uint32_t full = 0, zero = 0, eq = 0;
+            for (uint32_t j = 0; j < 16u; ++j) {
+                const uint8_t* b = buf + 4u + j;
+                full |= (utf8::err_at(b[0], b[-1], b[-2], b[-3]) ? 1u : 0u) << j;
+                zero |= (utf8::cut_off(b[-1], b[-2], b[-3]) ? 1u : 0u) << j;
+                eq |= (b[0] == delim ? 1u : 0u) << j;
+            }
+            for (uint32_t r = 0; r < nrems; ++r) {
+                const int32_t rem = rems[r];
+                uint32_t want = 0;
+                if (rem >= 16) want = eq | (full << 16);
+                else if (rem >= 0) want = (eq & ((1u << rem) - 1u)) | (((full & ((1u << rem) - 1u)) | (zero & (1u << rem))) << 16);
+                const uint32_t got = fuse::chunk_masks(w[1], w[2], w[3], w[4], w[0], delim * 0x01010101u, rem);
+                ++stats[0];
+                stats[1] += (uint64_t)__builtin_popcount(want >> 16);
+                stats[2] += (uint64_t)__builtin_popcount(want & 0xFFFFu);
+                if (got != want && wrong++ == 0) first[0] = i, first[1] = o, first[2] = rem, first[3] = got, first[4] = want;
+            }
+        }
+    }
+    return wrong;
 }

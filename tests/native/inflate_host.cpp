@@ -3,7 +3,7 @@
 #include <vector>
 
 #include "fg_inflate.hpp"
-#include "fg_syslen_parse.hpp"
+#include "fg_utf8.hpp"
 
 using namespace fg::inflate;
 
@@ -22,12 +22,10 @@ extern "C" uint32_t fgi_unpack(const uint8_t* p, uint64_t len, uint32_t max_infl
     st = write_datagram(p, len, st, *size, t, out);
     *drop = st > UDP_GZIP;
     if (*drop) return st;
-    const uint32_t n = *size;
-    for (uint32_t i = 0; i <= n; ++i)
-        if (fg::syslen::utf8_err_at(i < n ? out[i] : 0u, i >= 1 ? out[i - 1] : 0u, i >= 2 ? out[i - 2] : 0u, i >= 3 ? out[i - 3] : 0u)) {
-            *drop = 1;
-            return UDP_BAD_UTF8;
-        }
+    if (fg::utf8::payload_bad(out, *size)) {
+        *drop = 1;
+        return UDP_BAD_UTF8;
+    }
     return st;
 }
 

@@ -16,11 +16,7 @@ extern "C" void fgs_parse(const uint8_t* bytes, uint64_t nbytes, uint64_t p, uin
     const Prefix pr = parse_prefix([&](uint64_t a) { return (uint32_t)bytes[a]; }, p, nbytes, bound);
     out[0] = pr.st; out[1] = pr.plen; out[2] = pr.len;
 }
-extern "C" int fgs_utf8_bad(const uint8_t* b, uint64_t n) {
-    for (uint64_t i = 0; i <= n; ++i)
-        if (utf8_err_at(i < n ? b[i] : 0u, i >= 1 ? b[i - 1] : 0u, i >= 2 ? b[i - 2] : 0u, i >= 3 ? b[i - 3] : 0u)) return 1;
-    return 0;
-}
+extern "C" int fgs_utf8_bad(const uint8_t* b, uint64_t n) { return fg::utf8::payload_bad(b, n) ? 1 : 0; }
 
 // bytes: readable up to nbytes rounded up to 16.  hdr: H_WORDS words out.  Returns 0, or -1 on a wave divergence.
 extern "C" int fgs_frame(const uint8_t* bytes, uint64_t nbytes, uint8_t* packed, uint64_t* offsets, uint64_t* starts, uint8_t* bad,

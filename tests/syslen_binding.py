@@ -12,7 +12,7 @@ HERE = Path(__file__).resolve().parent / "native"
 ROOT = HERE.parent.parent
 LIB = HERE / "libsyslen_host.so"
 SRC = [HERE / "syslen_host.cpp", HERE / "fg_wave_emu.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_syslen.hpp",
-       ROOT / "flowgger_amd" / "csrc" / "fg_wave.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_syslen_parse.hpp"]
+       ROOT / "flowgger_amd" / "csrc" / "fg_wave.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_syslen_parse.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_utf8.hpp"]
 
 CLEAN, TAIL, BAD_LEN, LONG_PREFIX, VALID = range(5)
 U64_MAX = (1 << 64) - 1

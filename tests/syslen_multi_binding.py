@@ -13,7 +13,7 @@ ROOT = HERE.parent.parent
 CSRC = ROOT / "flowgger_amd" / "csrc"
 LIB = HERE / "libsyslen_multi_host.so"
 SRC = [HERE / "syslen_multi_host.cpp", HERE / "fg_wave_emu.hpp", CSRC / "fg_syslen_multi.hpp", CSRC / "fg_syslen.hpp", CSRC / "fg_wave.hpp",
-       CSRC / "fg_syslen_parse.hpp", CSRC / "fg_frame_multi.hpp"]
+       CSRC / "fg_syslen_parse.hpp", CSRC / "fg_frame_multi.hpp", CSRC / "fg_utf8.hpp"]
 GUARD = 0xEE
 U64_GUARD = 0xEEEEEEEEEEEEEEEE
 

@@ -17,7 +17,7 @@ ROOT = Path(__file__).resolve().parent.parent
 HERE = ROOT / "tests" / "native"
 LIB = HERE / "libhost_pipeline_fake.so"
 SRC = [HERE / "host_pipeline_fake.cpp", HERE / "fakehip/hip/hip_runtime.h"] + [ROOT / "flowgger_amd/csrc" / f for f in
-                                                                                ("fg_capi.cpp", "fg_host_pipeline.cpp", "fg_ctx.hpp", "fg_table_cols.hpp", "fg_fused_plan.hpp", "fg_tile_cap.hpp", "fg_gather.cpp", "fg_materialize.cpp")] + [ROOT / "include/fg_hip.h"]
+                                                                                ("fg_capi.cpp", "fg_host_pipeline.cpp", "fg_ctx.hpp", "fg_table_cols.hpp", "fg_fused_plan.hpp", "fg_tile_cap.hpp", "fg_gather.cpp", "fg_materialize.cpp", "fg_syslen_parse.hpp", "fg_utf8.hpp")] + [ROOT / "include/fg_hip.h"]
 u64, vp = C.c_uint64, C.c_void_p
 COLS = ["meta", "ts", "hostname", "appname", "procid", "msgid", "msg", "full_msg", "ent_count"]
 

@@ -17,7 +17,7 @@ import numpy as np
 HERE = Path(__file__).resolve().parent / "native"
 ROOT = HERE.parent.parent
 LIB = HERE / "libinflate_host.so"
-SRC = [HERE / "inflate_host.cpp", ROOT / "flowgger_amd" / "csrc" / "fg_inflate.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_syslen_parse.hpp"]
+SRC = [HERE / "inflate_host.cpp", ROOT / "flowgger_amd" / "csrc" / "fg_inflate.hpp", ROOT / "flowgger_amd" / "csrc" / "fg_utf8.hpp"]
 
 RAW, ZLIB, GZIP, BAD_ZLIB, BAD_GZIP, BAD_UTF8, TOO_LARGE = range(7)
 DEFAULT_MAX = 65_527 * 5
