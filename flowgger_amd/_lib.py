@@ -98,6 +98,7 @@ FG_PATH_FRAME_SYSLEN_DEVICE, FG_PATH_FRAME_SYSLEN_HOST = 6, 7
 FG_PATH_FRAME_CAPNP_DEVICE, FG_PATH_FRAME_CAPNP_HOST = 8, 9
 FG_PATH_FRAME_MULTI = 10
 FG_PATH_FRAME_SYSLEN_MULTI_DEVICE, FG_PATH_FRAME_SYSLEN_MULTI_HOST = 11, 12
+FG_PATH_FRAME_CAPNP_MULTI_DEVICE, FG_PATH_FRAME_CAPNP_MULTI_HOST = 13, 14
 FG_SLOT_FRAME, FG_SLOT_BAD_UTF8, FG_SLOT_CARRY = 0, 1, 2  # fg_slot_kind
 FG_LO_RESERVED = 0x40000000  # the library's own (fg_set_launch_opts clears it)
 
@@ -207,6 +208,9 @@ def lib() -> C.CDLL:
     L.fg_frame_syslen_multi_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
     L.fg_frame_decode_syslen_multi_batch.argtypes = [vp, C.c_int, vp, u64, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp),
                                                      C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.fg_frame_capnp_multi_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
+    L.fg_frame_decode_capnp_multi_batch.argtypes = [vp, vp, u64, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                    C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

@@ -28,7 +28,7 @@ VARIANT_DEFS = os.environ.get("FG_BUILD_DEFS", "").split()
 LIB = ROOT / (f"libfg_hip_{VARIANT}.so" if VARIANT else "libfg_hip_prof.so" if PROF else "libfg_hip.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip", "fg_capnp.hip", "fg_syslen.hip", "fg_udp.hip", "fg_capnp_frame.hip", "fg_frame_multi.hip", "fg_syslen_multi.hip"]
+HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip", "fg_capnp.hip", "fg_syslen.hip", "fg_udp.hip", "fg_capnp_frame.hip", "fg_frame_multi.hip", "fg_syslen_multi.hip", "fg_capnp_frame_multi.hip"]
 HIP_HOST_SOURCES = ["fg_capi.cpp", "fg_host_pipeline.cpp"]  # host code that needs the HIP headers / launch syntax
 CXX_SOURCES = ["fg_materialize.cpp", "fg_gather.cpp"]
 
@@ -250,6 +250,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         if " fg_launch_capnp_frame\n" not in syms:
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without fg_launch_capnp_frame (fg_capnp_frame.hip)")
+        if " fg_launch_capnp_frame_multi\n" not in syms:
+            LIB.unlink()
+            raise RuntimeError("libfg_hip was linked without fg_launch_capnp_frame_multi (fg_capnp_frame_multi.hip)")
         if " fg_launch_frame_multi\n" not in syms:
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without fg_launch_frame_multi (fg_frame_multi.hip)")

@@ -563,6 +563,41 @@ int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, 
     return FG_OK;
 }
 
+// ... for the chunks of n_segs connections at once (a CapnpSplitter per connection: input/tcp/tcp_input.rs:39-47)
+int fg_frame_capnp_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs,
+                                uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap_slots, uint64_t* d_seg_first, uint64_t* d_seg_consumed,
+                                uint8_t* d_seg_stop, uint64_t* n_slots, void* stream) {
+    if (!ctx || !d_offsets || !n_slots || (nbytes && !d_bytes) || (cap_slots && !d_kind)) return FG_ERR_ARG;
+    if (n_segs ? (!d_seg_starts || !d_seg_first || !d_seg_consumed || !d_seg_stop) : nbytes != 0) return FG_ERR_ARG;
+    if (((uintptr_t)d_bytes & 15u) != 0) return FG_ERR_ARG;
+    *n_slots = 0;
+    if (nbytes > FG_CAPNP_FRAME_MAX_BYTES || n_segs > (1ull << 24)) return FG_ERR_ARG;  // (word indices in 29 bits, node numbers in 32)
+    if (!fg_launch_capnp_frame_multi || !fg_capnp_frame_multi_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (nbytes == 0) {  // no slots: every segment is empty and CLEAN
+        FG_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s));
+        if (n_segs) {
+            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
+            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
+            FG_HIP(ctx, hipMemsetAsync(d_seg_stop, FG_CAPNP_CLEAN, n_segs, s));
+        }
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_capnp_frame_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
+    uint32_t* d_hdr = nullptr;
+    FG_LAUNCH(ctx, fg_launch_capnp_frame_multi(d_bytes, nbytes, d_seg_starts, n_segs, ctx->d_frame, d_offsets, d_kind, cap_slots, d_seg_first,
+                                                d_seg_consumed, d_seg_stop, &d_hdr, s));
+    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (hdr[0] != 0 || hdr[4] != 1) return FG_ERR_UNSUPPORTED;  // declined: more nodes than the store holds
+    *n_slots = hdr[2];
+    return hdr[2] > cap_slots ? FG_ERR_ENT_OVERFLOW : FG_OK;
+}
+
 const char* fg_udp_error_string(uint8_t st) {
     switch (st) {
         case FG_UDP_RAW:
@@ -699,7 +734,7 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
             break;
         case FG_CAPNP:
             if (!fg_launch_capnp) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernel: fg_ctx.hpp)
-            rc = fg_launch_capnp(d_bytes, d_offsets, n, &dt, avg_len, s, &lo_call, tk);
+            rc = fg_launch_capnp(d_bytes, d_offsets, n, &dt, avg_len, s, d_bad_utf8, &lo_call, tk);
             break;
         default:
             return FG_ERR_UNSUPPORTED;

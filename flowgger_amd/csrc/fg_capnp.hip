@@ -86,10 +86,10 @@ __global__ __launch_bounds__(kWave, 2) void k_capnp(const uint8_t* __restrict__ 
 }  // namespace fg
 
 extern "C" int fg_launch_capnp(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, uint64_t avg_len,
-                               hipStream_t stream, const fg_launch_opts* lo, fg::TicketSlot* tk) {
+                               hipStream_t stream, const uint8_t* line_bad, const fg_launch_opts* lo, fg::TicketSlot* tk) {
     if (n == 0) return 0;
     const auto ks = fg::kernels(fg::k_capnp<fg::kWindowKiB, false>, FG_PROF_TWIN(fg::k_capnp<fg::kWindowKiB, true>), "capnp");
-    return fg::plan_and_launch(ks, fg::DecodeCall{n, t, stream, fg::FrameArgs{FG_FRAME_NONE, nullptr}, lo, tk}, avg_len, 0u, fg::kMaxTile, 0u,
+    return fg::plan_and_launch(ks, fg::DecodeCall{n, t, stream, fg::FrameArgs{FG_FRAME_NONE, line_bad}, lo, tk}, avg_len, 0u, fg::kMaxTile, 0u,
                                fg::PlanFormat().classes(0u),
                                [&](auto k, const fg::LaunchPlan& p, const fg::DevTables& tt, const fg::FrameArgs& fr, unsigned long long* prof) {
                                    hipLaunchKernelGGL(k, dim3(p.blocks), dim3(fg::kWave), p.lds, stream, d_bytes, d_offsets, n, tt, p.tile, p.L, p.chunk,

@@ -38,7 +38,8 @@ constexpr uint32_t kNodeMin = 64;
 constexpr uint32_t kNil = 0xFFFFFFFFu;
 constexpr uint64_t kMaxBytes = 0xFFFF0000ull;    // word indices and a 3-bit kind share a 32-bit word of the scratch
 constexpr uint32_t kKindShift = 29, kPosMask = (1u << kKindShift) - 1u;
-enum { K_EXIT = 4, K_HOP = 5 };                  // kinds of a word beyond the four stop reasons: its message leaves / stays in the tile
+enum { K_EXIT = 4, K_HOP = 5, K_END = 6 };       // kinds of a word beyond the four stop reasons: its message leaves / stays in the tile /
+                                                 // ends exactly on its SEGMENT's end (fg_capnp_frame_multi.hpp only): counted, no exit, no hop
 // the result words of a launch
 enum { H_DECLINE = 0, H_STOP = 1, H_NFRAMES = 2, H_CONSUMED = 3 /* a word index */, H_DONE = 4, H_NODES = 5, H_WORDS = 16 };
 
@@ -101,6 +102,19 @@ FG_WV void load16(const uint8_t* p, uint32_t q[4]) { memcpy(q, p, 16); }
 FG_WV uint32_t load4(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
 #endif
 
+// What a word may reach to and which words start a stream: the whole chunk and word 0 here.  The segmented framer
+// (fg_capnp_frame_multi.hpp) instantiates the stages below with the end of the SEGMENT that holds the word and every segment's start.
+struct Whole {
+    static constexpr bool kSegmented = false;
+    uint64_t nbytes;
+    struct Tile {
+        uint64_t lim;
+        FG_WV uint64_t limit(uint64_t) const { return lim; }
+    };
+    FG_WV Tile tile(uint64_t) const { return Tile{nbytes}; }
+    FG_WV bool root(uint32_t w) const { return w == 0u; }
+};
+
 // LDS of the three tile stages, in dwords: the tile | nx | c | fin | the tile's bitmap slice, its prefix popcounts, four state words
 constexpr uint32_t kLdsTile = kTileBytes / 4u;
 constexpr uint32_t kLdsWords = kLdsTile + 3u * kTileWords + 2u * kBmWords + 4u;
@@ -122,7 +136,8 @@ FG_WV Lds lds_of(uint32_t* lds) {
 // Every word i of the tile: nx[i] = the word of the tile its message ends at and c[i] = 1 (K_HOP), or nx[i] = i and c[i] = 0 (the
 // message leaves the tile, K_EXIT, or none starts here: a stop reason); fin[i] = kind << 29 | that word (the word itself for a stop).
 // All 64 lanes; ends with a barrier.
-FG_WV void resolve_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Lds& m) {
+template <class Span>
+FG_WV void resolve_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Lds& m, const Span& span) {
     const uint32_t l = wv::lane();
     const uint64_t base_w = (uint64_t)tile * kTileWords, base_b = base_w * 8ull, end_b = base_b + kTileBytes;
     const uint64_t lim = (nbytes + 15ull) & ~15ull;
@@ -134,25 +149,30 @@ FG_WV void resolve_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, co
     wv::sync();
     // (a table that runs past the tile: its sizes lie inside the chunk -- next_at checks that before it asks for them)
     auto get32 = [&](uint64_t p) { return p < end_b ? m.tw[(uint32_t)(p - base_b) >> 2] : load4(bytes + p); };
+    const typename Span::Tile here = span.tile(base_b);
     for (uint32_t j = 0; j < kTileWords / wv::kLanes; ++j) {
         const uint32_t i = j * wv::kLanes + l;
         const uint64_t w = base_w + i;
-        const Next r = next_at(get32, w, nbytes);
+        const uint64_t reach = here.limit(w * 8ull);  // the end of the chunk, or of the segment that holds w
+        const Next r = next_at(get32, w, reach);
         uint32_t nx = i, c = 0u, fin = (r.st << kKindShift) | (uint32_t)w;
         if (r.st == ST_VALID) {
             const uint64_t x = w + r.words;
-            if (x < base_w + kTileWords) { nx = (uint32_t)(x - base_w); c = 1u; fin = ((uint32_t)K_HOP << kKindShift) | (uint32_t)x; }
+            if (Span::kSegmented && x * 8ull == reach) fin = ((uint32_t)K_END << kKindShift) | (uint32_t)x;
+            else if (x < base_w + kTileWords) { nx = (uint32_t)(x - base_w); c = 1u; fin = ((uint32_t)K_HOP << kKindShift) | (uint32_t)x; }
             else fin = ((uint32_t)K_EXIT << kKindShift) | (uint32_t)x;
         }
         m.nx[i] = nx; m.c[i] = c; m.fin[i] = fin;
     }
     wv::sync();
 }
+FG_WV void resolve_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Lds& m) { resolve_tile(bytes, nbytes, tile, m, Whole{nbytes}); }
 
 // ---- 1: mark.  All 64 lanes; `lds` = kLdsWords dwords. -------------------------------------------------------------------------
-FG_WV void mark_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+template <class Span>
+FG_WV void mark_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds, const Span& span) {
     const Lds m = lds_of(lds);
-    resolve_tile(bytes, nbytes, tile, m);
+    resolve_tile(bytes, nbytes, tile, m, span);
     const uint32_t l = wv::lane();
     for (uint32_t j = 0; j < kTileWords / wv::kLanes; ++j) {
         const uint32_t f = m.fin[j * wv::kLanes + l];
@@ -160,6 +180,9 @@ FG_WV void mark_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const
         const uint32_t x = f & kPosMask;  // (<= words_of(nbytes): the message fits the chunk)
         g_or32(&sc.bitmap[x >> 5], 1u << (x & 31u));
     }
+}
+FG_WV void mark_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+    mark_tile(bytes, nbytes, tile, sc, lds, Whole{nbytes});
 }
 
 // how many marked words of a tile lie before its word i (bm = the tile's kBmWords dwords of the bitmap)
@@ -170,7 +193,8 @@ FG_WV uint32_t rank_in_tile(const uint32_t* bm, uint32_t i) {
 }
 
 // ---- 2: nodes.  All 64 lanes; `lds` = kLdsWords dwords. ------------------------------------------------------------------------
-FG_WV void nodes_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+template <class Span>
+FG_WV void nodes_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds, const Span& span) {
     const Lds m = lds_of(lds);
     const uint32_t l = wv::lane();
     if (l < kBmWords) m.sb[l] = sc.bitmap[(uint64_t)tile * kBmWords + l];
@@ -193,7 +217,7 @@ FG_WV void nodes_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, cons
     wv::sync();
     const uint32_t first = m.st[0], total = m.st[1];
     if (total == 0u) return;  // (wave-uniform)
-    resolve_tile(bytes, nbytes, tile, m);
+    resolve_tile(bytes, nbytes, tile, m, span);
     for (uint32_t r = 0; r < kDoubling; ++r) {
         uint32_t n2[kTileWords / wv::kLanes], c2[kTileWords / wv::kLanes];
 #pragma unroll
@@ -216,16 +240,21 @@ FG_WV void nodes_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, cons
         if (!((m.sb[i >> 5] >> (i & 31u)) & 1u)) continue;
         const uint32_t u = first + m.pre[i >> 5] + wv::popc32(m.sb[i >> 5] & ((1u << (i & 31u)) - 1u));
         const uint32_t f = m.fin[m.nx[i]];
-        const uint32_t cnt = m.c[i] + ((f >> kKindShift) == (uint32_t)K_EXIT ? 1u : 0u);
+        const uint32_t kind = f >> kKindShift;
+        const uint32_t cnt = m.c[i] + (kind == (uint32_t)K_EXIT || (Span::kSegmented && kind == (uint32_t)K_END) ? 1u : 0u);
         sc.nd_pos[u] = tile * kTileWords + i;
         sc.nd_fin[u] = f;
         sc.nd_cnt[u] = cnt;
         sc.jf0[u] = cnt;
     }
 }
+FG_WV void nodes_tile(const uint8_t* bytes, uint64_t nbytes, uint32_t tile, const Scratch& sc, uint32_t* lds) {
+    nodes_tile(bytes, nbytes, tile, sc, lds, Whole{nbytes});
+}
 
 // ---- 3: one thread per node slot ---------------------------------------------------------------------------------------------------
-FG_WV void link_node(uint32_t u, const Scratch& sc) {
+template <class Span>
+FG_WV void link_node(uint32_t u, const Scratch& sc, const Span& span) {
     if (sc.hdr[H_DECLINE] != 0u || u >= sc.hdr[H_NODES]) return;
     const uint32_t f = sc.nd_fin[u];
     uint32_t next = kNil;
@@ -236,8 +265,9 @@ FG_WV void link_node(uint32_t u, const Scratch& sc) {
         else g_or32(&sc.hdr[H_DECLINE], 2u);  // (never: the mark stage set the bit of every exit)
     }
     sc.jn0[u] = next;
-    if (sc.nd_pos[u] == 0u) { sc.mk_stamp[u] = 1u; sc.mk_f[u] = 0u; }  // the stream's own start
+    if (span.root(sc.nd_pos[u])) { sc.mk_stamp[u] = 1u; sc.mk_f[u] = 0u; }  // the start of a stream of its own
 }
+FG_WV void link_node(uint32_t u, const Scratch& sc) { link_node(u, sc, Whole{0}); }
 
 // ---- 4: round r = 1 .. rounds of the ranking, one thread per node slot -------------------------------------------------------------
 FG_WV void jump_round(uint32_t u, uint32_t r, const Scratch& sc) {

@@ -46,7 +46,7 @@ extern "C" int fg_launch_rfc3164(const uint8_t* d_bytes, const uint64_t* d_offse
 // (a WEAK reference: the CPU suite links the host side of the C ABI against fake launchers -- tests/native/host_pipeline_fake.cpp --
 //  which have none for this format; FG_CAPNP then answers FG_ERR_UNSUPPORTED.  The product library always has the kernel.)
 extern "C" int fg_launch_capnp(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t, uint64_t avg_len,
-                               hipStream_t stream, const fg_launch_opts* lo, fg::TicketSlot* tk) __attribute__((weak));
+                               hipStream_t stream, const uint8_t* line_bad, const fg_launch_opts* lo, fg::TicketSlot* tk) __attribute__((weak));
 extern "C" uint64_t fg_rfc3164_scratch_bytes(uint64_t n);
 extern "C" uint64_t fg_rfc3164_regroup_from(void);   // lines from which the library regroups by itself  // the regrouped form's scratch: shape keys, block counts, the line permutation
 extern "C" int fg_launch_encode_sizes(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const fg::DevTables* t,
@@ -103,6 +103,14 @@ extern "C" int fg_launch_syslen_multi(const uint8_t* d_bytes, uint64_t nbytes, c
                                       uint8_t* d_packed, uint64_t* d_offsets, uint64_t* d_starts, uint8_t* d_bad, uint64_t cap,
                                       uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop, uint32_t** d_hdr_out,
                                       hipStream_t stream) __attribute__((weak));
+// the segmented Cap'n Proto framer (fg_capnp_frame_multi.hip): *d_hdr_out = its result words in device memory (fg::capnpf H_DECLINE,
+// H_NFRAMES = the slots, H_DONE).  (WEAK references, as fg_launch_syslen above: without the kernels fg_frame_capnp_multi_device answers
+// FG_ERR_UNSUPPORTED and fg_frame_decode_capnp_multi_batch walks the segments on the host.  The product library always has them:
+// build.py checks the link.)
+extern "C" uint64_t fg_capnp_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t n_segs) __attribute__((weak));
+extern "C" int fg_launch_capnp_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs, uint8_t* scratch,
+                                           uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first, uint64_t* d_seg_consumed,
+                                           uint8_t* d_seg_stop, uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,

@@ -1271,6 +1271,119 @@ extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, co
     return rc;
 }
 
+// The CAP'N PROTO chunks of many connections in one buffer (a CapnpSplitter per connection, capnp_splitter.rs:24-46): upload once, frame
+// every segment as its own stream on the device, decode the messages where they lie with the slot kinds as the skip array (a CARRY slot
+// is a skipped row).  When the device framer declines (fg_frame_capnp_multi_device: FG_ERR_UNSUPPORTED) the segments are walked on the
+// host over the caller's bytes and the slots are uploaded: the same results either way.
+extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
+                                                 fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
+                                                 const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop,
+                                                 uint64_t* n_slots) {
+    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_slots || (nbytes && !bytes))
+        return FG_ERR_ARG;
+    if (n_segs && !seg_starts) return FG_ERR_ARG;
+    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
+    for (uint64_t k = 0; k < n_segs; ++k)
+        if (seg_starts[k] > seg_starts[k + 1] || (seg_starts[k] & 7u) != 0) return FG_ERR_ARG;  // (the framer works on words of the buffer)
+    if (nbytes > FG_CAPNP_FRAME_MAX_BYTES || n_segs > (1ull << 24)) return FG_ERR_ARG;
+    *n_slots = 0;
+    *out = fg_tables{};
+    *out_offsets = nullptr;
+    *out_kind = nullptr;
+    *out_seg_first = nullptr;
+    *out_seg_consumed = nullptr;
+    *out_seg_stop = nullptr;
+    ctx->last_host_path = 0;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    // seg_starts | seg_first | seg_consumed | seg_stop on the device; seg_first | seg_consumed | seg_stop | offsets | kinds in the pinned mirror
+    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_stop = o_cons + up(n_segs * 8 + 8, 256);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_stop + up(n_segs + 1, 256))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
+    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
+    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
+    uint8_t* const d_stop = ctx->d_ms + o_stop;
+    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+    auto ensure = [&](uint64_t cap) -> int {
+        int r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
+        return grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1);
+    };
+    // 1. frame: a message of the record schema is a few hundred bytes (as capnp_stage), one tail per segment; exact on retry
+    uint64_t cap = nbytes / 64 + n_segs + 1024, n = 0;
+    for (;;) {
+        if ((rc = ensure(cap)) != FG_OK) return rc;
+        rc = fg_frame_capnp_multi_device(ctx, ctx->d_bytes, nbytes, d_starts, n_segs, ctx->d_offsets, ctx->d_bad, cap, d_first, d_cons, d_stop, &n,
+                                         FG_STREAM_OWN);
+        if (rc != FG_ERR_ENT_OVERFLOW) break;
+        cap = n + 16;
+    }
+    if (rc != FG_OK && rc != FG_ERR_UNSUPPORTED) return rc;
+    const bool device = rc == FG_OK;
+    std::vector<uint64_t> offs, first{0}, cons;
+    std::vector<uint8_t> kind, stop;
+    if (!device) {  // the host walk (what capnp_stage does for one chunk), segment by segment
+        for (uint64_t k = 0; k < n_segs; ++k) {
+            const uint64_t at = seg_starts[k], len = seg_starts[k + 1] - at;
+            uint64_t consumed = 0;
+            stop.push_back((uint8_t)fg::capnpf::host_walk(bytes + at, len, &consumed, [&](uint64_t p) {
+                offs.push_back(at + p);
+                kind.push_back(FG_SLOT_FRAME);
+            }));
+            if (consumed < len) {
+                offs.push_back(at + consumed);
+                kind.push_back(FG_SLOT_CARRY);
+            }
+            cons.push_back(consumed);
+            first.push_back(kind.size());
+        }
+        offs.push_back(nbytes);
+        n = kind.size();
+        if ((rc = ensure(n)) != FG_OK) return rc;
+    }
+    const uint64_t h_cons = o_first, h_stop = h_cons + up(n_segs * 8 + 8, 256), h_off = h_stop + up(n_segs + 1, 256), h_kind = h_off + up((n + 1) * 8, 256);
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_kind + up(n + 1, 256))) != FG_OK) return rc;
+    uint8_t* const h = ctx->h_ms;
+    if (device) {
+        if (n_segs) {
+            FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
+            FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
+            FG_HIP(ctx, hipMemcpyAsync(h + h_stop, d_stop, n_segs, hipMemcpyDeviceToHost, s));
+        } else {
+            memset(h, 0, 8);
+        }
+        FG_HIP(ctx, hipMemcpyAsync(h + h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_kind, ctx->d_bad, n, hipMemcpyDeviceToHost, s));
+    } else {
+        memcpy(h, first.data(), (n_segs + 1) * 8);
+        if (n_segs) memcpy(h + h_cons, cons.data(), n_segs * 8);
+        if (n_segs) memcpy(h + h_stop, stop.data(), n_segs);
+        memcpy(h + h_off, offs.data(), (n + 1) * 8);
+        if (n) memcpy(h + h_kind, kind.data(), n);
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, h + h_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, h + h_kind, n, hipMemcpyHostToDevice, s));
+    }
+    *n_slots = n;
+    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
+    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
+    *out_seg_stop = h + h_stop;
+    *out_offsets = reinterpret_cast<const uint64_t*>(h + h_off);
+    *out_kind = h + h_kind;
+    ctx->last_host_path = device ? FG_PATH_FRAME_CAPNP_MULTI_DEVICE : FG_PATH_FRAME_CAPNP_MULTI_HOST;
+    if (n == 0) {
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    // 2. decode the slots where they lie (a nonzero kind -> FG_ST_BAD_UTF8, not decoded)
+    rc = decode_stage_to_host(ctx, FG_CAPNP, FG_FRAME_NONE, nbytes, n, ctx->d_bad, ctx->d_bytes, out);
+    if (rc != FG_OK) ctx->last_host_path = 0;
+    return rc;
+}
+
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB
 // on the ctx's two streams, so that the upload of slice k+1 and the (2-3x larger) download of slice k's messages share the
 // full-duplex link, and the kernels hide behind both.  The host only waits for one small number per slice (its encoded size:

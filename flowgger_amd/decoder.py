@@ -388,6 +388,61 @@ class Decoder:
         seg_stop = np.ctypeslib.as_array(C.cast(stop, u8p), (K,)).copy() if K else np.zeros(0, np.uint8)
         return (HostTables.from_struct(st) if nf else None), frame_starts, seg_first, seg_cons, seg_stop
 
+    def frame_capnp_multi_device(self, d_bytes, d_seg_starts, cap_slots: Optional[int] = None, stream=None):
+        """fg_frame_capnp_multi_device: d_bytes holds the Cap'n Proto chunks of K connections back to back (segment k =
+        d_bytes[seg_starts[k]:seg_starts[k + 1]], torch int64 / uint64 [K + 1], every start but the last a multiple of 8); every
+        segment is walked as a stream of its own (a CapnpSplitter per connection, tcp_input.rs:39-47).  Returns (d_offsets int64[n + 1],
+        d_kind uint8[n], n_slots, d_seg_first int64[K + 1], d_seg_consumed int64[K], d_seg_stop uint8[K] (FG_CAPNP_*)): slot i =
+        d_bytes[offsets[i]:offsets[i + 1]], kind FG_SLOT_FRAME (a whole message) or FG_SLOT_CARRY (the bytes of a segment behind its
+        consumed); d_kind is decode_frames_device's d_bad as it is.  FgError(FG_ERR_UNSUPPORTED) when the device path declines the
+        buffer: walk it on the host.  d_bytes as frame_capnp_device wants it."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        dev = d_bytes.device
+        nbytes, K = d_bytes.numel(), d_seg_starts.numel() - 1
+        cap = cap_slots if cap_slots is not None else nbytes // 64 + K + 16
+        d_first = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
+        d_stop = torch.empty(max(K, 1), dtype=torch.uint8, device=dev)
+        while True:
+            d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            d_kind = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            n = C.c_uint64()
+            rc = L.lib().fg_frame_capnp_multi_device(self._ctx, d_bytes.data_ptr(), nbytes, d_seg_starts.data_ptr(), K, d_offsets.data_ptr(),
+                                                     d_kind.data_ptr(), cap, d_first.data_ptr(), d_cons.data_ptr(), d_stop.data_ptr(),
+                                                     C.byref(n), C.c_void_p(stream.cuda_stream))
+            if rc == L.FG_ERR_ENT_OVERFLOW and cap_slots is None:
+                cap = int(n.value) + 16
+                continue
+            L.check(rc, "fg_frame_capnp_multi_device")
+            k = int(n.value)
+            return d_offsets[:k + 1], d_kind[:k], k, d_first, d_cons[:K], d_stop[:K]
+
+    def frame_decode_capnp_multi(self, raw: Union[bytes, np.ndarray], seg_starts):
+        """fg_frame_decode_capnp_multi_batch: the Cap'n Proto chunks of K connections back to back in, tables out.  Returns (HostTables
+        or None, offsets uint64[n + 1], kind uint8[n], seg_first uint64[K + 1], seg_consumed uint64[K], seg_stop uint8[K]); the row of
+        a FG_SLOT_CARRY slot has status FG_ST_BAD_UTF8.  last_host_path() says whether the device framed the buffer or the host
+        walked it."""
+        buf = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, np.uint8)
+        starts = np.ascontiguousarray(seg_starts, np.uint64)
+        K = len(starts) - 1
+        st = L.fg_tables()
+        off, kind, first, cons, stop = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = C.c_uint64()
+        L.check(L.lib().fg_frame_decode_capnp_multi_batch(self._ctx, buf.ctypes.data if buf.size else None, buf.size, starts.ctypes.data, K,
+                                                          C.byref(st), C.byref(off), C.byref(kind), C.byref(first), C.byref(cons),
+                                                          C.byref(stop), C.byref(n)), "fg_frame_decode_capnp_multi_batch")
+        ns = int(n.value)
+        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+        offsets = np.ctypeslib.as_array(C.cast(off, u64p), (ns + 1,)).copy()
+        kinds = np.ctypeslib.as_array(C.cast(kind, u8p), (ns,)).copy() if ns else np.zeros(0, np.uint8)
+        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
+        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
+        seg_stop = np.ctypeslib.as_array(C.cast(stop, u8p), (K,)).copy() if K else np.zeros(0, np.uint8)
+        return (HostTables.from_struct(st) if ns else None), offsets, kinds, seg_first, seg_cons, seg_stop
+
     # -- the UDP input (input/udp_input.rs:100-143) -------------------------------------------------------
     def udp_decode_packed(self, data: np.ndarray, offsets: np.ndarray, max_inflated: Optional[int] = None):
         """Datagrams back to back in, tables out (fg_udp_decode_batch: upload, inflate / copy + UTF-8 on the GPU, decode).  Returns
@@ -894,6 +949,89 @@ class CapnpSplitter:
         blob, offs = tab.serialize(L.FG_CAPNP, data, offsets)
         raw = blob.tobytes()
         return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
+
+
+class MultiCapnpSplitter:
+    """MultiStreamSplitter for CAP'N PROTO connections (input.format = "capnp": flowgger instances relaying to a collector): parks the
+    chunks of many connections and hands them to the GPU together -- one fg_frame_decode_capnp_multi_batch call walks every
+    connection's bytes as its own stream and decodes the messages.  Per connection the output is what a CapnpSplitter of its own
+    returns for the bytes pushed so far: a Record (or the DecodeError the reference prints) per whole message; the bytes behind the
+    last whole message are carried over to the connection's next chunk.  A table that ends the connection (512 or more segments, more
+    than 8 Mi words) puts its CapnpStreamError last, behind the whole messages in front of it: later pushes raise ValueError.
+    close(conn) ends the connection: its whole messages come with the next flush, carried bytes are dropped and nothing more is
+    reported."""
+
+    def __init__(self, decoder: Optional[CapnpDecoder] = None, policy: Optional[FlushPolicy] = None):
+        self.decoder, self.policy = decoder or CapnpDecoder(), policy or FlushPolicy()
+        self._carry: dict = {}
+        self._pending: dict = {}
+        self._closed: set = set()   # close() seen, not flushed yet
+        self._over: set = set()     # the connection ended: closed, or a table read_message refuses
+        self._bytes = 0
+        self._first_at: Optional[float] = None
+
+    def push(self, conn_id, chunk: bytes) -> list:
+        """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
+        import time
+
+        if conn_id in self._closed or conn_id in self._over:
+            raise ValueError("push after the connection ended")
+        if chunk:
+            self._pending.setdefault(conn_id, []).append(bytes(chunk))
+            self._bytes += len(chunk)
+            if self._first_at is None:
+                self._first_at = time.monotonic()
+        due = self._bytes >= self.policy.max_bytes or (
+            self._first_at is not None and (time.monotonic() - self._first_at) * 1e3 >= self.policy.max_latency_ms)
+        return self.flush() if due else []
+
+    def close(self, conn_id) -> None:
+        """the connection ends: what it still holds is framed at the next flush, an incomplete message is dropped"""
+        if conn_id not in self._over:
+            self._closed.add(conn_id)
+            self._pending.setdefault(conn_id, [])
+
+    def pending_bytes(self) -> int:
+        return self._bytes
+
+    def flush(self) -> list:
+        """-> [(conn_id, [Record | DecodeError | CapnpStreamError, ...]), ...] for every connection that had chunks parked or was
+        closed, in arrival order"""
+        conns = list(self._pending)
+        whole = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
+        self._pending, self._bytes, self._first_at = {}, 0, None
+        if not conns:
+            return []
+        # a segment starts on a word of the buffer: the last len % 8 bytes can never complete a message and stay on the host
+        segs = [w[:len(w) & ~7] for w in whole]
+        raw = b"".join(segs)
+        starts = np.zeros(len(segs) + 1, np.uint64)
+        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
+        tab, offsets, kind, first, cons, stop = self.decoder.frame_decode_capnp_multi(raw, starts)
+        can, coffs = b"", None
+        if tab is not None:
+            blob, coffs = tab.serialize(L.FG_CAPNP, np.frombuffer(raw + b"\0" * 32, np.uint8), offsets)
+            can = blob.tobytes()
+        out = []
+        for k, c in enumerate(conns):
+            res: list = [parse_canonical(can[int(coffs[i]):int(coffs[i + 1])]) for i in range(int(first[k]), int(first[k + 1]))
+                         if kind[i] == L.FG_SLOT_FRAME]
+            tail = whole[k][int(cons[k]):]
+            over = c in self._closed
+            if stop[k] in (L.FG_CAPNP_TOO_MANY_SEGMENTS, L.FG_CAPNP_TOO_LARGE):
+                try:
+                    CapnpFramer.frame(tail)  # (the text of the error: the few words of the table at `consumed`)
+                    raise AssertionError("the framer stopped at a table the host walk accepts")
+                except CapnpStreamError as e:
+                    res.append(e)
+                over = True
+            self._closed.discard(c)
+            if over:
+                self._over.add(c)
+            elif tail:
+                self._carry[c] = tail
+            out.append((c, res))
+        return out
 
 
 class CapnpTranscodingSplitter:

@@ -347,7 +347,7 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
  *                  to 0, the last to nbytes): the results are then those of the clamped list, and memory safety never depends on it.
  *   d_seg_final    n_segs bytes (device) or NULL = all zero: nonzero = connection k ended with this chunk
  *   framing        FG_FRAME_LINE or FG_FRAME_NUL (FG_ERR_ARG otherwise: FG_FRAME_SYSLEN has fg_frame_syslen_multi_device, FG_FRAME_CAPNP
- *                  its single-stream entry point)
+ *                  fg_frame_capnp_multi_device)
  * Every segment is framed as if it were the whole stream.  The output is a list of SLOTS that tile the buffer, in buffer order:
  *   d_offsets      out, cap_slots + 1 entries: slot i = [offsets[i], offsets[i + 1]), terminator included.  A nonempty segment has
  *                  one slot per delimiter in it and one more when its last byte is no delimiter (its tail); an empty one has none
@@ -474,6 +474,36 @@ int fg_frame_syslen_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t n
 #define FG_CAPNP_FRAME_MAX_BYTES 0xFFFF0000ull
 int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, int final, uint64_t* d_offsets, uint64_t cap_frames,
                           uint64_t* n_frames, uint64_t* consumed, int* stop_reason, void* stream);
+/* GPU FRAMING OF THE CAP'N PROTO CHUNKS OF MANY CONNECTIONS IN ONE LAUNCH (additive under the same FG_ABI_VERSION).  The reference gives
+ * every connection a CapnpSplitter of its own (input/tcp/tcp_input.rs:39-47, splitter/capnp_splitter.rs:24-46); this call replaces the
+ * walk over the segment tables for K connections at once.  Every segment is walked as if it were the whole chunk: a table or a body
+ * that would cross its segment's end is a TAIL whatever bytes the buffer holds there, and a stop in one segment changes nothing in
+ * any other.
+ *   d_bytes         as fg_frame_capnp_device
+ *   d_seg_starts    n_segs + 1 entries (device), as fg_frame_multi_device, with ONE more rule: every start seg_starts[k], k < n_segs, is
+ *                   a multiple of 8 (the framer works on 8-byte words counted from the buffer's start).  nbytes need not be, so only
+ *                   the last segment may end off a word.  The rule loses nothing: a message is whole words, so the last len % 8 bytes
+ *                   of a connection's pending bytes never complete one -- keep them back.  The list is clamped on the device and each
+ *                   start rounded DOWN to a word: memory safety never depends on it.  Empty segments are allowed
+ *   d_offsets       out, cap_slots + 1 entries INTO d_bytes.  The slots TILE the buffer: slot i = [off[i], off[i + 1]), off[n_slots] = nbytes
+ *   d_kind          out, cap_slots bytes: FG_SLOT_FRAME -- a whole message with its segment table -- or FG_SLOT_CARRY -- the bytes of a
+ *                   segment behind seg_consumed: at most one per segment, none when the segment ended CLEAN, the tail of a TAIL,
+ *                   TOO_MANY_SEGMENTS or TOO_LARGE stop alike.  FG_SLOT_BAD_UTF8 never occurs: Text is the decoder's business.  With
+ *                   d_bytes and d_offsets it is exactly what fg_decode_frames_device(FG_CAPNP, FG_FRAME_NONE, ..., d_bad_utf8 = d_kind)
+ *                   takes: the CARRY rows are skipped (status FG_ST_BAD_UTF8)
+ *   d_seg_first     out, n_segs + 1 entries: the slots of segment k are [seg_first[k], seg_first[k + 1]); seg_first[n_segs] = *n_slots
+ *   d_seg_consumed  out, n_segs entries: the bytes of segment k that its messages cover
+ *   d_seg_stop      out, n_segs bytes: an fg_capnp_stop -- how the walk of segment k ended at seg_starts[k] + seg_consumed[k]; an empty
+ *                   segment is CLEAN with no slots
+ *   n_slots         out (host); the call synchronises the stream
+ * With n_segs == 1 the FRAME offsets, seg_consumed[0] and seg_stop[0] are those of fg_frame_capnp_device on the same bytes.
+ * Returns FG_ERR_ENT_OVERFLOW when cap_slots is too small (*n_slots holds the need; NOTHING is written to the slot outputs and the
+ * per-segment outputs; nbytes / 8 + n_segs always suffices), FG_ERR_UNSUPPORTED when the launch DECLINES (as fg_frame_capnp_device,
+ * with n_segs more nodes in the store: nothing is valid, walk the segments on the host), FG_ERR_ARG for more than
+ * FG_CAPNP_FRAME_MAX_BYTES bytes or more than 2^24 segments. */
+int fg_frame_capnp_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs,
+                                uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap_slots, uint64_t* d_seg_first, uint64_t* d_seg_consumed,
+                                uint8_t* d_seg_stop, uint64_t* n_slots, void* stream);
 int fg_frame_decode_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                            uint64_t* d_offsets, uint64_t cap_frames, const fg_tables* tables, uint64_t avg_line_hint,
                            uint64_t* d_result, void* stream);
@@ -596,6 +626,21 @@ int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t
                                        uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts, const uint64_t** out_seg_first,
                                        const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop, uint64_t* n_frames);
 
+/* HOST-BUFFER decode of the CAP'N PROTO chunks of many connections: one call uploads the buffer, frames every segment as its own stream
+ * (fg_frame_capnp_multi_device, whose contract this shares) and decodes the messages where they lie (FG_CAPNP, FG_FRAME_NONE, with
+ * the slot kinds as the skip array).  The list IS checked here: FG_ERR_ARG when seg_starts does not tile the buffer or a start
+ * seg_starts[k], k < n_segs, is not a multiple of 8.
+ *   out               tables in ctx-owned pinned host memory, *n_slots rows; a FG_SLOT_CARRY row has status FG_ST_BAD_UTF8 and no entries;
+ *                     spans are relative to each slot's start (*out_offsets)[i], the segment table included
+ *   out_offsets       *n_slots + 1 entries into `bytes`;  out_kind: *n_slots bytes
+ *   out_seg_first     n_segs + 1 entries;  out_seg_consumed: n_segs entries;  out_seg_stop: n_segs bytes (fg_capnp_stop)
+ * When the device framer declines, every segment is walked on the host: the same results.  fg_last_host_path says
+ * FG_PATH_FRAME_CAPNP_MULTI_DEVICE or FG_PATH_FRAME_CAPNP_MULTI_HOST.  Everything returned is ctx-owned and stays valid until the next
+ * call on this ctx.  Out of scope here: slicing over streams, fg_transcode_batch for segmented input. */
+int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
+                                      fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
+                                      const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop, uint64_t* n_slots);
+
 /* HOST-BUFFER UDP decode: upload the datagrams, fg_udp_unpack_device, decode -- the whole of handle_record_maybe_compressed for a
  * batch.  `bytes` / `offsets` pinned or pageable.  `out`: tables in ctx-owned pinned host memory, n rows; a dropped datagram has
  * status FG_ST_BAD_UTF8 and (*udp_status)[i] says why.  *out_lines / *out_line_offsets (n + 1 entries): the payloads as decoded, in
@@ -620,7 +665,9 @@ enum {
     FG_PATH_FRAME_CAPNP_HOST = 9,  /* ... the device framer declined the chunk: the segment tables were walked on the host */
     FG_PATH_FRAME_MULTI = 10,      /* fg_frame_decode_multi_batch: upload, segmented framing, decode */
     FG_PATH_FRAME_SYSLEN_MULTI_DEVICE = 11, /* fg_frame_decode_syslen_multi_batch: every segment framed + packed by the device */
-    FG_PATH_FRAME_SYSLEN_MULTI_HOST = 12    /* ... the device framer declined the buffer: the segments were hopped on the host */
+    FG_PATH_FRAME_SYSLEN_MULTI_HOST = 12,   /* ... the device framer declined the buffer: the segments were hopped on the host */
+    FG_PATH_FRAME_CAPNP_MULTI_DEVICE = 13,  /* fg_frame_decode_capnp_multi_batch: every segment framed by the device */
+    FG_PATH_FRAME_CAPNP_MULTI_HOST = 14     /* ... the device framer declined the buffer: the segments were walked on the host */
 };
 int fg_last_host_path(const fg_ctx* ctx);
 /* How the chain of segment tables of the last FG_FRAME_CAPNP call of fg_frame_decode_batch / fg_transcode_batch on this ctx ended (an

@@ -16,7 +16,11 @@ and around fg_frame_device (the same bytes as one stream), both HBM-resident, me
                between two events around ONE fg_frame_syslen_multi_device call against K fg_frame_syslen_device calls on the same bytes
                (every chunk 16-byte aligned in a buffer of its own; each call synchronises, as it must to return its counts), for
                --syslen-cells K:chunk,...; and one stream (--syslen-one bytes) with n_segs == 1 against the single-stream call -- what
-               the segment lookup costs when it finds nothing.  Median (min .. max) of 9 after 3 warm-up runs."""
+               the segment lookup costs when it finds nothing.  Median (min .. max) of 9 after 3 warm-up runs.
+    --capnp    Cap'n Proto chunks instead (single-segment messages of 6 .. 70 words whose bodies hold pointer-like words, zero words
+               and text; a connection's chunk ends inside a message, on a word), HBM-resident: ONE fg_frame_capnp_multi_device call
+               against K fg_frame_capnp_device calls on the same bytes, for --capnp-cells K:chunk,...; and one stream (--capnp-one bytes)
+               with n_segs == 1 against the single-stream call.  Timed as --syslen."""
 import argparse
 import ctypes as C
 import json
@@ -235,6 +239,77 @@ def syslen_mode(dec, lines, dev, cells, one_bytes):
     print(json.dumps({"probe": "multi_stream_syslen", "cells": rows, "one_stream": {"bytes": len(raw), "multi_us": multi, "single_us": single}}))
 
 
+def capnp_chunks(rng, K, chunk):
+    """K chunks of about `chunk` bytes: whole messages, then the first words of the next one"""
+    import struct
+
+    fills = [b"\0", struct.pack("<2I", 0, 3), struct.pack("<4I", 1, 2, 0, 0), b"some text, ", struct.pack("<2I", 12, 1)]
+    out = []
+    for _ in range(K):
+        buf = bytearray()
+        while True:
+            words = int(rng.integers(6, 71))
+            fill = fills[int(rng.integers(0, len(fills)))]
+            m = struct.pack("<2I", 0, words) + (fill * (8 * words // len(fill) + 1))[:8 * words]
+            if len(buf) + len(m) > chunk:
+                buf += m[:max(8, min(len(m) // 2, chunk - len(buf))) & ~7]
+                break
+            buf += m
+        out.append(bytes(buf))
+    return out
+
+
+def capnp_mode(dev, cells, one_bytes):
+    from flowgger_amd import CapnpDecoder
+
+    dec = CapnpDecoder()
+    rng = np.random.default_rng(1)
+
+    def to_dev(raw):
+        host = np.zeros(((len(raw) + 15) & ~15) + 16, np.uint8)
+        host[:len(raw)] = np.frombuffer(raw, np.uint8)
+        return torch.from_numpy(host).to(dev)[:len(raw)]
+
+    s = torch.cuda.current_stream(dev)
+
+    def timed(fn):
+        ts = []
+        for i in range(12):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize(dev)
+            if i >= 3:
+                ts.append(a.elapsed_time(b) * 1e3)
+        return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+    rows = []
+    for K, chunk in cells:
+        chunks = capnp_chunks(rng, K, chunk)
+        raw = b"".join(chunks)
+        starts = np.zeros(K + 1, np.int64)
+        starts[1:] = np.cumsum([len(c) for c in chunks])
+        d_bytes, d_starts, d_each = to_dev(raw), torch.from_numpy(starts).to(dev), [to_dev(c) for c in chunks]
+        cap = len(raw) // 32 + K + 1024
+        n_multi = dec.frame_capnp_multi_device(d_bytes, d_starts, cap_slots=cap)[2] - K  # (every chunk ends in a CARRY slot)
+        n_each = sum(dec.frame_capnp_device(d, False, len(c) // 32 + 64)[1] for d, c in zip(d_each, chunks))
+        assert n_multi == n_each, (n_multi, n_each)
+        multi = timed(lambda: dec.frame_capnp_multi_device(d_bytes, d_starts, cap_slots=cap))
+        each = timed(lambda: [dec.frame_capnp_device(d, False, len(c) // 32 + 64) for d, c in zip(d_each, chunks)])
+        rows.append({"K": K, "chunk": chunk, "bytes": len(raw), "messages": n_multi, "multi_us": multi, "k_calls_us": each})
+        print(f"capnp K={K:5d} chunk={chunk:8d} total={len(raw) / 2**20:7.2f} MiB messages={n_multi}  one launch {multi['median']:.0f} us "
+              f"({multi['min']:.0f}..{multi['max']:.0f})  K calls {each['median']:.0f} us ({each['min']:.0f}..{each['max']:.0f})", flush=True)
+    raw = capnp_chunks(rng, 1, one_bytes)[0]
+    d_bytes, d_starts = to_dev(raw), torch.tensor([0, len(raw)], dtype=torch.int64, device=dev)
+    cap = len(raw) // 32 + 1024
+    multi = timed(lambda: dec.frame_capnp_multi_device(d_bytes, d_starts, cap_slots=cap))
+    single = timed(lambda: dec.frame_capnp_device(d_bytes, False, cap))
+    print(f"capnp one stream {len(raw) / 2**20:.2f} MiB  n_segs == 1 {multi['median']:.0f} us ({multi['min']:.0f}..{multi['max']:.0f})  "
+          f"single-stream call {single['median']:.0f} us ({single['min']:.0f}..{single['max']:.0f})", flush=True)
+    print(json.dumps({"probe": "multi_stream_capnp", "cells": rows, "one_stream": {"bytes": len(raw), "multi_us": multi, "single_us": single}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.5)
@@ -244,8 +319,14 @@ def main():
     ap.add_argument("--syslen", action="store_true")
     ap.add_argument("--syslen-cells", default="64:131072,4096:2048")
     ap.add_argument("--syslen-one", type=int, default=8 << 20)
+    ap.add_argument("--capnp", action="store_true")
+    ap.add_argument("--capnp-cells", default="64:131072,4096:2048")
+    ap.add_argument("--capnp-one", type=int, default=8 << 20)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if args.capnp:
+        capnp_mode(dev, [tuple(int(x) for x in c.split(":")) for c in args.capnp_cells.split(",")], args.capnp_one)
+        return
     dec = RFC5424Decoder()
     lines = synth.rfc5424_lines(args.lines, cfg=2)
     if args.syslen:
