@@ -93,6 +93,7 @@ FG_LO_TAPER_1 = 4096
 FG_LO_TAPER_2 = 8192
 FG_LO_NO_FUSED_FRAMING = 16384
 FG_LO_RFC3164_REGROUP, FG_LO_RFC3164_NO_REGROUP = 32768, 65536
+FG_LO_NO_SPARSE, FG_LO_FORCE_SPARSE = 131072, 262144
 FG_PATH_DECODE_ZERO_COPY, FG_PATH_DECODE_SLICED, FG_PATH_FRAME_FUSED, FG_PATH_FRAME_SLICED, FG_PATH_FRAME_ONE_PIECE = 1, 2, 3, 4, 5
 FG_PATH_FRAME_SYSLEN_DEVICE, FG_PATH_FRAME_SYSLEN_HOST = 6, 7
 FG_PATH_FRAME_CAPNP_DEVICE, FG_PATH_FRAME_CAPNP_HOST = 8, 9

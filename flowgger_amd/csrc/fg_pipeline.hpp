@@ -15,6 +15,7 @@
 #pragma once
 #include "fg_device.hpp"
 #include "fg_plan_policy.hpp"
+#include "fg_sparse_need.hpp"
 #include "fg_wave.hpp"
 
 namespace fg {
@@ -165,6 +166,7 @@ struct RowOut {
     fg_span span[6];
     uint32_t first, count;
     bool skip = false;  // the format has written what it wants of this row itself (kernels that complete rows of an earlier kernel)
+    bool handed = false;  // (SPARSE window) the head of this line was not enough, or would not have been: read by the loop, never stored
 };
 __device__ __forceinline__ void store_row(const DevTables& t, uint64_t li, const RowOut& o) {
     if (o.skip) return;
@@ -337,11 +339,23 @@ struct head_cap { static constexpr uint32_t value = kHeadCap; };
 template <class F>
 struct head_cap<F, decltype((void)F::kHeadBytes)> { static constexpr uint32_t value = F::kHeadBytes; };
 
-template <int NB, bool PROF, class F, bool HEAD = false>
+// SPARSE = H > 0: SHORT lines whose decoder looks at the head and the last byte only (RFC5424 without structured data: two thirds of
+// what the whole-line window reads is message text).  The window and the tile stay exactly as they are -- NB coalesced loads, lines
+// at their natural tile offsets -- but a lane whose 16-byte chunk overlaps neither the first H bytes nor the last bytes of a line
+// of the group (fg_sparse_need.hpp) gets an offset beyond the descriptor's range: it fetches nothing and stages zeros.  HBM moves
+// 128-byte pieces, so what is saved are the pieces that lie wholly inside a message.  The decoder gets HEAD-style
+// context (tbase, tlen = min(len, H), the last byte) and hands back every line whose result could depend on a byte it did not see;
+// a wave whose group handed back more than kSparseHandful lines stages dense (all chunks, tlen = len) from the group after the
+// one already in flight on, until a dense group holds no line that would have been handed back.
+constexpr uint32_t kSparseHandful = 4;
+
+template <int NB, bool PROF, class F, bool HEAD = false, uint32_t SPARSE = 0>
 __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets,
                                                 uint64_t n, const DevTables& t, uint32_t tile_cap, uint32_t L, uint64_t chunk_lines,
                                                 unsigned long long* prof, uint64_t* stash_base, F& fmt, FrameArgs fr) {
     static_assert(!HEAD || F::kClasses <= 1, "HEAD staging classifies one stage-A byte class at most");
+    static_assert(SPARSE == 0 || (!HEAD && F::kClasses == 0), "the sparse window builds its need bitmap where a stage-A class bitmap would lie");
+    static_assert(SPARSE % 16u == 0 && SPARSE <= 112u, "a line's run of chunks (at most (H + 4 + 14) / 16 + 1) must fit two bitmap words at any shift");
     const uint64_t kChunkLines = chunk_lines;  // lines a wave takes at a time (LaunchPlan::chunk)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint16_t* bm16 = reinterpret_cast<uint16_t*>(smem + tile_cap + 64u);
@@ -418,6 +432,50 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
 #pragma unroll
         for (int k = 0; k < NB; ++k) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane * 16u + k * 1024u), 0, FG_STREAM_AUX);
     };
+    // ---- SPARSE mode ----
+    // The voffsets of the window's loads for a group (a0, span, nl lines, the lanes' lines [lo0, lo1)).  A bitmap with one bit per chunk
+    // of the window, SET = not fetched, lives in LDS -- in the bitmap block behind the tile, which stage B of the group BEFORE is done
+    // with and stage B of this one has not touched yet: all ones, then every lane clears the run of its line (at most eight chunks, two
+    // consecutive words: two ds_and) and the last line's lane the run of its end; a dense group clears the chunks of the span instead.
+    // Each lane reads its bit of every row back and puts it into bit 31 of the load's voffset -- lane * 16 alone otherwise: the row's
+    // KiB goes into the scalar offset, which the descriptor's range check does not see (every fetched chunk lies inside the span by
+    // construction).  No global access, no branch around a load: the NB loads stay unconditional, so stage A's progressive vmcnt(k)
+    // waits stay exact.  The wave runs at its instruction issue rate, so this is written to be few instructions: 32-bit tile offsets,
+    // two VALU instructions per row.
+    const uint32_t sparse_tail = fr.strip != FG_FRAME_NONE ? kSparseTailFramed : kSparseTailPlain;  // wave-uniform
+    auto sparse_offsets = [&](uint64_t a0_, uint32_t span_, uint32_t nl_, uint64_t lo0, uint64_t lo1, bool dense, uint32_t* vo) {
+        uint32_t* skip = reinterpret_cast<uint32_t*>(bm16);
+        const uint32_t nchunk_ = span_ >> 4;
+        const uint32_t nwin = nchunk_ < (uint32_t)NB * kWave ? nchunk_ : (uint32_t)NB * kWave;  // chunks the window can hold
+        const uint32_t nword = 2u * NB + 2u < tile_cap / 32u + 8u ? 2u * NB + 2u : tile_cap / 32u + 8u;  // (the block's words)
+        if (lane < nword) {
+            const uint32_t c = lane * 32u;  // the word's first chunk
+            skip[lane] = !dense || c >= nchunk_ ? ~0u : nchunk_ - c >= 32u ? 0u : ~0u << (nchunk_ - c);
+        }
+        __syncthreads();
+        if (!dense) {  // wave-uniform
+            auto mark = [&](const NeedRange& r, bool on) {
+                const bool go = on && r.n != 0u && r.c0 < nwin;  // (a run that starts in the window ends at most a word behind it)
+                const uint64_t m = go ? ((1ull << r.n) - 1ull) << (r.c0 & 31u) : 0ull;
+                const uint32_t w = go ? r.c0 >> 5 : 0u;
+                __hip_atomic_fetch_and(skip + w, ~(uint32_t)m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_and(skip + w + 1u, ~(uint32_t)(m >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            const uint32_t t0 = (uint32_t)lo0 - (uint32_t)a0_, t1 = (uint32_t)lo1 - (uint32_t)a0_;  // (tile offsets: the low words do)
+            mark(need_head(t0, t1 - t0, SPARSE, sparse_tail, lane == 0u), lane < nl_);
+            if (lane + 1u == nl_) mark(need_tail(t1, sparse_tail), true);
+            __syncthreads();
+        }
+        const uint32_t half = lane >> 5, bit = lane & 31u, off = lane * 16u;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) vo[k] = ((skip[2 * k + (int)half] >> bit) << 31) | off;
+    };
+    auto load_window_sparse = [&](uint64_t a0_, uint32_t span_, const uint32_t* vo, u32x4* v) {
+        __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(bytes + a0_), (short)0, (int)span_, 0x00020000);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)vo[k], k * 1024, FG_STREAM_AUX);
+    };
     // ---- HEAD mode ----
     // per lane: st = bytes of its line's row in the tile (alignment slack + head, a multiple of 16, <= kHeadCap), tb = the row's tile
     // offset (exclusive prefix sum); a group = the leading lines whose rows fit the tile
@@ -472,10 +530,17 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
         geometry_head(p, o0, o1, &nl, &span, &st, &tb);
         load_window_head(o0, st, v);
         last2 = load_last2(o0, o1);
+    } else if constexpr (SPARSE != 0) {
+        geometry(p, o0, o1, &nl, &a0, &span);
+        uint32_t vo[NB];
+        sparse_offsets(a0, span, nl, o0, o1, false, vo);
+        load_window_sparse(a0, span, vo, v);
     } else {
         geometry(p, o0, o1, &nl, &a0, &span);
         load_window(a0, span, v);
     }
+    // (SPARSE) dense = the group in hand was staged whole; dense_next = so is the one in flight; dense_then = so will be the one after
+    bool dense = false, dense_next = false, dense_then = false;  // wave-uniform
     // The table row of a group is normally stored one iteration LATE (after the next group's stage A,
     // before the prefetch after that is issued): vmcnt retires in order, so stores issued
     // behind the window loads would have to be waited for at the top of every iteration.
@@ -594,6 +659,10 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
                     }
                 }
             }
+            // (sparse kernel: rows of w[] that a scalar branch skipped stay "in flight" as far as the compiler can count, and the first
+            //  write to one of their registers on the hot path behind W1 became a full vmcnt wait -- for the whole next window.  Here the
+            //  window has landed: waiting for the tail's own loads costs nothing.)
+            if constexpr (SPARSE != 0) __builtin_amdgcn_s_waitcnt(0x0F70);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the old window dead before the new one is loaded
         FG_MARK(S);
@@ -612,6 +681,11 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
             if constexpr (HEAD) geometry_head(pn, no0, no1, &pnl, &pspan, &pst, &ptb);
             else geometry(pn, no0, no1, &pnl, &pa0, &pspan);
         }
+        uint32_t pvo[SPARSE != 0 ? NB : 1];
+        if constexpr (SPARSE != 0) {
+            dense_next = dense_then;
+            if (more) sparse_offsets(pa0, pspan, pnl, no0, no1, dense_next, pvo);
+        }
         FG_MARK(ST);
         if (pend_valid && !(ablate & 1u)) store_row(t, pend_li, pend);
         // ---- prefetch: the next group's bytes into the register window, back to back with the stores (stores first: stage A's
@@ -621,6 +695,8 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
             if constexpr (HEAD) {
                 load_window_head(no0, pst, v);
                 plast2 = load_last2(no0, no1);
+            } else if constexpr (SPARSE != 0) {
+                load_window_sparse(pa0, pspan, pvo, v);
             } else {
                 load_window(pa0, pspan, v);
             }
@@ -684,7 +760,24 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
                 c.tlen = st == 0u ? 0u : (st - al < len ? st - al : len);
                 c.last2 = l2;
             }
+            if constexpr (SPARSE != 0) {
+                // the line lies at its natural place in the tile, its first tlen bytes and its last ones staged; the last two bytes of the
+                // line AS DECODED (behind its terminator) are read there (the line longer than the tile: not looked at, see decode)
+                const uint32_t len = (uint32_t)(e1 - o0);
+                c.tbase = (uint32_t)(o0 - a0);
+                c.tlen = dense || len < SPARSE ? len : SPARSE;
+                c.last2 = 0u;
+                if (valid && e1 > o0 && (o1 - a0) <= (uint64_t)span) {
+                    const uint32_t q = (uint32_t)(e1 - a0);
+                    c.last2 = smem[q - 1u];
+                    if (len >= 2u) c.last2 |= (uint32_t)smem[q - 2u] << 8;
+                }
+            }
             pend = fmt.decode(c, t);
+            if constexpr (SPARSE != 0) {
+                const uint32_t nh = (uint32_t)__popcll(__ballot(valid && pend.handed));
+                dense_then = dense ? nh != 0u : nh > kSparseHandful;
+            }
             if (fr.line_bad && valid && fr.line_bad[li]) {  // "Invalid UTF-8 input": the frame never reaches decode()
                 pend.meta = FG_ST_BAD_UTF8 | (0xFFu << 8) | (0xFFu << 16);
                 pend.ts = 0.0;
@@ -718,6 +811,7 @@ __device__ __forceinline__ void persistent_loop(const uint8_t* __restrict__ byte
         o1 = no1;
         a0 = pa0;
         span = pspan;
+        if constexpr (SPARSE != 0) dense = dense_next;
         if constexpr (HEAD) {
             st = pst;
             tb = ptb;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/fg_hip.h"
+#include "fg_sparse_need.hpp"
 
 #if defined(__HIPCC__)
 #define FG_POLICY_HD __host__ __device__
@@ -171,6 +172,19 @@ struct Variant { bool head, pairs; };
 inline Variant pick_variant(uint64_t avg_len, uint32_t flags) {
     return Variant{(flags & FG_LO_FORCE_HEAD) || (avg_len >= kHeadFromLen && !(flags & FG_LO_NO_HEAD)),
                    (flags & FG_LO_SD_PAIRS) || (avg_len >= kPairsFromLen && !(flags & FG_LO_SD_WALK))};
+}
+// The sparse window (fg_pipeline.hpp, fg_sparse_need.hpp: the whole-line window without the chunks that lie inside the messages): only
+// the whole-line kernel without the pair-parallel walk has a sparse form, and it is taken from the average length on above which there
+// is anything to skip.  The default since round 9 (every alternated run above every run of the whole-line window, the
+// trace's mean below the other's minimum); -DFG_SPARSE_DEFAULT=0 builds the library that takes it only under FG_LO_FORCE_SPARSE (A/B,
+// FG_BUILD_VARIANT / FG_BUILD_DEFS of flowgger_amd/build.py).  pick_variant's results are what they were.
+#if !defined(FG_SPARSE_DEFAULT)
+#define FG_SPARSE_DEFAULT 1
+#endif
+constexpr bool kSparseDefault = FG_SPARSE_DEFAULT != 0;
+inline bool pick_sparse(uint64_t avg_len, uint32_t flags, const Variant& v) {
+    if (v.head || v.pairs) return false;
+    return (flags & FG_LO_FORCE_SPARSE) || (kSparseDefault && avg_len >= kSparseFromLen && !(flags & FG_LO_NO_SPARSE));
 }
 // GELF: the average group of eight lines (+6.25 % + 256 B) fits a tile of exactly the 3 KiB register window ...
 inline bool gelf_group_fits_3k(uint64_t avg_len) { return 8u * avg_len * 17u / 16u + 256u <= 3072u; }

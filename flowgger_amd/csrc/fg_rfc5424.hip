@@ -307,6 +307,7 @@ struct Fast {
     uint32_t d0;       // index of part 7
     uint32_t c7;       // its first byte
     uint32_t e, s;     // message end / start after the cheap trims
+    uint32_t start_ok; // the cheap test settled the trim behind the '-' (f.s is the message's start)
 };
 
 // RFC3339 from registers, branch-free: [t0, t0+L) is the timestamp part.  Returns 1 = converted,
@@ -341,8 +342,10 @@ __device__ __forceinline__ uint32_t take_space(uint64_t& lo, uint64_t& hi, uint3
 // stay converged; what it cannot decide is reported in Fast::route.
 // (last_byte: the line's last byte when the caller has it -- HEAD staging, where the end of a long line is not in the tile --
 //  else kNoLastByte: read from the tile)
+// (vis: the bytes of the line, from its first, that the tile holds -- len, or less under the sparse window, where what lies behind
+//  them is zeros or a neighbour's bytes: no space at or beyond vis is counted)
 constexpr uint32_t kNoLastByte = 0xFFFFFFFFu;
-__device__ __forceinline__ Fast parse_line_fast(const Tile& T, uint32_t base, uint32_t len, Row& r, uint32_t last_byte = kNoLastByte) {
+__device__ __forceinline__ Fast parse_line_fast(const Tile& T, uint32_t base, uint32_t len, Row& r, uint32_t last_byte, uint32_t vis) {
     Fast f;
     // ---- independent LDS reads: the line's first 132 bytes (line-aligned dwords) and its last byte.
     //      The space mask of the header is derived HERE, per line, from those registers: classifying
@@ -391,8 +394,8 @@ __device__ __forceinline__ Fast parse_line_fast(const Tile& T, uint32_t base, ui
         hi = (uint64_t)(m[4] | (m[5] << 16)) | ((uint64_t)(m[6] | (m[7] << 16)) << 32);
     }
     {
-        const uint64_t lo_keep = len < 64u ? (1ull << (len & 63u)) - 1ull : ~0ull;
-        const uint64_t hi_keep = len < 64u ? 0ull : len < 128u ? (1ull << ((len - 64u) & 63u)) - 1ull : ~0ull;
+        const uint64_t lo_keep = vis < 64u ? (1ull << (vis & 63u)) - 1ull : ~0ull;
+        const uint64_t hi_keep = vis < 64u ? 0ull : vis < 128u ? (1ull << ((vis - 64u) & 63u)) - 1ull : ~0ull;
         lo &= lo_keep & ~((2ull << sp0) - 1ull);  // no space can precede sp0 in "<ddd>1"; sp0 itself is known
         hi &= hi_keep;
     }
@@ -444,6 +447,7 @@ __device__ __forceinline__ Fast parse_line_fast(const Tile& T, uint32_t base, ui
     const bool one_sp = s + 1u < len && cA == ' ' && cB > 0x20u && cB < 0x80u;
     const bool no_sp = s < len && cA > 0x20u && cA < 0x80u;
     f.s = one_sp ? s + 1u : s;
+    f.start_ok = (one_sp || no_sp) ? 1u : 0u;
     f.route |= (live && c == '-' && !(end_plain && (one_sp || no_sp))) ? R_TRIM : 0u;
     return f;
 }
@@ -739,8 +743,15 @@ constexpr uint32_t kShortSdTail = 64;  // bytes after the header up to which a l
 // SDX = true: the instantiation for batches of lines long enough to carry structured data (the launcher: average >= 320 bytes): the LDS
 // behind the tile holds a second bitmap and the scratch of the pair-parallel walk (fg_sd2.hpp); structured data takes that walk, and
 // the (rare) lines it hands back are parsed from global memory.  SDX = false is byte for byte the kernel of round 3.
-template <bool HEAD, bool SDX = false, bool PROF = false>
+// HB > 0 (with HEAD): the head form for the SPARSE window (fg_pipeline.hpp) -- the line lies at its natural place in the tile, its first
+// c.tlen = min(len, HB) bytes and its last one staged.  A row is produced from those only when no other byte can change it: the
+// header and the three bytes the cheap trim test reads end inside the head, part 7 is a lone '-', both trims are settled by the cheap
+// tests.  Everything else is decoded again from the whole line (coop_redo below), and RowOut::handed says so to the loop.
+// NESTED: the whole-line decode inside coop_redo -- it carries no assembly mark of its own (tools/hot_waits.py wants each mark once).
+template <bool HEAD, bool SDX = false, bool PROF = false, uint32_t HB = 0, bool NESTED = false>
 struct Rfc5424FormatT {
+    static_assert(HB == 0 || (HEAD && !SDX), "the sparse head form is a head form without the pair-parallel walk");
+    static constexpr bool kSparse = HB != 0;
     // no stage-A bitmap: the fast path classifies the header bytes itself, the SD walker's
     // quote bitmap is built on demand (rebuild_bitmap) for groups that hold SD lines.  (Round 5 measured the pair-parallel kernel with
     // the quote / backslash masks computed in stage A, while the bytes sit in registers, so that the chunk pass no longer reads the tile
@@ -767,9 +778,12 @@ struct Rfc5424FormatT {
     }
     const uint32_t len = (uint32_t)(o1 - o0);
     // HEAD staging: the tile holds the line's first c.tlen bytes at c.tbase -- the whole line (in_tile) or its head only
-    const bool in_tile = HEAD ? c.tlen == len : (o1 - a0) <= (uint64_t)span;
-    const bool head_only = HEAD && !in_tile && c.tlen >= 512u;
+    // (sparse: a line longer than the tile is a group of its own and keeps the whole-line kernel's route, from global memory)
+    const bool in_window = !kSparse || (o1 - a0) <= (uint64_t)span;
+    const bool in_tile = HEAD ? c.tlen == len && in_window : (o1 - a0) <= (uint64_t)span;
+    const bool head_only = HEAD && !in_tile && (kSparse ? in_window : c.tlen >= 512u);
     const uint32_t walk_len = HEAD ? c.tlen : len;
+    const uint32_t sd_len = kSparse ? len : walk_len;  // bytes a structured-data walk sees (sparse: only whole lines are walked)
     const uint32_t base = HEAD ? c.tbase : (uint32_t)(o0 - a0);
     bool from_global = false;  // the line ended up parsed from global memory (its entries are written from there as well)
     uint32_t* tile_w = reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(smem));
@@ -791,8 +805,10 @@ struct Rfc5424FormatT {
     if (valid) {
         route = R_GENERIC;
         if (in_tile || head_only) {
-            f = parse_line_fast(T, base, len, r, HEAD ? (len ? (c.last2 & 0xFFu) : 0u) : kNoLastByte);
+            f = parse_line_fast(T, base, len, r, HEAD ? (len ? (c.last2 & 0xFFu) : 0u) : kNoLastByte, kSparse ? walk_len : len);
             route = f.route;
+            // (sparse) the header, or one of the three bytes behind it that the cheap trim test has read, lies beyond the head
+            if (kSparse && head_only && f.d0 + 3u > walk_len) route |= R_GENERIC;
             if (!(route & R_GENERIC)) {
                 if (route & R_TS_SLOW) {  // rare
                     LdsReader rd(T.w, base);
@@ -808,11 +824,11 @@ struct Rfc5424FormatT {
     //         quote/backslash bitmap, built by the whole wave -------------------------------------
     // (a group with only a few SHORT bracketed tails -- typically malformed lines of a corpus without structured
     //  data -- is not worth two barriers and a pass over the whole tile: those lanes take the byte-wise parse_tail)
-    const bool sd_any = valid && !(route & R_GENERIC) && (route & R_TAIL) && r.status == E_OK && f.c7 == '[';
+    const bool sd_any = valid && !(route & R_GENERIC) && (route & R_TAIL) && r.status == E_OK && f.c7 == '[' && !(kSparse && head_only);
     const uint64_t sd_ballot = __ballot(sd_any);
     const bool group_has_sd = __any(sd_any && len - f.d0 > kShortSdTail) || __popcll(sd_ballot) > 4;  // wave-uniform
     const bool sd_lane = sd_any && group_has_sd;
-    FG_MARK(F);  // the end of the straight-line fast path: up to here no line of a staged group waits for global memory
+    if constexpr (!NESTED) FG_MARK(F);  // the end of the straight-line fast path: up to here no line of a staged group waits for global memory
     tick(0);
     sd2::Lds SL{};
     sd2::LineIn sin{false, 0u, 0u, 0u, false};
@@ -838,6 +854,13 @@ struct Rfc5424FormatT {
         rebuild_bitmap<QuoteClass>(smem, bm16, span >> 4);
         __syncthreads();
     }
+    // (sparse) the line's end from its last two bytes: a plain ASCII byte, or ONE ASCII blank behind one (a third of the bench corpus'
+    // lines end in a blank); the message's start from the head: the cheap test, or the trim walked over the head's bytes when the byte
+    // it stops at and the two behind it lie inside the head (a sixth of the corpus' lines have two blanks behind the '-')
+    const uint32_t end_b1 = c.last2 & 0xFFu, end_b2 = (c.last2 >> 8) & 0xFFu;
+    const bool end_is_plain = end_b1 > 0x20u && end_b1 < 0x80u;
+    const bool end_settled = end_is_plain || (len >= 2u && ascii_ws(end_b1) && end_b2 > 0x20u && end_b2 < 0x80u);
+    bool trim_settled = false;  // (sparse) an R_TRIM line whose trims the head and the last two bytes settle
     // ---- 3. the rare / heavy routes ------------------------------------------------------------
     bool redo = false;  // (HEAD) the head of the line was not enough: the whole line again, from global memory
     bool coop = false;  // (HEAD) ... by the whole wave, once this group is done (the line fits the tile)
@@ -854,11 +877,11 @@ struct Rfc5424FormatT {
                             r.status = slo.status;
                         } else {
                             r.n_ent = slo.n_ent;
-                            redo = !finish_sd_tail(T, base, len, walk_len, c.last2, slo.msg_at, r, bytes, o0);
+                            redo = !finish_sd_tail(T, base, len, sd_len, c.last2, slo.msg_at, r, bytes, o0);
                         }
                     }
                 } else if (sd_lane) {
-                    redo = !parse_tail_sd_tile(T, base, f.d0, len, walk_len, c.last2, r, t, stash ? tile_w : nullptr, &rec_ok, bytes, o0);
+                    redo = !parse_tail_sd_tile(T, base, f.d0, len, sd_len, c.last2, r, t, stash ? tile_w : nullptr, &rec_ok, bytes, o0);
                 } else if (head_only && (route & R_TAIL)) {
                     redo = true;  // (a short bracketed tail or garbage in a long line)
                 } else if (route & R_TAIL) {  // garbage instead of '-' / '['
@@ -868,7 +891,12 @@ struct Rfc5424FormatT {
                     uint32_t e = f.e, s0 = f.s;
                     if (route & R_TRIM) {  // rare
                         LdsReader rd(T.w, base);
-                        if (head_only) {  // the message starts in the head; its end is looked at in global memory
+                        if (kSparse && head_only) {
+                            e = end_is_plain ? len : len - 1u;
+                            if (!f.start_ok) s0 = trim_start(rd, f.d0 + 1u, walk_len);
+                            trim_settled = end_settled && s0 + 3u <= walk_len;
+                            redo = !trim_settled;  // (else the whole line)
+                        } else if (head_only) {  // the message starts in the head; its end is looked at in global memory
                             s0 = trim_start(rd, f.d0 + 1u, walk_len - 8u);
                             GlobalReader grd(reinterpret_cast<const uint32_t*>(bytes), o0);
                             e = trim_end(grd, 0u, len);
@@ -876,6 +904,7 @@ struct Rfc5424FormatT {
                         } else {
                             e = trim_end(rd, 0u, len);
                             s0 = trim_start(rd, f.d0 + 1u, len);
+                            if (kSparse) trim_settled = end_settled && s0 + 3u <= HB;  // (a dense group: what the head form would have done)
                         }
                     }
                     r.data0 = f.d0;
@@ -977,7 +1006,7 @@ struct Rfc5424FormatT {
                 sd_walk<true>(rd, r.data0, len, &msg_at, &cnt, t, first);
                 FG_RARE_END();
             } else if (sd_lane) {  // (measurement build without records: the tile is intact)
-                sd_walk_tile<SD_EMIT>(T, base, r.data0, walk_len, &msg_at, &cnt, t, first);
+                sd_walk_tile<SD_EMIT>(T, base, r.data0, sd_len, &msg_at, &cnt, t, first);
             } else if (in_tile) {
                 LdsReader rd(T.w, base);
                 sd_walk<true>(rd, r.data0, len, &msg_at, &cnt, t, first);
@@ -1000,6 +1029,11 @@ struct Rfc5424FormatT {
     for (int k = 0; k < 6; ++k) o.span[k] = ok ? fg_span{r.off[k], r.len[k]} : fg_span{0, FG_NONE};
     o.first = first;
     o.count = r.n_ent;
+    if constexpr (kSparse) {
+        // handed back -- or, in a group staged dense (tlen == len), a line that the head form would have handed back
+        o.handed = valid && in_window && (coop ||
+                             (len > HB && ((route & (R_GENERIC | R_TAIL)) != 0u || ((route & R_TRIM) != 0u && !trim_settled) || f.d0 + 3u > HB)));
+    }
     if constexpr (HEAD) {
         // ---- lines whose head was not enough (structured data that runs past it, a bracketed tail behind it ...): one in five hundred
         // of the 64 B .. 8 KiB corpus.  Rounds 3-4 sent the lane through the byte-wise parser over global memory, a dword per trip:
@@ -1035,7 +1069,7 @@ struct Rfc5424FormatT {
             __syncthreads();
             GroupCtx c2{bytes, smem, bm16, ro0, ro1, ra0, rspan, lane == 0u, rli, c.stash, ablate, c.ent_state, nullptr};
             c2.tile_cap = c.tile_cap;
-            Rfc5424FormatT<false, SDX, false> whole;
+            Rfc5424FormatT<false, SDX, false, 0, true> whole;
             const RowOut w = whole.decode(c2, t);
             // lane 0's row -> the lane that owns the line
             auto b32 = [&](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
@@ -1096,6 +1130,26 @@ __global__ __launch_bounds__(kWave, 2) void k_rfc5424(const uint8_t* __restrict_
     }
 }
 
+// The whole-line window with the chunks inside the messages left out (persistent_loop<..., SPARSE = H>) and the head form of the decoder
+// for it: short lines without structured data (pick_sparse, fg_plan_policy.hpp).  Same arguments and launch shape as k_rfc5424.
+template <int NB, bool PROF, uint32_t H>
+__global__ __launch_bounds__(kWave, 2) void k_rfc5424_sparse(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, uint64_t n,
+                                                            DevTables t, uint32_t tile_cap, uint32_t L, uint64_t groups,
+                                                            unsigned long long* prof, uint64_t* stash_base, FrameArgs fr) {
+    Rfc5424FormatT<true, false, PROF, H> fmt;
+    if constexpr (PROF) {
+        __shared__ unsigned long long pacc[10];
+        if (threadIdx.x < 10) pacc[threadIdx.x] = 0ull;
+        fmt.pacc = pacc;
+        __syncthreads();
+        persistent_loop<NB, PROF, Rfc5424FormatT<true, false, PROF, H>, false, H>(bytes, offsets, n, t, tile_cap, L, groups, prof, stash_base, fmt, fr);
+        __syncthreads();
+        if (prof && threadIdx.x < 10) atomicAdd(&prof[6 + threadIdx.x], pacc[threadIdx.x]);
+    } else {
+        persistent_loop<NB, PROF, Rfc5424FormatT<true, false, PROF, H>, false, H>(bytes, offsets, n, t, tile_cap, L, groups, prof, stash_base, fmt, fr);
+    }
+}
+
 // The same decoder over a RAW stream: the kernel frames its tiles itself (fg_fused.hpp).  Whole lines only (a stream of long lines
 // -- head staging -- keeps the separate framing pass).
 template <int NB, bool SDX>
@@ -1134,7 +1188,10 @@ extern "C" int fg_launch_rfc5424(const uint8_t* d_bytes, const uint64_t* d_offse
                                  const uint8_t* line_bad, const fg_launch_opts* lo, fg::TicketSlot* tk) {
     if (n == 0) return 0;
     const fg::Variant v = fg::pick_variant(avg_len, lo->flags);
-    const auto ks = v.pairs ? (v.head ? rfc5424_kernels<true, true>("rfc5424 (head, pairs)") : rfc5424_kernels<false, true>("rfc5424 (pairs)"))
+    const bool sparse = fg::pick_sparse(avg_len, lo->flags, v);
+    const auto ks = sparse ? fg::kernels(fg::k_rfc5424_sparse<fg::kWindowKiB, false, fg::kSparseHead>,
+                                         FG_PROF_TWIN(fg::k_rfc5424_sparse<fg::kWindowKiB, true, fg::kSparseHead>), "rfc5424 (sparse)")
+                    : v.pairs ? (v.head ? rfc5424_kernels<true, true>("rfc5424 (head, pairs)") : rfc5424_kernels<false, true>("rfc5424 (pairs)"))
                             : (v.head ? rfc5424_kernels<true, false>("rfc5424 (head)") : rfc5424_kernels<false, false>("rfc5424"));
     // (default tile from the same-box sweeps, profiles/r04g_sweep_*: 12 KiB -- eight waves per CU -- for whole lines and for heads)
     // (THREE waves per SIMD -- the compiler fits the whole-line instantiation into 168 registers without a spill under

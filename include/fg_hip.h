@@ -287,6 +287,9 @@ enum {
     FG_LO_RFC3164_REGROUP = 32768, /* FG_RFC3164: hand the lines of the slow shapes (zone names, the custom form) to a second kernel, 64 of a kind to the workgroup,
                                       for batches of any size -- the library does so from 1 M lines on (tests) */
     FG_LO_RFC3164_NO_REGROUP = 65536, /* ... never: lines in arrival order, a wave runs the union of its lines' shapes (rounds 1-5; A/B) */
+    FG_LO_NO_SPARSE = 131072,      /* RFC5424: the whole-line window for short lines even where the library would leave the message bodies out of it */
+    FG_LO_FORCE_SPARSE = 262144,   /* RFC5424: the sparse window -- only the chunks that hold a line's head or its last bytes are fetched -- for every
+                                      batch that takes the whole-line kernel without the pair-parallel walk (parity sweeps, A/B) */
     FG_LO_RESERVED = 0x40000000    /* the library's own (fg_set_launch_opts clears it) */
 };
 
