@@ -6,6 +6,8 @@
 // (src/flowgger/mod.rs:413-422, src/flowgger/decoder/mod.rs:23-36): a ctx is built once from the
 // configuration and cloned per connection thread.
 #include "fg_ctx.hpp"
+#include "fg_syslen_parse.hpp"
+#include "fg_capnp_next.hpp"
 
 namespace {
 
@@ -425,6 +427,36 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     return FG_OK;
 }
 
+// An EMPTY buffer of n_segs connections: no slots, every segment starts at slot 0, consumed nothing and stopped `clean` (d_offsets,
+// d_seg_stop: null where the framing has none).
+static int clear_segments(fg_ctx* ctx, uint64_t n_segs, uint64_t* d_offsets, uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop,
+                          int clean, hipStream_t s) {
+    if (d_offsets) FG_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s));
+    if (n_segs) {
+        FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
+        FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
+        if (d_seg_stop) FG_HIP(ctx, hipMemsetAsync(d_seg_stop, clean, n_segs, s));
+    }
+    if (d_offsets || n_segs) FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+
+// The result words of a chained framer's launch (fg::syslen / fg::capnpf H_*; `done` = the framing's H_DONE) into hdr: a launch
+// that declined or did not finish -> FG_ERR_UNSUPPORTED; *n = its frames, more than cap -> FG_ERR_ENT_OVERFLOW.
+namespace sl = fg::syslen;
+namespace cp = fg::capnpf;
+static_assert((int)sl::H_DECLINE == (int)cp::H_DECLINE && (int)sl::H_NFRAMES == (int)cp::H_NFRAMES, "both framings keep these two words in one place");
+constexpr int kHdrWords = 8;  // the words the host reads: every H_* it asks for lies below
+static_assert(sl::H_DONE < kHdrWords && cp::H_DONE < kHdrWords && sl::H_TOTAL < kHdrWords, "a result word the host reads is not copied");
+static int read_frame_hdr(fg_ctx* ctx, const uint32_t* d_hdr, int done, uint64_t cap, uint64_t* n, uint32_t* hdr, hipStream_t s) {
+    memset(hdr, 0, kHdrWords * sizeof(uint32_t));
+    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, kHdrWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (hdr[sl::H_DECLINE] != 0 || hdr[done] != 1) return FG_ERR_UNSUPPORTED;
+    *n = hdr[sl::H_NFRAMES];
+    return *n > cap ? FG_ERR_ENT_OVERFLOW : FG_OK;
+}
+
 // replaces the per-connection `buf_reader.lines()` / `split(0)` + str::from_utf8 (tcp_input.rs:39-47, line_splitter.rs:17-25,
 // nul_splitter.rs:18-40) for the chunks of n_segs connections at once
 int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts,
@@ -438,14 +470,7 @@ int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_byte
     if (!fg_launch_frame_multi || !fg_frame_multi_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (nbytes == 0 || n_segs == 0) {  // no slots: every segment is empty
-        if (n_segs) {
-            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
-            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
-            FG_HIP(ctx, hipStreamSynchronize(s));
-        }
-        return FG_OK;
-    }
+    if (nbytes == 0 || n_segs == 0) return clear_segments(ctx, n_segs, nullptr, d_seg_first, d_seg_consumed, nullptr, 0, s);
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
     uint64_t res[2] = {0, 0};
@@ -480,15 +505,11 @@ int fg_frame_syslen_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_syslen_scratch_bytes(nbytes))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
     FG_LAUNCH(ctx, fg_launch_syslen(d_bytes, nbytes, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8, cap_frames, &d_hdr, s));
-    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (hdr[0] != 0 || hdr[5] != 1) return FG_ERR_UNSUPPORTED;  // declined: more speculative chains than the kernels track
-    *n_frames = hdr[2];
-    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
-    *consumed = hdr[3];
-    *stop_reason = (int)hdr[1];
-    ctx->last_syslen_payload = hdr[4];
+    uint32_t hdr[kHdrWords];  // (declined: more speculative chains than the kernels track)
+    if ((rc = read_frame_hdr(ctx, d_hdr, sl::H_DONE, cap_frames, n_frames, hdr, s)) != FG_OK) return rc;
+    *consumed = hdr[sl::H_CONSUMED];
+    *stop_reason = (int)hdr[sl::H_STOP];
+    ctx->last_syslen_payload = hdr[sl::H_TOTAL];
     return FG_OK;
 }
 
@@ -507,30 +528,16 @@ int fg_frame_syslen_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t n
     if (nbytes > fg_syslen_max_bytes()) return FG_ERR_UNSUPPORTED;  // (the scratch keeps positions as 32-bit words)
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (nbytes == 0) {  // no frames: every segment is empty and CLEAN
-        FG_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s));
-        if (n_segs) {
-            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
-            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
-            FG_HIP(ctx, hipMemsetAsync(d_seg_stop, FG_SYSLEN_CLEAN, n_segs, s));
-        }
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
+    if (nbytes == 0) return clear_segments(ctx, n_segs, d_offsets, d_seg_first, d_seg_consumed, d_seg_stop, FG_SYSLEN_CLEAN, s);
     if (n_segs > (1ull << 24)) return FG_ERR_UNSUPPORTED;  // (node numbers are 32-bit words)
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_syslen_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
     FG_LAUNCH(ctx, fg_launch_syslen_multi(d_bytes, nbytes, d_seg_starts, n_segs, ctx->d_frame, d_packed, d_offsets, d_frame_starts, d_bad_utf8,
                                            cap_frames, d_seg_first, d_seg_consumed, d_seg_stop, &d_hdr, s));
-    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (hdr[0] != 0 || hdr[5] != 1) return FG_ERR_UNSUPPORTED;  // declined: more speculative chains than the kernels track
-    *n_frames = hdr[2];
-    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
-    *payload_bytes = hdr[4];
-    ctx->last_syslen_payload = hdr[4];
+    uint32_t hdr[kHdrWords];  // (declined: more speculative chains than the kernels track)
+    if ((rc = read_frame_hdr(ctx, d_hdr, sl::H_DONE, cap_frames, n_frames, hdr, s)) != FG_OK) return rc;
+    *payload_bytes = ctx->last_syslen_payload = hdr[sl::H_TOTAL];
     return FG_OK;
 }
 
@@ -552,14 +559,10 @@ int fg_frame_capnp_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, 
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_capnp_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
     FG_LAUNCH(ctx, fg_launch_capnp_frame(d_bytes, nbytes, ctx->d_frame, d_offsets, cap_frames, &d_hdr, s));
-    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (hdr[0] != 0 || hdr[4] != 1) return FG_ERR_UNSUPPORTED;  // declined: more nodes than the store holds
-    *n_frames = hdr[2];
-    if (hdr[2] > cap_frames) return FG_ERR_ENT_OVERFLOW;
-    *consumed = (uint64_t)hdr[3] * 8u;
-    *stop_reason = (int)hdr[1];
+    uint32_t hdr[kHdrWords];  // (declined: more nodes than the store holds)
+    if ((rc = read_frame_hdr(ctx, d_hdr, cp::H_DONE, cap_frames, n_frames, hdr, s)) != FG_OK) return rc;
+    *consumed = (uint64_t)hdr[cp::H_CONSUMED] * 8u;
+    *stop_reason = (int)hdr[cp::H_STOP];
     return FG_OK;
 }
 
@@ -575,27 +578,14 @@ int fg_frame_capnp_multi_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nb
     if (!fg_launch_capnp_frame_multi || !fg_capnp_frame_multi_scratch_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (nbytes == 0) {  // no slots: every segment is empty and CLEAN
-        FG_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s));
-        if (n_segs) {
-            FG_HIP(ctx, hipMemsetAsync(d_seg_first, 0, (n_segs + 1) * 8, s));
-            FG_HIP(ctx, hipMemsetAsync(d_seg_consumed, 0, n_segs * 8, s));
-            FG_HIP(ctx, hipMemsetAsync(d_seg_stop, FG_CAPNP_CLEAN, n_segs, s));
-        }
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
+    if (nbytes == 0) return clear_segments(ctx, n_segs, d_offsets, d_seg_first, d_seg_consumed, d_seg_stop, FG_CAPNP_CLEAN, s);
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_capnp_frame_multi_scratch_bytes(nbytes, n_segs))) != FG_OK) return rc;
     uint32_t* d_hdr = nullptr;
     FG_LAUNCH(ctx, fg_launch_capnp_frame_multi(d_bytes, nbytes, d_seg_starts, n_segs, ctx->d_frame, d_offsets, d_kind, cap_slots, d_seg_first,
                                                 d_seg_consumed, d_seg_stop, &d_hdr, s));
-    uint32_t hdr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FG_HIP(ctx, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (hdr[0] != 0 || hdr[4] != 1) return FG_ERR_UNSUPPORTED;  // declined: more nodes than the store holds
-    *n_slots = hdr[2];
-    return hdr[2] > cap_slots ? FG_ERR_ENT_OVERFLOW : FG_OK;
+    uint32_t hdr[kHdrWords];  // (declined: more nodes than the store holds)
+    return read_frame_hdr(ctx, d_hdr, cp::H_DONE, cap_slots, n_slots, hdr, s);
 }
 
 const char* fg_udp_error_string(uint8_t st) {

@@ -40,8 +40,7 @@ constexpr uint64_t kMaxBytes = 0xFFFF0000ull;    // word indices and a 3-bit kin
 constexpr uint32_t kKindShift = 29, kPosMask = (1u << kKindShift) - 1u;
 enum { K_EXIT = 4, K_HOP = 5, K_END = 6 };       // kinds of a word beyond the four stop reasons: its message leaves / stays in the tile /
                                                  // ends exactly on its SEGMENT's end (fg_capnp_frame_multi.hpp only): counted, no exit, no hop
-// the result words of a launch
-enum { H_DECLINE = 0, H_STOP = 1, H_NFRAMES = 2, H_CONSUMED = 3 /* a word index */, H_DONE = 4, H_NODES = 5, H_WORDS = 16 };
+// (the result words of a launch, H_*: fg_capnp_next.hpp)
 
 // ---- device scratch: 32-bit words -------------------------------------------------------------------------------------------
 struct Scratch {

@@ -40,22 +40,7 @@ namespace capnpf {
 constexpr uint64_t kMaxSegs = 1ull << 24;  // (the node store and the per-segment words are 32-bit counts)
 
 // the rounded starts as the stages ask for them
-struct Segs {
-    static constexpr bool kSegmented = true;
-    const uint64_t* c;  // n_segs + 1, non-decreasing, c[0] = 0, c[k < n_segs] a multiple of 8, c[n_segs] = nbytes
-    uint64_t n_segs;
-    // the first index j with c[j] > p, n_segs when there is none: p < nbytes lies in segment j - 1, which ends at c[j]
-    FG_WV uint64_t behind(uint64_t p) const { return fmulti::upper_bound_u64(c, 0, n_segs, p); }
-    // ... for the positions of one tile: the boundaries inside it are c[j0 .. j1)
-    struct Tile {
-        const uint64_t* c;
-        uint64_t j0, j1;
-        FG_WV uint64_t limit(uint64_t p) const { return c[j0 == j1 ? j0 : fmulti::upper_bound_u64(c, j0, j1, p)]; }
-    };
-    FG_WV Tile tile(uint64_t base) const {
-        const uint64_t j0 = behind(base);
-        return Tile{c, j0, fmulti::upper_bound_u64(c, j0, n_segs, base + kTileBytes - 1u)};
-    }
+struct Segs : fmulti::Segs<kTileBytes> {  // (c[k < n_segs] a multiple of 8)
     // word w is the first word of a non-empty segment
     FG_WV bool root(uint32_t w) const {
         const uint64_t p = (uint64_t)w * 8ull;
@@ -71,7 +56,7 @@ struct MScratch : Scratch {
     uint32_t* sg_cons;  // [n_segs] bytes its messages cover
     uint32_t* sg_stop;  // [n_segs] ST_*, kNil until its chain's last node reports
     uint32_t n_segs;
-    FG_WV Segs segs() const { return Segs{c, n_segs}; }
+    FG_WV Segs segs() const { return Segs{{c, n_segs}}; }
 };
 FG_WVH uint32_t m_node_cap(uint64_t nbytes, uint64_t n_segs) { return node_cap_of(nbytes) + (uint32_t)n_segs; }
 // hdr, bitmap, mk_stamp are cleared; sg_stop is filled with kNil

@@ -20,6 +20,8 @@ constexpr uint64_t kMaxSegments = 512;    // "Too many segments" from this count
 constexpr uint64_t kMaxWords = 8ull << 20;  // "Message has N words, which is too large" beyond it
 // fg_capnp_stop + "a whole message starts here"
 enum { ST_CLEAN = 0, ST_TAIL = 1, ST_TOO_MANY_SEGMENTS = 2, ST_TOO_LARGE = 3, ST_VALID = 4 };
+// the result words of a launch of the device framer (fg_capnp_frame.hpp, fg_capnp_frame_multi.hpp), as the host reads them back (fg_capi.cpp)
+enum { H_DECLINE = 0, H_STOP = 1, H_NFRAMES = 2, H_CONSUMED = 3 /* a word index */, H_DONE = 4, H_NODES = 5, H_WORDS = 16 };
 
 struct Next {
     uint32_t st;

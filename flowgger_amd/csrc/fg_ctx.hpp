@@ -208,9 +208,9 @@ struct fg_ctx {
     uint64_t d_udp_st_cap = 0;
     uint8_t* h_udp = nullptr;        // ... pinned: inflated lines | their offsets | fg_udp_status
     uint64_t h_udp_cap = 0;
-    uint8_t* d_ms = nullptr;         // fg_frame_decode_multi_batch: seg_starts | seg_first | seg_consumed | seg_final
+    uint8_t* d_ms = nullptr;         // the multi-connection host entries: the per-segment device columns (SegBatch, fg_host_pipeline.cpp)
     uint64_t d_ms_cap = 0;
-    uint8_t* h_ms = nullptr;         // ... pinned: seg_first | seg_consumed | slot offsets | slot kinds
+    uint8_t* h_ms = nullptr;         // ... pinned: the mirror their out_* pointers name
     uint64_t h_ms_cap = 0;
     uint8_t* d_bad = nullptr;    // fg_frame_decode_batch: per-frame UTF-8 verdicts
     uint64_t d_bad_cap = 0;

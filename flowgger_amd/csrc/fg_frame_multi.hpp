@@ -63,6 +63,28 @@ FG_FM_FN uint64_t upper_bound_u64(const uint64_t* a, uint64_t lo, uint64_t hi, u
     return lo;
 }
 
+// The clamped starts as the tile stages of the chained framers ask for them (fg_syslen_multi.hpp, fg_capnp_frame_multi.hpp: a stage
+// works on tiles of kTileBytes and wants to know how far the frame that starts at a position may reach)
+template <uint32_t kTileBytes>
+struct Segs {
+    static constexpr bool kSegmented = true;
+    const uint64_t* c;  // n_segs + 1, non-decreasing, c[0] = 0, c[n_segs] = nbytes
+    uint64_t n_segs;
+    // the first index j with c[j] > p, n_segs when there is none: p < nbytes lies in segment j - 1, which ends at c[j]
+    FG_FM_FN uint64_t behind(uint64_t p) const { return upper_bound_u64(c, 0, n_segs, p); }
+    FG_FM_FN uint64_t limit(uint64_t p) const { return c[behind(p)]; }
+    // ... for the positions of one tile: the boundaries inside it are c[j0 .. j1)
+    struct Tile {
+        const uint64_t* c;
+        uint64_t j0, j1;
+        FG_FM_FN uint64_t limit(uint64_t p) const { return c[j0 == j1 ? j0 : upper_bound_u64(c, j0, j1, p)]; }
+    };
+    FG_FM_FN Tile tile(uint64_t base) const {
+        const uint64_t j0 = behind(base);
+        return Tile{c, j0, upper_bound_u64(c, j0, n_segs, base + kTileBytes - 1u)};
+    }
+};
+
 // The patches of the boundary at p (0 < p < nbytes).  prev: the nearest boundary before p (0 = none: the buffer's start); next: the
 // nearest boundary behind p (kNoBoundary = none; the buffer's end is no boundary).  byte(x): the buffer's byte, asked for x < nbytes
 // only.  sink: set_delim(x), put_err(x, v) (the bit's final value), or_err(x) -- x <= nbytes; a sink may ignore positions that are

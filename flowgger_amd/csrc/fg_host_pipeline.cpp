@@ -483,6 +483,50 @@ static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int fin
 static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, uint64_t nbytes, uint64_t n, const uint8_t* d_bad,
                                 const uint8_t* d_src, fg_tables* out);
 
+// A framer's capacity is an estimate: call(cap) grows what depends on it and calls the device entry, which answers FG_ERR_ENT_OVERFLOW
+// with the count it found in *n -- the whole framer then runs again, sized from that count.
+extern "C++" {  // (a template cannot stand in the extern "C" block around it)
+template <class Call>
+static int frame_with_retry(uint64_t cap, const uint64_t* n, Call&& call) {
+    for (;;) {
+        const int rc = call(cap);
+        if (rc != FG_ERR_ENT_OVERFLOW) return rc;
+        cap = *n + 16;
+    }
+}
+}
+
+// The host hop of the octet-counted framing (what fg::BatchingSplitter's Syslen branch does), prefixes of any length: walk() one chunk
+// after the other, then upload() the packed batch where the device framer would have left it (ctx->d_sl_packed, d_offsets, d_bad).
+struct SyslenHop {
+    std::vector<uint64_t> starts, offs{0};  // per frame: where its prefix starts in the buffer; its payload in `packed` (n + 1)
+    std::vector<uint8_t> packed, bad;
+    // the chunk bytes[at .. at + len): its frames are appended; -> its stop reason, *consumed = the bytes of the chunk they cover
+    int walk(const uint8_t* bytes, uint64_t at, uint64_t len, uint64_t* consumed) {
+        const uint8_t* const seg = bytes + at;
+        return (int)fg::syslen::host_walk(seg, len, ~0ull, consumed, [&](uint64_t pos, uint32_t plen, uint64_t flen) {
+            const uint8_t* b = seg + pos + plen;
+            starts.push_back(at + pos);
+            packed.insert(packed.end(), b, b + flen);
+            offs.push_back(packed.size());
+            bad.push_back(fg::utf8::payload_bad(b, flen) ? 1 : 0);
+        });
+    }
+    // queued on s, NOT waited for: the caller synchronises before this object goes out of scope
+    int upload(fg_ctx* ctx, hipStream_t s) const {
+        const uint64_t n = bad.size(), payload = packed.size();
+        if (payload) FG_HIP(ctx, hipMemcpyAsync(ctx->d_sl_packed, packed.data(), payload, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, bad.data(), n, hipMemcpyHostToDevice, s));
+        return FG_OK;
+    }
+};
+// ... and of the Cap'n Proto framing: the offsets of the whole messages of the chunk bytes[at .. at + len) are appended
+static int capnp_hop(const uint8_t* bytes, uint64_t at, uint64_t len, uint64_t* consumed, std::vector<uint64_t>& offs) {
+    return (int)fg::capnpf::host_walk(bytes + at, len, consumed, [&](uint64_t p) { offs.push_back(at + p); });
+}
+
 // FG_FRAME_SYSLEN stage shared by fg_frame_decode_batch and fg_transcode_batch (the read_msglen / read_exact loop of
 // SyslenSplitter::run, syslen_splitter.rs:42-57, for a chunk): the chunk goes up as it is (one copy; from a pinned
 // chunk the copy engine reads it in place at link speed and no payload byte is touched by the host's cores) and is framed + packed in HBM.  When the device
@@ -509,13 +553,11 @@ static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int 
     // (two deliberate simplifications: a cap_frames that turns out too small runs the whole framer again with the count it reported --
     //  the next chunk is sized from this one's frames per byte --, and a prefix beyond the device parser's bound sends the WHOLE chunk
     //  through the host hop below, not just that one frame: leading zeros by the dozen are legal and never seen)
-    for (;;) {
-        if ((rc = ensure(cap)) != FG_OK) return rc;
-        rc = fg_frame_syslen_device(ctx, d_src, nbytes, final, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts, ctx->d_bad, cap, &n, consumed, &stop,
-                                    FG_STREAM_OWN);
-        if (rc != FG_ERR_ENT_OVERFLOW) break;
-        cap = n + 16;
-    }
+    rc = frame_with_retry(cap, &n, [&](uint64_t c) {
+        const int r = ensure(c);
+        return r != FG_OK ? r : fg_frame_syslen_device(ctx, d_src, nbytes, final, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts, ctx->d_bad, c, &n,
+                                                       consumed, &stop, FG_STREAM_OWN);
+    });
     if (rc == FG_OK && stop != FG_SYSLEN_LONG_PREFIX) {
         ctx->last_host_path = FG_PATH_FRAME_SYSLEN_DEVICE;
         *payload = ctx->last_syslen_payload;
@@ -524,27 +566,15 @@ static int syslen_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int 
         FG_HIP(ctx, hipMemcpyAsync(ctx->h_off, ctx->d_sl_starts, (n + 1) * 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
     } else if (rc == FG_OK || rc == FG_ERR_UNSUPPORTED) {
-        // the host hop (what fg::BatchingSplitter's Syslen branch does, over a chunk): prefixes of any length
-        namespace sl = fg::syslen;
-        std::vector<uint64_t> starts, offs{0};
-        std::vector<uint8_t> packed, bad;
-        stop = (int)sl::host_walk(bytes, nbytes, ~0ull, consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
-            const uint8_t* b = bytes + pos + plen;
-            starts.push_back(pos);
-            packed.insert(packed.end(), b, b + len);
-            offs.push_back(packed.size());
-            bad.push_back(fg::utf8::payload_bad(b, len) ? 1 : 0);
-        });
-        starts.push_back(*consumed);
-        n = starts.size() - 1;
+        SyslenHop hop;
+        stop = hop.walk(bytes, 0, nbytes, consumed);
+        n = hop.starts.size();
+        hop.starts.push_back(*consumed);
         if ((rc = ensure(n)) != FG_OK) return rc;
-        memcpy(ctx->h_off, starts.data(), (n + 1) * 8);
-        if (!packed.empty()) FG_HIP(ctx, hipMemcpyAsync(ctx->d_sl_packed, packed.data(), packed.size(), hipMemcpyHostToDevice, s));
-        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + packed.size(), 0, up(packed.size(), 16) + 16 - packed.size(), s));
-        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, bad.data(), n, hipMemcpyHostToDevice, s));
+        memcpy(ctx->h_off, hop.starts.data(), (n + 1) * 8);
+        if ((rc = hop.upload(ctx, s)) != FG_OK) return rc;
         FG_HIP(ctx, hipStreamSynchronize(s));  // (the vectors go out of scope)
-        *payload = packed.size();
+        *payload = hop.packed.size();
         ctx->last_host_path = FG_PATH_FRAME_SYSLEN_HOST;
     } else {
         return rc;
@@ -564,18 +594,16 @@ static int capnp_stage(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int f
     int rc, stop = FG_CAPNP_CLEAN;
     // (a message of the record schema is a few hundred bytes; a cap_frames that turns out too small runs the framer again with the
     //  count it reported, like syslen_stage)
-    uint64_t cap = nbytes / 64 + 1024, n = 0;
-    for (;;) {
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
-        rc = fg_frame_capnp_device(ctx, ctx->d_bytes, nbytes, final, ctx->d_offsets, cap, &n, consumed, &stop, FG_STREAM_OWN);
-        if (rc != FG_ERR_ENT_OVERFLOW) break;
-        cap = n + 16;
-    }
+    uint64_t n = 0;
+    rc = frame_with_retry(nbytes / 64 + 1024, &n, [&](uint64_t cap) {
+        const int r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8);
+        return r != FG_OK ? r : fg_frame_capnp_device(ctx, ctx->d_bytes, nbytes, final, ctx->d_offsets, cap, &n, consumed, &stop, FG_STREAM_OWN);
+    });
     if (rc == FG_OK) {
         ctx->last_host_path = FG_PATH_FRAME_CAPNP_DEVICE;
     } else if (rc == FG_ERR_UNSUPPORTED) {
         std::vector<uint64_t> offs;
-        stop = (int)fg::capnpf::host_walk(bytes, nbytes, consumed, [&](uint64_t p) { offs.push_back(p); });
+        stop = capnp_hop(bytes, 0, nbytes, consumed, offs);
         offs.push_back(*consumed);
         n = offs.size() - 1;
         if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 2) * 8)) != FG_OK) return rc;
@@ -1076,312 +1104,239 @@ static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, 
     return FG_OK;
 }
 
-// The chunks of many connections in one buffer: upload, frame every segment as its own stream, decode every slot (CARRY and
-// BAD_UTF8 slots are skipped rows), tables and slot lists back.  One piece: a batch of connection chunks is far below the sizes
-// from which the sliced forms pay.
+// ---- The chunks of MANY connections in one buffer (fg_frame_decode_multi_batch and its syslen / capnp siblings): upload once, frame every
+// segment as its own stream, decode every slot, tables and per-segment / per-slot lists back.  One piece: a batch of connection chunks is
+// far below the sizes from which the sliced forms pay.  What the three entries share lives here; each keeps its format check, its
+// first capacity, its device call, its host hop and what its decode reads.
+//   ctx->d_ms: seg_starts | seg_first | seg_consumed | a byte per segment (seg_final going in, or seg_stop coming out)
+//   ctx->h_ms: seg_first | seg_consumed | seg_stop | a u64 per slot (n + 1) | a byte per slot (n)     <- what the out_* pointers name
+struct SegBatch {
+    fg_ctx* ctx;
+    uint64_t n_segs;
+    // the caller's outputs; o_stop / o_slot8 null: the entry has no such column, and the mirror then has none either
+    fg_tables* out;
+    uint64_t* n_out;
+    const uint64_t **o_first, **o_cons;
+    const uint8_t** o_stop;
+    const uint64_t** o_slot64;
+    const uint8_t** o_slot8;
+    hipStream_t s = nullptr;
+    uint64_t *d_starts = nullptr, *d_first = nullptr, *d_cons = nullptr;
+    uint8_t* d_seg8 = nullptr;
+    uint64_t *h_first = nullptr, *h_cons = nullptr, *h_slot64 = nullptr;
+    uint8_t *h_stop = nullptr, *h_slot8 = nullptr;
+
+    // seg_starts tiles [0, nbytes]: starts at 0, ends at nbytes, never steps back, every start but the last clear of `mask`
+    static bool list_ok(const uint64_t* seg_starts, uint64_t n_segs, uint64_t nbytes, uint64_t mask) {
+        if (n_segs && !seg_starts) return false;
+        if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return false;
+        for (uint64_t k = 0; k < n_segs; ++k)
+            if (seg_starts[k] > seg_starts[k + 1] || (seg_starts[k] & mask) != 0) return false;
+        return true;
+    }
+    void publish(uint64_t n) const {
+        *n_out = n;
+        *o_first = h_first;
+        *o_cons = h_cons;
+        *o_slot64 = h_slot64;
+        if (o_stop) *o_stop = h_stop;
+        if (o_slot8) *o_slot8 = h_slot8;
+    }
+    // clears the outputs; the bytes (zero padded), the starts and seg_final go up
+    int upload(const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, const uint8_t* seg_final) {
+        *out = fg_tables{};
+        publish(0);
+        ctx->last_host_path = 0;
+        s = ctx->stream;
+        int rc;
+        const uint64_t w = up((n_segs + 1) * 8, 256);
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, 3 * w + up(n_segs + 1, 256))) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+        d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
+        d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + w);
+        d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + 2 * w);
+        d_seg8 = ctx->d_ms + 3 * w;
+        if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+        FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+        if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n_segs && seg_final) FG_HIP(ctx, hipMemcpyAsync(d_seg8, seg_final, n_segs, hipMemcpyHostToDevice, s));
+        return FG_OK;
+    }
+    // Lays the mirror out for n slots and fills every column from its source: `device` -- device columns, copied on s and NOT waited
+    // for --, else host arrays.  n64: the entries of the u64-per-slot column the source holds (the column has room for n + 1).
+    int mirror(uint64_t n, uint64_t n64, const uint64_t* first, const uint64_t* cons, const uint8_t* stop, const uint64_t* slot64, const uint8_t* slot8,
+               bool device) {
+        const uint64_t w = up((n_segs + 1) * 8, 256), at64 = 2 * w + (o_stop ? up(n_segs + 1, 256) : 0), at8 = at64 + up((n + 1) * 8, 256);
+        int rc;
+        if ((rc = grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, at8 + (o_slot8 ? up(n + 1, 256) : 0))) != FG_OK) return rc;
+        uint8_t* const h = ctx->h_ms;
+        h_first = reinterpret_cast<uint64_t*>(h);
+        h_cons = reinterpret_cast<uint64_t*>(h + w);
+        h_stop = o_stop ? h + 2 * w : nullptr;
+        h_slot64 = reinterpret_cast<uint64_t*>(h + at64);
+        h_slot8 = o_slot8 ? h + at8 : nullptr;
+        auto put = [&](void* dst, const void* src, uint64_t bytes) -> int {
+            if (bytes && device) FG_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+            else if (bytes) memcpy(dst, src, bytes);
+            return FG_OK;
+        };
+        h_first[0] = h_slot64[0] = 0;  // (what a call without segments / a column nobody filled reads as)
+        if ((rc = put(h_first, first, n_segs ? (n_segs + 1) * 8 : 0)) != FG_OK || (rc = put(h_cons, cons, n_segs * 8)) != FG_OK) return rc;
+        if (o_stop && (rc = put(h_stop, stop, n_segs)) != FG_OK) return rc;
+        if ((rc = put(h_slot64, slot64, n64 * 8)) != FG_OK) return rc;
+        return o_slot8 ? put(h_slot8, slot8, n) : FG_OK;
+    }
+    // the mirror goes out, and the n slots are decoded from d_src (ctx->d_offsets; ctx->d_bad nonzero -> FG_ST_BAD_UTF8, not decoded)
+    int finish(uint64_t n, int path, fg_format fmt, fg_framing framing, uint64_t used_bytes, const uint8_t* d_src) {
+        publish(n);
+        ctx->last_host_path = path;
+        if (n == 0) {
+            FG_HIP(ctx, hipStreamSynchronize(s));  // (the mirror's copies)
+            return FG_OK;
+        }
+        const int rc = decode_stage_to_host(ctx, fmt, framing, used_bytes, n, ctx->d_bad, d_src, out);
+        if (rc != FG_OK) ctx->last_host_path = 0;
+        return rc;
+    }
+};
+static bool text_format(fg_format fmt) { return fmt == FG_RFC5424 || fmt == FG_LTSV || fmt == FG_GELF || fmt == FG_RFC3164; }
+
+// Lines / NUL: CARRY and BAD_UTF8 slots are skipped rows; the slots are decoded where they lie (terminators stripped in-kernel).
 extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
                                            const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs, fg_tables* out,
                                            const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
                                            const uint64_t** out_seg_consumed, uint64_t* n_slots) {
     if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !n_slots || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) return FG_ERR_ARG;
-    if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF && fmt != FG_RFC3164) return FG_ERR_ARG;
-    if (n_segs && !seg_starts) return FG_ERR_ARG;
-    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
-    for (uint64_t k = 0; k < n_segs; ++k)
-        if (seg_starts[k] > seg_starts[k + 1]) return FG_ERR_ARG;
-    *n_slots = 0;
-    *out = fg_tables{};
-    *out_offsets = nullptr;
-    *out_kind = nullptr;
-    *out_seg_first = nullptr;
-    *out_seg_consumed = nullptr;
-    ctx->last_host_path = 0;
+    if ((framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) || !text_format(fmt)) return FG_ERR_ARG;
+    if (!SegBatch::list_ok(seg_starts, n_segs, nbytes, 0)) return FG_ERR_ARG;
+    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, nullptr, out_offsets, out_kind};
     DeviceGuard g(ctx->device);
-    hipStream_t s = ctx->stream;
     int rc;
-    // seg_starts | seg_first | seg_consumed | seg_final on the device; seg_first | seg_consumed | offsets | kinds in the pinned mirror
-    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_final = o_cons + up(n_segs * 8 + 8, 256);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_final + up(n_segs + 1, 256))) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
-    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
-    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
-    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
-    uint8_t* const d_final = seg_final ? ctx->d_ms + o_final : nullptr;
-    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
-    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
-    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_segs && seg_final) FG_HIP(ctx, hipMemcpyAsync(d_final, seg_final, n_segs, hipMemcpyHostToDevice, s));
-    // 1. frame: capacity one slot per 32 bytes and one tail per segment to start with, exact on retry (as frame_stage)
-    uint64_t cap = nbytes / 32 + n_segs + 1024, n = 0;
-    for (;;) {
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return rc;
-        rc = fg_frame_multi_device(ctx, framing, ctx->d_bytes, nbytes, d_starts, d_final, n_segs, ctx->d_offsets, ctx->d_bad, cap, d_first, d_cons, &n,
-                                   FG_STREAM_OWN);
-        if (rc != FG_ERR_ENT_OVERFLOW) break;
-        cap = n + 16;
-    }
+    if ((rc = b.upload(bytes, nbytes, seg_starts, seg_final)) != FG_OK) return rc;
+    // capacity: one slot per 32 bytes and one tail per segment to start with (as frame_stage)
+    uint64_t n = 0;
+    rc = frame_with_retry(nbytes / 32 + n_segs + 1024, &n, [&](uint64_t cap) {
+        int r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return r;
+        return fg_frame_multi_device(ctx, framing, ctx->d_bytes, nbytes, b.d_starts, seg_final ? b.d_seg8 : nullptr, n_segs, ctx->d_offsets, ctx->d_bad, cap,
+                                     b.d_first, b.d_cons, &n, FG_STREAM_OWN);
+    });
     if (rc != FG_OK) return rc;
-    const uint64_t h_cons = o_first, h_off = h_cons + up(n_segs * 8 + 8, 256), h_kind = h_off + up((n + 1) * 8, 256);
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_kind + up(n + 1, 256))) != FG_OK) return rc;
-    uint8_t* const h = ctx->h_ms;
-    if (n_segs) {
-        FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
-    } else {
-        memset(h, 0, 8);
-    }
-    if (nbytes && n_segs) FG_HIP(ctx, hipMemcpyAsync(h + h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    else memset(h + h_off, 0, 8);
-    if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_kind, ctx->d_bad, n, hipMemcpyDeviceToHost, s));
-    *n_slots = n;
-    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
-    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
-    *out_offsets = reinterpret_cast<const uint64_t*>(h + h_off);
-    *out_kind = h + h_kind;
-    ctx->last_host_path = FG_PATH_FRAME_MULTI;
-    if (n == 0) {
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    // 2. decode the slots where they lie (terminators stripped in-kernel; a nonzero kind -> FG_ST_BAD_UTF8, not decoded)
-    rc = decode_stage_to_host(ctx, fmt, framing, nbytes, n, ctx->d_bad, ctx->d_bytes, out);
-    if (rc != FG_OK) ctx->last_host_path = 0;
-    return rc;
+    // (an empty buffer: the device entry leaves the offsets alone)
+    if ((rc = b.mirror(n, nbytes && n_segs ? n + 1 : 0, b.d_first, b.d_cons, nullptr, ctx->d_offsets, ctx->d_bad, true)) != FG_OK) return rc;
+    return b.finish(n, FG_PATH_FRAME_MULTI, fmt, framing, nbytes, ctx->d_bytes);
 }
 
-// The OCTET-COUNTED chunks of many connections in one buffer (a SyslenSplitter per connection, syslen_splitter.rs:42-57): upload once,
-// frame + pack every segment as its own stream on the device, decode the packed payloads (FG_FRAME_NONE, with the UTF-8 flags).  When the
-// device framer declines (fg_frame_syslen_multi_device: FG_ERR_UNSUPPORTED) or a segment meets a prefix beyond the device parser's
-// bound, the whole buffer is hopped on the host, segment by segment, and the packed batch is uploaded: the same results either way
-// (the two simplifications of syslen_stage hold here too).
+// OCTET-COUNTED chunks (a SyslenSplitter per connection, syslen_splitter.rs:42-57): framed AND packed on the device; what is decoded is the
+// packed batch (FG_FRAME_NONE, with the UTF-8 flags).  When the device framer declines (fg_frame_syslen_multi_device: FG_ERR_UNSUPPORTED)
+// or a segment meets a prefix beyond the device parser's bound, the whole buffer is hopped on the host, segment by segment, and the
+// packed batch is uploaded: the same results either way (the two simplifications of syslen_stage hold here too).
 extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
                                                   uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts,
                                                   const uint64_t** out_seg_first, const uint64_t** out_seg_consumed,
                                                   const uint8_t** out_seg_stop, uint64_t* n_frames) {
     if (!ctx || !out || !out_frame_starts || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_frames || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (fmt != FG_RFC5424 && fmt != FG_LTSV && fmt != FG_GELF && fmt != FG_RFC3164) return FG_ERR_ARG;
-    if (n_segs && !seg_starts) return FG_ERR_ARG;
-    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
-    for (uint64_t k = 0; k < n_segs; ++k)
-        if (seg_starts[k] > seg_starts[k + 1]) return FG_ERR_ARG;
-    *n_frames = 0;
-    *out = fg_tables{};
-    *out_frame_starts = nullptr;
-    *out_seg_first = nullptr;
-    *out_seg_consumed = nullptr;
-    *out_seg_stop = nullptr;
-    ctx->last_host_path = 0;
+    if (!text_format(fmt) || !SegBatch::list_ok(seg_starts, n_segs, nbytes, 0)) return FG_ERR_ARG;
+    SegBatch b{ctx, n_segs, out, n_frames, out_seg_first, out_seg_consumed, out_seg_stop, out_frame_starts, nullptr};
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
     int rc;
-    // seg_starts | seg_first | seg_consumed | seg_stop on the device; seg_first | seg_consumed | seg_stop | frame starts in the pinned mirror
-    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_stop = o_cons + up(n_segs * 8 + 8, 256);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_stop + up(n_segs + 1, 256))) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
-    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
-    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
-    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
-    uint8_t* const d_stop = ctx->d_ms + o_stop;
-    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
-    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
-    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = b.upload(bytes, nbytes, seg_starts, nullptr)) != FG_OK) return rc;
     auto ensure = [&](uint64_t cap) -> int {
         int r;
         if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
         if ((r = grow_dev(ctx, (void**)&ctx->d_sl_starts, &ctx->d_sl_starts_cap, (cap + 2) * 8)) != FG_OK) return r;
         return grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1);
     };
-    // 1. frame + pack: capacity from the frames per byte this ctx last saw, exact on retry (as syslen_stage)
-    uint64_t cap = (uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 1024, n = 0, payload = 0;
-    for (;;) {
-        if ((rc = ensure(cap)) != FG_OK) return rc;
-        rc = fg_frame_syslen_multi_device(ctx, ctx->d_bytes, nbytes, d_starts, n_segs, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts, ctx->d_bad, cap,
-                                          d_first, d_cons, d_stop, &n, &payload, FG_STREAM_OWN);
-        if (rc != FG_ERR_ENT_OVERFLOW) break;
-        cap = n + 16;
-    }
+    // capacity from the frames per byte this ctx last saw (as syslen_stage)
+    uint64_t n = 0, payload = 0;
+    rc = frame_with_retry((uint64_t)((double)nbytes * ctx->frames_per_byte * 1.25) + 1024, &n, [&](uint64_t cap) {
+        const int r = ensure(cap);
+        return r != FG_OK ? r : fg_frame_syslen_multi_device(ctx, ctx->d_bytes, nbytes, b.d_starts, n_segs, ctx->d_sl_packed, ctx->d_offsets, ctx->d_sl_starts,
+                                                             ctx->d_bad, cap, b.d_first, b.d_cons, b.d_seg8, &n, &payload, FG_STREAM_OWN);
+    });
     if (rc != FG_OK && rc != FG_ERR_UNSUPPORTED) return rc;
-    const uint64_t h_cons = o_first, h_stop = h_cons + up(n_segs * 8 + 8, 256), h_fs = h_stop + up(n_segs + 1, 256);
-    auto mirror = [&](uint64_t frames) -> int { return grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_fs + up((frames + 1) * 8, 256)); };
     bool device = rc == FG_OK;
     if (device) {
-        if ((rc = mirror(n)) != FG_OK) return rc;
-        uint8_t* const h = ctx->h_ms;
-        if (n_segs) {
-            FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipMemcpyAsync(h + h_stop, d_stop, n_segs, hipMemcpyDeviceToHost, s));
-        } else {
-            memset(h, 0, 8);
-        }
-        if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_fs, ctx->d_sl_starts, n * 8, hipMemcpyDeviceToHost, s));
+        if ((rc = b.mirror(n, n, b.d_first, b.d_cons, b.d_seg8, ctx->d_sl_starts, nullptr, true)) != FG_OK) return rc;
         // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
         FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
-        for (uint64_t k = 0; k < n_segs && device; ++k) device = h[h_stop + k] != FG_SYSLEN_LONG_PREFIX;
+        for (uint64_t k = 0; k < n_segs && device; ++k) device = b.h_stop[k] != FG_SYSLEN_LONG_PREFIX;
     }
     if (!device) {
-        // the host hop (what syslen_stage does for one chunk), segment by segment: prefixes of any length
-        namespace sl = fg::syslen;
-        std::vector<uint64_t> starts, offs{0}, first{0}, cons;
-        std::vector<uint8_t> packed, bad, stop;
+        SyslenHop hop;
+        std::vector<uint64_t> first{0}, cons(n_segs);
+        std::vector<uint8_t> stop;
         for (uint64_t k = 0; k < n_segs; ++k) {
-            const uint64_t at = seg_starts[k];
-            const uint8_t* const seg = bytes + at;
-            uint64_t consumed = 0;
-            stop.push_back((uint8_t)sl::host_walk(seg, seg_starts[k + 1] - at, ~0ull, &consumed, [&](uint64_t pos, uint32_t plen, uint64_t len) {
-                const uint8_t* b = seg + pos + plen;
-                starts.push_back(at + pos);
-                packed.insert(packed.end(), b, b + len);
-                offs.push_back(packed.size());
-                bad.push_back(fg::utf8::payload_bad(b, len) ? 1 : 0);
-            }));
-            cons.push_back(consumed);
-            first.push_back(starts.size());
+            stop.push_back((uint8_t)hop.walk(bytes, seg_starts[k], seg_starts[k + 1] - seg_starts[k], &cons[k]));
+            first.push_back(hop.starts.size());
         }
-        n = starts.size();
-        payload = packed.size();
-        if ((rc = ensure(n)) != FG_OK || (rc = mirror(n)) != FG_OK) return rc;
-        uint8_t* const h = ctx->h_ms;
-        memcpy(h, first.data(), (n_segs + 1) * 8);
-        if (n_segs) memcpy(h + h_cons, cons.data(), n_segs * 8);
-        if (n_segs) memcpy(h + h_stop, stop.data(), n_segs);
-        if (n) memcpy(h + h_fs, starts.data(), n * 8);
-        if (payload) FG_HIP(ctx, hipMemcpyAsync(ctx->d_sl_packed, packed.data(), payload, hipMemcpyHostToDevice, s));
-        FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
-        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, bad.data(), n, hipMemcpyHostToDevice, s));
+        n = hop.starts.size();
+        payload = hop.packed.size();
+        if ((rc = ensure(n)) != FG_OK) return rc;
+        if ((rc = b.mirror(n, n, first.data(), cons.data(), stop.data(), hop.starts.data(), nullptr, false)) != FG_OK) return rc;
+        if ((rc = hop.upload(ctx, s)) != FG_OK) return rc;
         FG_HIP(ctx, hipStreamSynchronize(s));  // (the vectors go out of scope)
     }
     if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
-    uint8_t* const h = ctx->h_ms;
-    *n_frames = n;
-    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
-    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
-    *out_seg_stop = h + h_stop;
-    *out_frame_starts = reinterpret_cast<const uint64_t*>(h + h_fs);
-    ctx->last_host_path = device ? FG_PATH_FRAME_SYSLEN_MULTI_DEVICE : FG_PATH_FRAME_SYSLEN_MULTI_HOST;
-    if (n == 0) return FG_OK;
-    // 2. decode the packed payloads (a flagged payload -> FG_ST_BAD_UTF8, not decoded)
-    rc = decode_stage_to_host(ctx, fmt, FG_FRAME_NONE, payload, n, ctx->d_bad, ctx->d_sl_packed, out);
-    if (rc != FG_OK) ctx->last_host_path = 0;
-    return rc;
+    return b.finish(n, device ? FG_PATH_FRAME_SYSLEN_MULTI_DEVICE : FG_PATH_FRAME_SYSLEN_MULTI_HOST, fmt, FG_FRAME_NONE, payload, ctx->d_sl_packed);
 }
 
-// The CAP'N PROTO chunks of many connections in one buffer (a CapnpSplitter per connection, capnp_splitter.rs:24-46): upload once, frame
-// every segment as its own stream on the device, decode the messages where they lie with the slot kinds as the skip array (a CARRY slot
-// is a skipped row).  When the device framer declines (fg_frame_capnp_multi_device: FG_ERR_UNSUPPORTED) the segments are walked on the
-// host over the caller's bytes and the slots are uploaded: the same results either way.
+// CAP'N PROTO chunks (a CapnpSplitter per connection, capnp_splitter.rs:24-46): the messages are decoded where they lie, with the slot
+// kinds as the skip array (a CARRY slot is a skipped row).  When the device framer declines (fg_frame_capnp_multi_device:
+// FG_ERR_UNSUPPORTED) the segments are walked on the host over the caller's bytes and the slots are uploaded: the same results either way.
 extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
                                                  fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
                                                  const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop,
                                                  uint64_t* n_slots) {
     if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_slots || (nbytes && !bytes))
         return FG_ERR_ARG;
-    if (n_segs && !seg_starts) return FG_ERR_ARG;
-    if (n_segs ? (seg_starts[0] != 0 || seg_starts[n_segs] != nbytes) : nbytes != 0) return FG_ERR_ARG;
-    for (uint64_t k = 0; k < n_segs; ++k)
-        if (seg_starts[k] > seg_starts[k + 1] || (seg_starts[k] & 7u) != 0) return FG_ERR_ARG;  // (the framer works on words of the buffer)
+    if (!SegBatch::list_ok(seg_starts, n_segs, nbytes, 7)) return FG_ERR_ARG;  // (the framer works on words of the buffer)
     if (nbytes > FG_CAPNP_FRAME_MAX_BYTES || n_segs > (1ull << 24)) return FG_ERR_ARG;
-    *n_slots = 0;
-    *out = fg_tables{};
-    *out_offsets = nullptr;
-    *out_kind = nullptr;
-    *out_seg_first = nullptr;
-    *out_seg_consumed = nullptr;
-    *out_seg_stop = nullptr;
-    ctx->last_host_path = 0;
+    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, out_seg_stop, out_offsets, out_kind};
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
     int rc;
-    // seg_starts | seg_first | seg_consumed | seg_stop on the device; seg_first | seg_consumed | seg_stop | offsets | kinds in the pinned mirror
-    const uint64_t o_first = up((n_segs + 1) * 8, 256), o_cons = 2 * o_first, o_stop = o_cons + up(n_segs * 8 + 8, 256);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, o_stop + up(n_segs + 1, 256))) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
-    uint64_t* const d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
-    uint64_t* const d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + o_first);
-    uint64_t* const d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + o_cons);
-    uint8_t* const d_stop = ctx->d_ms + o_stop;
-    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
-    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
-    if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = b.upload(bytes, nbytes, seg_starts, nullptr)) != FG_OK) return rc;
     auto ensure = [&](uint64_t cap) -> int {
-        int r;
-        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
-        return grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1);
+        const int r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8);
+        return r != FG_OK ? r : grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1);
     };
-    // 1. frame: a message of the record schema is a few hundred bytes (as capnp_stage), one tail per segment; exact on retry
-    uint64_t cap = nbytes / 64 + n_segs + 1024, n = 0;
-    for (;;) {
-        if ((rc = ensure(cap)) != FG_OK) return rc;
-        rc = fg_frame_capnp_multi_device(ctx, ctx->d_bytes, nbytes, d_starts, n_segs, ctx->d_offsets, ctx->d_bad, cap, d_first, d_cons, d_stop, &n,
-                                         FG_STREAM_OWN);
-        if (rc != FG_ERR_ENT_OVERFLOW) break;
-        cap = n + 16;
+    // capacity: a message of the record schema is a few hundred bytes (as capnp_stage), one tail per segment
+    uint64_t n = 0;
+    rc = frame_with_retry(nbytes / 64 + n_segs + 1024, &n, [&](uint64_t cap) {
+        const int r = ensure(cap);
+        return r != FG_OK ? r : fg_frame_capnp_multi_device(ctx, ctx->d_bytes, nbytes, b.d_starts, n_segs, ctx->d_offsets, ctx->d_bad, cap, b.d_first, b.d_cons,
+                                                            b.d_seg8, &n, FG_STREAM_OWN);
+    });
+    if (rc == FG_OK) {
+        if ((rc = b.mirror(n, n + 1, b.d_first, b.d_cons, b.d_seg8, ctx->d_offsets, ctx->d_bad, true)) != FG_OK) return rc;
+        return b.finish(n, FG_PATH_FRAME_CAPNP_MULTI_DEVICE, FG_CAPNP, FG_FRAME_NONE, nbytes, ctx->d_bytes);
     }
-    if (rc != FG_OK && rc != FG_ERR_UNSUPPORTED) return rc;
-    const bool device = rc == FG_OK;
-    std::vector<uint64_t> offs, first{0}, cons;
+    if (rc != FG_ERR_UNSUPPORTED) return rc;
+    std::vector<uint64_t> offs, first{0}, cons(n_segs);
     std::vector<uint8_t> kind, stop;
-    if (!device) {  // the host walk (what capnp_stage does for one chunk), segment by segment
-        for (uint64_t k = 0; k < n_segs; ++k) {
-            const uint64_t at = seg_starts[k], len = seg_starts[k + 1] - at;
-            uint64_t consumed = 0;
-            stop.push_back((uint8_t)fg::capnpf::host_walk(bytes + at, len, &consumed, [&](uint64_t p) {
-                offs.push_back(at + p);
-                kind.push_back(FG_SLOT_FRAME);
-            }));
-            if (consumed < len) {
-                offs.push_back(at + consumed);
-                kind.push_back(FG_SLOT_CARRY);
-            }
-            cons.push_back(consumed);
-            first.push_back(kind.size());
+    for (uint64_t k = 0; k < n_segs; ++k) {
+        const uint64_t at = seg_starts[k], len = seg_starts[k + 1] - at;
+        stop.push_back((uint8_t)capnp_hop(bytes, at, len, &cons[k], offs));
+        kind.resize(offs.size(), FG_SLOT_FRAME);
+        if (cons[k] < len) {
+            offs.push_back(at + cons[k]);
+            kind.push_back(FG_SLOT_CARRY);
         }
-        offs.push_back(nbytes);
-        n = kind.size();
-        if ((rc = ensure(n)) != FG_OK) return rc;
+        first.push_back(kind.size());
     }
-    const uint64_t h_cons = o_first, h_stop = h_cons + up(n_segs * 8 + 8, 256), h_off = h_stop + up(n_segs + 1, 256), h_kind = h_off + up((n + 1) * 8, 256);
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_ms, &ctx->h_ms_cap, h_kind + up(n + 1, 256))) != FG_OK) return rc;
-    uint8_t* const h = ctx->h_ms;
-    if (device) {
-        if (n_segs) {
-            FG_HIP(ctx, hipMemcpyAsync(h, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipMemcpyAsync(h + h_cons, d_cons, n_segs * 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipMemcpyAsync(h + h_stop, d_stop, n_segs, hipMemcpyDeviceToHost, s));
-        } else {
-            memset(h, 0, 8);
-        }
-        FG_HIP(ctx, hipMemcpyAsync(h + h_off, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (n) FG_HIP(ctx, hipMemcpyAsync(h + h_kind, ctx->d_bad, n, hipMemcpyDeviceToHost, s));
-    } else {
-        memcpy(h, first.data(), (n_segs + 1) * 8);
-        if (n_segs) memcpy(h + h_cons, cons.data(), n_segs * 8);
-        if (n_segs) memcpy(h + h_stop, stop.data(), n_segs);
-        memcpy(h + h_off, offs.data(), (n + 1) * 8);
-        if (n) memcpy(h + h_kind, kind.data(), n);
-        FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, h + h_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
-        if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, h + h_kind, n, hipMemcpyHostToDevice, s));
-    }
-    *n_slots = n;
-    *out_seg_first = reinterpret_cast<const uint64_t*>(h);
-    *out_seg_consumed = reinterpret_cast<const uint64_t*>(h + h_cons);
-    *out_seg_stop = h + h_stop;
-    *out_offsets = reinterpret_cast<const uint64_t*>(h + h_off);
-    *out_kind = h + h_kind;
-    ctx->last_host_path = device ? FG_PATH_FRAME_CAPNP_MULTI_DEVICE : FG_PATH_FRAME_CAPNP_MULTI_HOST;
-    if (n == 0) {
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    // 2. decode the slots where they lie (a nonzero kind -> FG_ST_BAD_UTF8, not decoded)
-    rc = decode_stage_to_host(ctx, FG_CAPNP, FG_FRAME_NONE, nbytes, n, ctx->d_bad, ctx->d_bytes, out);
-    if (rc != FG_OK) ctx->last_host_path = 0;
-    return rc;
+    offs.push_back(nbytes);
+    n = kind.size();
+    if ((rc = ensure(n)) != FG_OK) return rc;
+    if ((rc = b.mirror(n, n + 1, first.data(), cons.data(), stop.data(), offs.data(), kind.data(), false)) != FG_OK) return rc;
+    // (from the pinned mirror: the vectors may go out of scope while these are in flight)
+    FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, b.h_slot64, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, b.h_slot8, n, hipMemcpyHostToDevice, s));
+    return b.finish(n, FG_PATH_FRAME_CAPNP_MULTI_HOST, FG_CAPNP, FG_FRAME_NONE, nbytes, ctx->d_bytes);
 }
 
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB

@@ -34,8 +34,7 @@ constexpr uint32_t kExits = 64;       // distinct exits of a tile
 constexpr uint32_t kInbox = 16;       // entries of a tile anyone can reach
 constexpr uint32_t kNil = 0xFFFFFFFFu;
 constexpr uint64_t kMaxBytes = 0xFFFF0000ull;  // positions and sums are 32-bit words in the scratch
-// the result words of a launch
-enum { H_DECLINE = 0, H_STOP = 1, H_NFRAMES = 2, H_CONSUMED = 3, H_TOTAL = 4, H_DONE = 5, H_WORDS = 16 };
+// (the result words of a launch, H_*: fg_syslen_parse.hpp)
 
 // ---- device scratch: 32-bit words -------------------------------------------------------------------------------------------
 struct Scratch {

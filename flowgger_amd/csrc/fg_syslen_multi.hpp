@@ -32,25 +32,7 @@ namespace syslen {
 
 constexpr uint64_t kMaxSegs = 1ull << 24;  // node numbers are 32-bit words
 
-// the clamped starts as the stages ask for them
-struct Segs {
-    static constexpr bool kSegmented = true;
-    const uint64_t* c;  // n_segs + 1, non-decreasing, c[0] = 0, c[n_segs] = nbytes
-    uint64_t n_segs;
-    // the first index j with c[j] > p, n_segs when there is none: p < nbytes lies in segment j - 1, which ends at c[j]
-    FG_WV uint64_t behind(uint64_t p) const { return fmulti::upper_bound_u64(c, 0, n_segs, p); }
-    FG_WV uint64_t limit(uint64_t p) const { return c[behind(p)]; }
-    // ... for the positions of one tile: the boundaries inside it are c[j0 .. j1)
-    struct Tile {
-        const uint64_t* c;
-        uint64_t j0, j1;
-        FG_WV uint64_t limit(uint64_t p) const { return c[j0 == j1 ? j0 : fmulti::upper_bound_u64(c, j0, j1, p)]; }
-    };
-    FG_WV Tile tile(uint64_t base) const {
-        const uint64_t j0 = behind(base);
-        return Tile{c, j0, fmulti::upper_bound_u64(c, j0, n_segs, base + kTile - 1u)};
-    }
-};
+using Segs = fmulti::Segs<kTile>;  // the clamped starts as the stages ask for them
 
 // ---- device scratch: fg_syslen.hpp's, with n_segs root nodes behind the inbox nodes, and four words per segment ---------------------
 struct MScratch : Scratch {

@@ -22,6 +22,8 @@ namespace syslen {
 constexpr uint32_t kMaxPrefix = 24;  // FG_SYSLEN_MAX_PREFIX: bytes of "<len> " the device parser reads, the ' ' included
 // fg_syslen_stop + "a well-formed prefix whose payload fits"
 enum { ST_CLEAN = 0, ST_TAIL = 1, ST_BAD_LEN = 2, ST_LONG_PREFIX = 3, ST_VALID = 4 };
+// the result words of a launch of the device framer (fg_syslen.hpp, fg_syslen_multi.hpp), as the host reads them back (fg_capi.cpp)
+enum { H_DECLINE = 0, H_STOP = 1, H_NFRAMES = 2, H_CONSUMED = 3, H_TOTAL = 4, H_DONE = 5, H_WORDS = 16 };
 
 struct Prefix {
     uint32_t st, plen;

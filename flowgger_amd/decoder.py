@@ -38,6 +38,24 @@ def pack_lines(lines: Iterable[Union[str, bytes]]) -> Tuple[np.ndarray, np.ndarr
     return data, offsets
 
 
+def _copied(ptr, ctype, count: int) -> np.ndarray:
+    """`count` elements of a ctx-owned C array as a numpy array of its own; empty for a zero count (the pointer may be NULL then)"""
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (count,)).copy() if count else np.zeros(0, ctype)
+
+
+def _framed_within(what: str, cap: int, fixed: bool, slack: int, attempt):
+    """The capacity of a multi-connection device framer is an estimate: attempt(cap) allocates the tensors sized by it, calls the
+    entry and returns (rc, count, tensors).  FG_ERR_ENT_OVERFLOW comes with the count the buffer needs: unless the caller fixed the
+    capacity, once more with count + slack.  -> (count, tensors)"""
+    while True:
+        rc, n, tensors = attempt(cap)
+        if rc == L.FG_ERR_ENT_OVERFLOW and not fixed:
+            cap = n + slack
+            continue
+        L.check(rc, what)
+        return n, tensors
+
+
 class Decoder:
     """Base: owns an fg_ctx (the analogue of Box<dyn Decoder + Send>)."""
 
@@ -106,21 +124,23 @@ class Decoder:
 
     def decode_batch(self, lines: Sequence[Union[str, bytes]]) -> List[Union[Record, DecodeError]]:
         data, offsets = pack_lines(lines)
-        tab = self.decode_packed(data, offsets)
-        n_rows = len(offsets) - 1
-        if self.fmt == L.FG_LTSV:  # the decoder's stdout side effect (ltsv_decoder.rs:99), reproduced from the rows' flags
+        raw, offs = self._canonical(self.decode_packed(data, offsets), data, offsets)
+        return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(len(lines))]
+
+    def _canonical(self, tab: HostTables, data: np.ndarray, offsets: np.ndarray, framing: int = L.FG_FRAME_NONE):
+        """the rows of `tab` as canonical Record bytes -> (blob bytes, offsets uint64[n + 1]); before that, the decoder's stdout side
+        effect (ltsv_decoder.rs:99), reproduced from the rows' flags"""
+        if self.fmt == L.FG_LTSV and tab.n and bool(((tab.a["meta"][:tab.n] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
             import sys
 
             from .tables import tables_stdout
 
             # (only when a row carries the flag; fg_tables_stdout reads [offsets[i], offsets[i+1]) only: no copy, no slack -- ADVICE r3)
-            if n_rows and bool(((tab.a["meta"][:n_rows] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
-                text = tables_stdout(tab, self.fmt, data, offsets)
-                if text:
-                    sys.stdout.write(text.decode("utf-8", "replace"))
+            text = tables_stdout(tab, self.fmt, data, offsets, framing)
+            if text:
+                sys.stdout.write(text.decode("utf-8", "replace"))
         blob, offs = tab.serialize(self.fmt, data, offsets, cfg=self._cfg)
-        raw = blob.tobytes()
-        return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(len(lines))]
+        return blob.tobytes(), offs
 
     def decode_device(self, d_bytes, d_offsets, tables: DeviceTables, stream=None) -> None:
         """Device-resident hot path: torch uint8 / int64|uint64 tensors already in HBM.
@@ -295,7 +315,8 @@ class Decoder:
         cap = cap_slots if cap_slots is not None else nbytes // 16 + K + 16
         d_first = torch.empty(K + 1, dtype=torch.int64, device=d_bytes.device)
         d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=d_bytes.device)
-        while True:
+
+        def attempt(cap):
             d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=d_bytes.device)
             d_kind = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_bytes.device)
             n = C.c_uint64()
@@ -303,11 +324,10 @@ class Decoder:
                                                d_seg_final.data_ptr() if d_seg_final is not None else None, K, d_offsets.data_ptr(),
                                                d_kind.data_ptr(), cap, d_first.data_ptr(), d_cons.data_ptr(), C.byref(n),
                                                C.c_void_p(stream.cuda_stream))
-            if rc == L.FG_ERR_ENT_OVERFLOW and cap_slots is None:
-                cap = int(n.value)
-                continue
-            L.check(rc, "fg_frame_multi_device")
-            return d_offsets, d_kind, int(n.value), d_first, d_cons[:K]
+            return rc, int(n.value), (d_offsets, d_kind)
+
+        n, (d_offsets, d_kind) = _framed_within("fg_frame_multi_device", cap, cap_slots is not None, 0, attempt)
+        return d_offsets, d_kind, n, d_first, d_cons[:K]
 
     def frame_decode_multi(self, raw: Union[bytes, np.ndarray], seg_starts, seg_final, framing: int):
         """fg_frame_decode_multi_batch: the chunks of K connections back to back in, tables out.  Returns (HostTables or None, offsets
@@ -325,12 +345,8 @@ class Decoder:
                                                     C.byref(st), C.byref(off), C.byref(kind), C.byref(first), C.byref(cons), C.byref(n)),
                 "fg_frame_decode_multi_batch")
         ns = int(n.value)
-        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
-        offsets = np.ctypeslib.as_array(C.cast(off, u64p), (ns + 1,)).copy()
-        kinds = np.ctypeslib.as_array(C.cast(kind, u8p), (ns,)).copy() if ns else np.zeros(0, np.uint8)
-        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
-        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
-        return (HostTables.from_struct(st) if ns else None), offsets, kinds, seg_first, seg_cons
+        return ((HostTables.from_struct(st) if ns else None), _copied(off, C.c_uint64, ns + 1), _copied(kind, C.c_uint8, ns),
+                _copied(first, C.c_uint64, K + 1), _copied(cons, C.c_uint64, K))
 
     def frame_syslen_multi_device(self, d_bytes, d_seg_starts, cap_frames: Optional[int] = None, stream=None):
         """fg_frame_syslen_multi_device: d_bytes holds the octet-counted chunks of K connections back to back (segment k =
@@ -350,7 +366,8 @@ class Decoder:
         d_first = torch.empty(K + 1, dtype=torch.int64, device=dev)
         d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
         d_stop = torch.empty(max(K, 1), dtype=torch.uint8, device=dev)
-        while True:
+
+        def attempt(cap):
             d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=dev)
             d_starts = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
             d_bad = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
@@ -359,12 +376,10 @@ class Decoder:
                                                       d_offsets.data_ptr(), d_starts.data_ptr(), d_bad.data_ptr(), cap, d_first.data_ptr(),
                                                       d_cons.data_ptr(), d_stop.data_ptr(), C.byref(n), C.byref(payload),
                                                       C.c_void_p(stream.cuda_stream))
-            if rc == L.FG_ERR_ENT_OVERFLOW and cap_frames is None:
-                cap = int(n.value) + 16
-                continue
-            L.check(rc, "fg_frame_syslen_multi_device")
-            k = int(n.value)
-            return d_packed, d_offsets[:k + 1], d_starts[:k], d_bad[:k], k, d_first, d_cons[:K], d_stop[:K], int(payload.value)
+            return rc, int(n.value), (d_offsets, d_starts, d_bad, int(payload.value))
+
+        k, (d_offsets, d_starts, d_bad, payload) = _framed_within("fg_frame_syslen_multi_device", cap, cap_frames is not None, 16, attempt)
+        return d_packed, d_offsets[:k + 1], d_starts[:k], d_bad[:k], k, d_first, d_cons[:K], d_stop[:K], payload
 
     def frame_decode_syslen_multi(self, raw: Union[bytes, np.ndarray], seg_starts):
         """fg_frame_decode_syslen_multi_batch: the octet-counted chunks of K connections back to back in, tables out.  Returns
@@ -381,12 +396,8 @@ class Decoder:
                                                            starts.ctypes.data, K, C.byref(st), C.byref(fs), C.byref(first), C.byref(cons),
                                                            C.byref(stop), C.byref(n)), "fg_frame_decode_syslen_multi_batch")
         nf = int(n.value)
-        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
-        frame_starts = np.ctypeslib.as_array(C.cast(fs, u64p), (nf,)).copy() if nf else np.zeros(0, np.uint64)
-        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
-        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
-        seg_stop = np.ctypeslib.as_array(C.cast(stop, u8p), (K,)).copy() if K else np.zeros(0, np.uint8)
-        return (HostTables.from_struct(st) if nf else None), frame_starts, seg_first, seg_cons, seg_stop
+        return ((HostTables.from_struct(st) if nf else None), _copied(fs, C.c_uint64, nf), _copied(first, C.c_uint64, K + 1),
+                _copied(cons, C.c_uint64, K), _copied(stop, C.c_uint8, K))
 
     def frame_capnp_multi_device(self, d_bytes, d_seg_starts, cap_slots: Optional[int] = None, stream=None):
         """fg_frame_capnp_multi_device: d_bytes holds the Cap'n Proto chunks of K connections back to back (segment k =
@@ -406,19 +417,18 @@ class Decoder:
         d_first = torch.empty(K + 1, dtype=torch.int64, device=dev)
         d_cons = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
         d_stop = torch.empty(max(K, 1), dtype=torch.uint8, device=dev)
-        while True:
+
+        def attempt(cap):
             d_offsets = torch.empty(cap + 1, dtype=torch.int64, device=dev)
             d_kind = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
             n = C.c_uint64()
             rc = L.lib().fg_frame_capnp_multi_device(self._ctx, d_bytes.data_ptr(), nbytes, d_seg_starts.data_ptr(), K, d_offsets.data_ptr(),
                                                      d_kind.data_ptr(), cap, d_first.data_ptr(), d_cons.data_ptr(), d_stop.data_ptr(),
                                                      C.byref(n), C.c_void_p(stream.cuda_stream))
-            if rc == L.FG_ERR_ENT_OVERFLOW and cap_slots is None:
-                cap = int(n.value) + 16
-                continue
-            L.check(rc, "fg_frame_capnp_multi_device")
-            k = int(n.value)
-            return d_offsets[:k + 1], d_kind[:k], k, d_first, d_cons[:K], d_stop[:K]
+            return rc, int(n.value), (d_offsets, d_kind)
+
+        k, (d_offsets, d_kind) = _framed_within("fg_frame_capnp_multi_device", cap, cap_slots is not None, 16, attempt)
+        return d_offsets[:k + 1], d_kind[:k], k, d_first, d_cons[:K], d_stop[:K]
 
     def frame_decode_capnp_multi(self, raw: Union[bytes, np.ndarray], seg_starts):
         """fg_frame_decode_capnp_multi_batch: the Cap'n Proto chunks of K connections back to back in, tables out.  Returns (HostTables
@@ -435,13 +445,8 @@ class Decoder:
                                                           C.byref(st), C.byref(off), C.byref(kind), C.byref(first), C.byref(cons),
                                                           C.byref(stop), C.byref(n)), "fg_frame_decode_capnp_multi_batch")
         ns = int(n.value)
-        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
-        offsets = np.ctypeslib.as_array(C.cast(off, u64p), (ns + 1,)).copy()
-        kinds = np.ctypeslib.as_array(C.cast(kind, u8p), (ns,)).copy() if ns else np.zeros(0, np.uint8)
-        seg_first = np.ctypeslib.as_array(C.cast(first, u64p), (K + 1,)).copy()
-        seg_cons = np.ctypeslib.as_array(C.cast(cons, u64p), (K,)).copy() if K else np.zeros(0, np.uint64)
-        seg_stop = np.ctypeslib.as_array(C.cast(stop, u8p), (K,)).copy() if K else np.zeros(0, np.uint8)
-        return (HostTables.from_struct(st) if ns else None), offsets, kinds, seg_first, seg_cons, seg_stop
+        return ((HostTables.from_struct(st) if ns else None), _copied(off, C.c_uint64, ns + 1), _copied(kind, C.c_uint8, ns),
+                _copied(first, C.c_uint64, K + 1), _copied(cons, C.c_uint64, K), _copied(stop, C.c_uint8, K))
 
     # -- the UDP input (input/udp_input.rs:100-143) -------------------------------------------------------
     def udp_decode_packed(self, data: np.ndarray, offsets: np.ndarray, max_inflated: Optional[int] = None):
@@ -564,30 +569,30 @@ class FlushPolicy:
 _RUST_WS = "\t\n\x0b\x0c\r \x85\xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a\u2028\u2029\u202f\u205f\u3000"
 
 
-class MultiStreamSplitter:
-    """The stream-side sibling of the UDP batcher: parks the chunks of MANY connections and hands them to the GPU together -- one
-    fg_frame_decode_multi_batch call frames every connection's bytes as its own stream and decodes the frames.  Per connection the
-    output is what LineSplitter::run / NulSplitter::run (splitter/line_splitter.rs:17-54, nul_splitter.rs:18-60) produce for the bytes
-    pushed so far: a Record per decoded line, or a DecodeError whose text is the reference's stderr line -- "Invalid UTF-8 input", or
-    "<decoder's error>: [<trimmed line>]" (NUL framing prints nothing for a frame that trims to nothing, nul_splitter.rs:41-46).
-    The unterminated tail of a connection's chunk is carried over and prepended to its next one; close(conn) is its EOF."""
+class _MultiSplitter:
+    """What the multi-connection splitters share: the chunks of many connections parked until the policy says the batch is due, and
+    the bytes each connection carries over from its last batch.  A subclass frames and decodes what _take() hands it in flush()."""
 
-    def __init__(self, decoder: Decoder, framing: int, policy: Optional[FlushPolicy] = None):
-        if framing not in (L.FG_FRAME_LINE, L.FG_FRAME_NUL):
-            raise ValueError("MultiStreamSplitter frames FG_FRAME_LINE or FG_FRAME_NUL streams")
-        self.decoder, self.framing, self.policy = decoder, framing, policy or FlushPolicy()
+    PUSH_REFUSED = "push after the connection ended"
+
+    def __init__(self, decoder: Decoder, policy: Optional[FlushPolicy] = None):
+        self.decoder, self.policy = decoder, policy or FlushPolicy()
         self._carry: dict = {}     # conn -> bytes carried over from its last flushed chunk
         self._pending: dict = {}   # conn -> chunks pushed since the last flush (insertion order = arrival order)
-        self._closed: set = set()
+        self._closed: set = set()  # close() seen, not flushed yet
         self._bytes = 0
         self._first_at: Optional[float] = None
+
+    def _ended(self, conn_id) -> bool:
+        """the connection is over for good: it may not push, and closing it again means nothing"""
+        return False
 
     def push(self, conn_id, chunk: bytes) -> list:
         """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
         import time
 
-        if conn_id in self._closed:
-            raise ValueError("push after close")
+        if conn_id in self._closed or self._ended(conn_id):
+            raise ValueError(self.PUSH_REFUSED)
         if chunk:
             self._pending.setdefault(conn_id, []).append(bytes(chunk))
             self._bytes += len(chunk)
@@ -598,41 +603,65 @@ class MultiStreamSplitter:
         return self.flush() if due else []
 
     def close(self, conn_id) -> None:
-        """the connection's EOF: its unterminated tail is a frame at the next flush"""
-        self._closed.add(conn_id)
-        self._pending.setdefault(conn_id, [])
+        """the connection's EOF, acted on at the next flush (the class says how)"""
+        if not self._ended(conn_id):
+            self._closed.add(conn_id)
+            self._pending.setdefault(conn_id, [])
 
     def pending_bytes(self) -> int:
         return self._bytes
 
-    def flush(self) -> list:
-        """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
+    def _take(self, align: int = 1):
+        """-> (conns in arrival order, what each holds: carry + parked chunks, raw, starts uint64[K + 1]) and resets the batch; raw holds
+        the first len - len % align bytes of every connection back to back, connection k at raw[starts[k]:starts[k + 1]]"""
         conns = list(self._pending)
         segs = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
-        final = [1 if c in self._closed else 0 for c in conns]
         self._pending, self._bytes, self._first_at = {}, 0, None
-        for c in conns:
-            self._closed.discard(c)
+        sent = [s[:len(s) - len(s) % align] for s in segs]
+        starts = np.zeros(len(segs) + 1, np.uint64)
+        starts[1:] = np.cumsum([len(s) for s in sent], dtype=np.uint64)
+        return conns, segs, b"".join(sent), starts
+
+
+class _EndingSplitter(_MultiSplitter):
+    """... whose connections can end for good (their EOF, or input that ends them): _over"""
+
+    def __init__(self, decoder: Decoder, policy: Optional[FlushPolicy] = None):
+        super().__init__(decoder, policy)
+        self._over: set = set()
+
+    def _ended(self, conn_id) -> bool:
+        return conn_id in self._over
+
+
+class MultiStreamSplitter(_MultiSplitter):
+    """The stream-side sibling of the UDP batcher: parks the chunks of MANY connections and hands them to the GPU together -- one
+    fg_frame_decode_multi_batch call frames every connection's bytes as its own stream and decodes the frames.  Per connection the
+    output is what LineSplitter::run / NulSplitter::run (splitter/line_splitter.rs:17-54, nul_splitter.rs:18-60) produce for the bytes
+    pushed so far: a Record per decoded line, or a DecodeError whose text is the reference's stderr line -- "Invalid UTF-8 input", or
+    "<decoder's error>: [<trimmed line>]" (NUL framing prints nothing for a frame that trims to nothing, nul_splitter.rs:41-46).
+    The unterminated tail of a connection's chunk is carried over and prepended to its next one; close(conn) is its EOF."""
+
+    PUSH_REFUSED = "push after close"  # (a closed connection is forgotten at the next flush: its id may come back)
+
+    def __init__(self, decoder: Decoder, framing: int, policy: Optional[FlushPolicy] = None):
+        if framing not in (L.FG_FRAME_LINE, L.FG_FRAME_NUL):
+            raise ValueError("MultiStreamSplitter frames FG_FRAME_LINE or FG_FRAME_NUL streams")
+        super().__init__(decoder, policy)
+        self.framing = framing
+
+    def flush(self) -> list:
+        """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
+        conns, _, raw, starts = self._take()
+        final = [1 if c in self._closed else 0 for c in conns]  # (close(conn): its unterminated tail is a frame)
+        self._closed.difference_update(conns)
         if not conns:
             return []
-        raw = b"".join(segs)
-        starts = np.zeros(len(segs) + 1, np.uint64)
-        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
         tab, offsets, kind, first, _ = self.decoder.frame_decode_multi(raw, starts, final, self.framing)
-        fmt, out = self.decoder.fmt, []
+        out = []
         can, coffs = b"", None
         if tab is not None:
-            data = np.frombuffer(raw + b"\0" * 32, np.uint8)
-            if fmt == L.FG_LTSV and bool(((tab.a["meta"][:tab.n] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
-                import sys
-
-                from .tables import tables_stdout
-
-                text = tables_stdout(tab, fmt, data, offsets, self.framing)  # (the decoder's stdout side effect, ltsv_decoder.rs:99)
-                if text:
-                    sys.stdout.write(text.decode("utf-8", "replace"))
-            blob, coffs = tab.serialize(fmt, data, offsets, cfg=self.decoder._cfg)
-            can = blob.tobytes()
+            can, coffs = self.decoder._canonical(tab, np.frombuffer(raw + b"\0" * 32, np.uint8), offsets, self.framing)
         for k, c in enumerate(conns):
             res: list = []
             for i in range(int(first[k]), int(first[k + 1])):
@@ -663,7 +692,7 @@ SYSLEN_SHORT_READ = "failed to fill whole buffer"                        # read_
 SYSLEN_PANIC = "thread panicked: called `Result::unwrap()` on an `Err` value: FromUtf8Error (syslen_splitter.rs:32)"
 
 
-class MultiSyslenSplitter:
+class MultiSyslenSplitter(_EndingSplitter):
     """MultiStreamSplitter for OCTET-COUNTED connections (input.framing = "syslen": tcpco / tlsco inputs): parks the chunks of many
     connections and hands them to the GPU together -- one fg_frame_decode_syslen_multi_batch call walks every connection's bytes as its
     own stream and decodes the payloads.  Per connection the output is what SyslenSplitter::run (splitter/syslen_splitter.rs:17-57)
@@ -672,39 +701,6 @@ class MultiSyslenSplitter:
     be read ends the connection with DecodeError("Can't read message's length"), the first payload that is not valid UTF-8 with the
     reference's panic text (its `unwrap()`): later pushes raise.  close(conn) is its EOF: "Can't read message's length" with nothing
     carried, else what the reference reports for an EOF inside a length or a payload."""
-
-    def __init__(self, decoder: Decoder, policy: Optional[FlushPolicy] = None):
-        self.decoder, self.policy = decoder, policy or FlushPolicy()
-        self._carry: dict = {}
-        self._pending: dict = {}
-        self._closed: set = set()   # close() seen, EOF not reported yet
-        self._over: set = set()     # the connection ended: by its EOF, a bad length or an invalid payload
-        self._bytes = 0
-        self._first_at: Optional[float] = None
-
-    def push(self, conn_id, chunk: bytes) -> list:
-        """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
-        import time
-
-        if conn_id in self._closed or conn_id in self._over:
-            raise ValueError("push after the connection ended")
-        if chunk:
-            self._pending.setdefault(conn_id, []).append(bytes(chunk))
-            self._bytes += len(chunk)
-            if self._first_at is None:
-                self._first_at = time.monotonic()
-        due = self._bytes >= self.policy.max_bytes or (
-            self._first_at is not None and (time.monotonic() - self._first_at) * 1e3 >= self.policy.max_latency_ms)
-        return self.flush() if due else []
-
-    def close(self, conn_id) -> None:
-        """the connection's EOF, reported at the next flush"""
-        if conn_id not in self._over:
-            self._closed.add(conn_id)
-            self._pending.setdefault(conn_id, [])
-
-    def pending_bytes(self) -> int:
-        return self._bytes
 
     def _decode_error(self, r: DecodeError, payload: bytes) -> DecodeError:
         return DecodeError(f"{r}: [{payload.decode('utf-8').strip(_RUST_WS)}]")
@@ -726,16 +722,10 @@ class MultiSyslenSplitter:
 
     def flush(self) -> list:
         """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
-        conns = list(self._pending)
-        segs = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
-        self._pending, self._bytes, self._first_at = {}, 0, None
+        conns, segs, raw, starts = self._take()
         if not conns:
             return []
-        raw = b"".join(segs)
-        starts = np.zeros(len(segs) + 1, np.uint64)
-        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
         tab, fstart, first, cons, stop = self.decoder.frame_decode_syslen_multi(raw, starts)
-        fmt = self.decoder.fmt
         payloads = []
         for a in fstart:
             sp = raw.index(b" ", int(a))
@@ -743,17 +733,7 @@ class MultiSyslenSplitter:
         can, coffs = b"", None
         if tab is not None:
             data, offsets = pack_lines(payloads)
-            data = np.concatenate([data, np.zeros(32, np.uint8)])
-            if fmt == L.FG_LTSV and bool(((tab.a["meta"][:tab.n] >> 24) & L.FG_F_LTSV_NOVALUE).any()):
-                import sys
-
-                from .tables import tables_stdout
-
-                text = tables_stdout(tab, fmt, data, offsets)  # (the decoder's stdout side effect, ltsv_decoder.rs:99)
-                if text:
-                    sys.stdout.write(text.decode("utf-8", "replace"))
-            blob, coffs = tab.serialize(fmt, data, offsets, cfg=self.decoder._cfg)
-            can = blob.tobytes()
+            can, coffs = self.decoder._canonical(tab, np.concatenate([data, np.zeros(32, np.uint8)]), offsets)
             status = tab.a["meta"][:tab.n] & 0xFF
         out = []
         for k, c in enumerate(conns):
@@ -951,7 +931,7 @@ class CapnpSplitter:
         return [parse_canonical(raw[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
 
 
-class MultiCapnpSplitter:
+class MultiCapnpSplitter(_EndingSplitter):
     """MultiStreamSplitter for CAP'N PROTO connections (input.format = "capnp": flowgger instances relaying to a collector): parks the
     chunks of many connections and hands them to the GPU together -- one fg_frame_decode_capnp_multi_batch call walks every
     connection's bytes as its own stream and decodes the messages.  Per connection the output is what a CapnpSplitter of its own
@@ -962,51 +942,15 @@ class MultiCapnpSplitter:
     reported."""
 
     def __init__(self, decoder: Optional[CapnpDecoder] = None, policy: Optional[FlushPolicy] = None):
-        self.decoder, self.policy = decoder or CapnpDecoder(), policy or FlushPolicy()
-        self._carry: dict = {}
-        self._pending: dict = {}
-        self._closed: set = set()   # close() seen, not flushed yet
-        self._over: set = set()     # the connection ended: closed, or a table read_message refuses
-        self._bytes = 0
-        self._first_at: Optional[float] = None
-
-    def push(self, conn_id, chunk: bytes) -> list:
-        """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
-        import time
-
-        if conn_id in self._closed or conn_id in self._over:
-            raise ValueError("push after the connection ended")
-        if chunk:
-            self._pending.setdefault(conn_id, []).append(bytes(chunk))
-            self._bytes += len(chunk)
-            if self._first_at is None:
-                self._first_at = time.monotonic()
-        due = self._bytes >= self.policy.max_bytes or (
-            self._first_at is not None and (time.monotonic() - self._first_at) * 1e3 >= self.policy.max_latency_ms)
-        return self.flush() if due else []
-
-    def close(self, conn_id) -> None:
-        """the connection ends: what it still holds is framed at the next flush, an incomplete message is dropped"""
-        if conn_id not in self._over:
-            self._closed.add(conn_id)
-            self._pending.setdefault(conn_id, [])
-
-    def pending_bytes(self) -> int:
-        return self._bytes
+        super().__init__(decoder or CapnpDecoder(), policy)  # (_over: closed, or a table read_message refuses)
 
     def flush(self) -> list:
         """-> [(conn_id, [Record | DecodeError | CapnpStreamError, ...]), ...] for every connection that had chunks parked or was
         closed, in arrival order"""
-        conns = list(self._pending)
-        whole = [self._carry.pop(c, b"") + b"".join(self._pending[c]) for c in conns]
-        self._pending, self._bytes, self._first_at = {}, 0, None
+        # a segment starts on a word of the buffer: the last len % 8 bytes can never complete a message and stay on the host
+        conns, whole, raw, starts = self._take(align=8)
         if not conns:
             return []
-        # a segment starts on a word of the buffer: the last len % 8 bytes can never complete a message and stay on the host
-        segs = [w[:len(w) & ~7] for w in whole]
-        raw = b"".join(segs)
-        starts = np.zeros(len(segs) + 1, np.uint64)
-        starts[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
         tab, offsets, kind, first, cons, stop = self.decoder.frame_decode_capnp_multi(raw, starts)
         can, coffs = b"", None
         if tab is not None:

@@ -253,6 +253,54 @@ extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, ui
     return frame_blocks_fake(d_bytes, nbytes, delim, scratch, d_offsets, d_bad, cap, blk0, blk1, d_total_out);
 }
 
+// ---- the segmented framer (fg_frame_multi.hip), the contract above its fg_launch_frame_multi: every segment is split at the delimiter as
+//      a stream of its own; the unterminated tail of a segment that is not final is a FG_SLOT_CARRY slot and does not count as consumed;
+//      the two result words = the delimiters (a tail that a boundary ends counts as one; ~0: the one-pass form gave up) and the slots;
+//      NOTHING is written when the slots exceed `cap`.
+extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t, uint64_t) { return 64; }
+extern "C" int fg_launch_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, const uint64_t* d_seg_starts, const uint8_t* d_seg_final,
+                                     uint64_t n_segs, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first,
+                                     uint64_t* d_seg_consumed, uint64_t** d_result, hipStream_t, int classic) {
+    if (nbytes == 0 || n_segs == 0) return -1;
+    uint64_t* res = reinterpret_cast<uint64_t*>(scratch);
+    res[1] = 0;
+    if (fake_aborts(classic, scratch, 0, d_result)) return 0;
+    *d_result = res;
+    std::vector<uint64_t> c(n_segs + 1, 0), offs{0}, first, cons;
+    std::vector<uint8_t> kind;
+    for (uint64_t k = 1; k <= n_segs; ++k)  // (clamped as the kernels clamp them)
+        c[k] = k == n_segs ? nbytes : std::min(std::max(d_seg_starts[k], c[k - 1]), nbytes);
+    for (uint64_t k = 0; k < n_segs; ++k) {
+        uint64_t at = c[k];
+        bool bad = false;
+        first.push_back(kind.size());
+        cons.push_back(c[k + 1] - c[k]);
+        for (uint64_t p = c[k]; p < c[k + 1]; ++p) {
+            bad |= d_bytes[p] >= 0xF8u;
+            if (d_bytes[p] != (uint8_t)delim) continue;
+            offs.push_back(at = p + 1);
+            kind.push_back(bad ? FG_SLOT_BAD_UTF8 : FG_SLOT_FRAME);
+            bad = false;
+        }
+        if (at == c[k + 1]) continue;
+        const bool carry = !(d_seg_final && d_seg_final[k]);
+        offs.push_back(c[k + 1]);
+        kind.push_back(carry ? FG_SLOT_CARRY : bad ? FG_SLOT_BAD_UTF8 : FG_SLOT_FRAME);
+        if (carry) cons.back() = at - c[k];
+    }
+    const uint64_t n = kind.size();
+    first.push_back(n);
+    res[0] = n - (d_bytes[nbytes - 1] != (uint8_t)delim ? 1u : 0u);
+    res[1] = n;
+    if (n > cap) return 0;
+    memset(d_kind, 0, cap);
+    memcpy(d_offsets, offs.data(), (n + 1) * 8);
+    memcpy(d_kind, kind.data(), n);
+    memcpy(d_seg_first, first.data(), (n_segs + 1) * 8);
+    memcpy(d_seg_consumed, cons.data(), n_segs * 8);
+    return 0;
+}
+
 // ---- the fused launches (fg_fused.hpp): frame + decode of a raw chunk in one "kernel".  The real contract: offsets[i] = start of frame
 //      i, offsets[frames] = end of the last frame; rows and offsets only below `cap`; an unterminated tail is a frame iff `final`;
 //      the two result words = frames (may exceed cap), abort flag.
