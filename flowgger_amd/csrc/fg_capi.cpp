@@ -404,25 +404,11 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
     hipStream_t s = stream_of(ctx, stream);
     *n_frames = 0;
     if (nbytes == 0) return FG_OK;
-    int rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
-    uint64_t total = 0;
-    for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0;; classic = 1) {
-        uint64_t* d_total = nullptr;
-        FG_LAUNCH(ctx, fg_launch_frame(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, ctx->d_frame, d_offsets, d_bad_utf8,
-                                  cap_frames, &d_total, s, classic));
-        // frames = delimiters (+1 when the stream does not end with one)
-        FG_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        if (total != FG_FRAME_ABORTED || classic == 1) break;  // (the one-pass scan gave up waiting on a tile: the three-kernel form)
-    }
-    if (total + 1 > cap_frames) {
-        *n_frames = total + 1;
-        return FG_ERR_ENT_OVERFLOW;
-    }
-    uint64_t last_end = 0;
-    FG_HIP(ctx, hipMemcpyAsync(&last_end, d_offsets + total, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
+    // frames = delimiters (+1 when the stream does not end with one)
+    uint64_t total = 0, last_end = 0;
+    const int rc = frame_scan(ctx, framing, d_bytes, nbytes, d_offsets, d_bad_utf8, cap_frames, s, &total, &last_end);
+    if (rc == FG_ERR_ENT_OVERFLOW) *n_frames = total + 1;
+    if (rc != FG_OK) return rc;
     *n_frames = last_end == nbytes ? total : total + 1;
     return FG_OK;
 }
@@ -644,7 +630,7 @@ int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, cons
 }
 
 // reset_counter = false: a further slice of a batch whose entry counter is already live (the
-// pipelined host path decodes one batch as several slices on two streams).  span_bytes = the bytes
+// pipelined host paths decode one batch as several slices).  span_bytes = the bytes
 // the n lines cover (the launch geometry is planned from the average line length; nbytes is only
 // the readable range of d_bytes and, for a slice, covers the whole batch).
 int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
@@ -665,7 +651,7 @@ int fg_decode_frames_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
     int rc;
     if ((rc = ensure_launch_state(ctx)) != FG_OK) return rc;
     uint64_t* stash = ctx->d_stash;
-    if (lane) {  // a second launch that may be in flight at the same time (fg_transcode_batch's second lane)
+    if (lane) {  // (fg_ctx.hpp: the sliced fg_transcode_batch's odd slices)
         if (!ctx->d_stash2) FG_HIP(ctx, hipMalloc((void**)&ctx->d_stash2, fg_stash_bytes(ctx->stash_blocks)));
         stash = ctx->d_stash2;
     }
@@ -852,14 +838,11 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
     if (total) *total = 0;
-    fg::EncCfgHost h;
-    if (!fg::build_enc_cfg(src_fmt, ecfg, ctx->suffix, ctx->has_suffix, &h)) return FG_ERR_ARG;
-    const uint64_t keys_bytes = up(h.keys.size() * sizeof(fg::StaticKey), 16), blob_bytes = up(h.blob.size() + 16, 256);
-    const uint64_t cfg_bytes = up(keys_bytes + blob_bytes, 256);
     int rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_enc, &ctx->d_enc_cap, cfg_bytes + up(n * 4 + 4, 256) + up((n / 64 + 2) * 8, 256))) != FG_OK) return rc;
+    EncStage enc;
+    if ((rc = stage_encoder(ctx, src_fmt, ecfg, n, n / 64 + 2, &enc)) != FG_OK) return rc;
     uint64_t ent_used = ~0ull;
-    if (async && cfg_bytes <= fg_ctx::kEncSlot) {
+    if (async && enc.image_bytes <= fg_ctx::kEncSlot) {
         // the configuration through a pinned ring: the copy is queued, nothing waits (a slot is reused four calls later; its
         // event has long fired by then)
         if (!ctx->h_enc_ring) {
@@ -869,16 +852,13 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
         const uint32_t slot = ctx->enc_ring_next++ % fg_ctx::kEncRing;
         FG_HIP(ctx, hipEventSynchronize(ctx->ev_enc[slot]));
         uint8_t* hp = ctx->h_enc_ring + (size_t)slot * fg_ctx::kEncSlot;
-        memset(hp, 0, cfg_bytes);
-        if (!h.keys.empty()) memcpy(hp, h.keys.data(), h.keys.size() * sizeof(fg::StaticKey));
-        if (!h.blob.empty()) memcpy(hp + keys_bytes, h.blob.data(), h.blob.size());
-        FG_HIP(ctx, hipMemcpyAsync(ctx->d_enc, hp, cfg_bytes, hipMemcpyHostToDevice, s));
+        enc.write_image(hp);
+        FG_HIP(ctx, hipMemcpyAsync(ctx->d_enc, hp, enc.image_bytes, hipMemcpyHostToDevice, s));
         FG_HIP(ctx, hipEventRecord(ctx->ev_enc[slot], s));
         ent_used = ent_hint;
     } else {
-        std::vector<uint8_t> host(cfg_bytes, 0);
-        if (!h.keys.empty()) memcpy(host.data(), h.keys.data(), h.keys.size() * sizeof(fg::StaticKey));
-        if (!h.blob.empty()) memcpy(host.data() + keys_bytes, h.blob.data(), h.blob.size());
+        std::vector<uint8_t> host(enc.image_bytes);
+        enc.write_image(host.data());
         // (synchronous copy of a few hundred bytes: `host` goes out of scope at return); the same sync brings back the
         // number of entries the decode produced, which sizes the GELF ranking scratch
         FG_HIP(ctx, hipMemcpyAsync(ctx->d_enc, host.data(), host.size(), hipMemcpyHostToDevice, s));
@@ -887,15 +867,11 @@ int encode_device_impl(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg
         FG_HIP(ctx, hipStreamSynchronize(s));
         if (async) ent_used = ent_hint;
     }
-    fg::EncCfg cfg = h.cfg;
-    cfg.keys = reinterpret_cast<const fg::StaticKey*>(ctx->d_enc);
-    cfg.blob = ctx->d_enc + keys_bytes;
-    if (ent_used == 0) cfg.sort_slots = 1;           // no pairs at all (e.g. RFC5424 without structured data)
-    else if (ent_used <= 2 * n) cfg.sort_slots = 8;  // on average <= 2 pairs per line
-    // mirror [static keys | blob] in LDS when it is small (it nearly always is)
-    const uint32_t cfg_lds = keys_bytes + h.blob.size() <= 4096 ? (uint32_t)up(keys_bytes + h.blob.size(), 16) : 0u;
-    uint32_t* d_sizes = reinterpret_cast<uint32_t*>(ctx->d_enc + cfg_bytes);
-    uint64_t* d_block_sums = reinterpret_cast<uint64_t*>(ctx->d_enc + cfg_bytes + up(n * 4 + 4, 256));
+    fg::EncCfg& cfg = enc.cfg;
+    pick_sort_slots(&cfg, ent_used, n);
+    const uint32_t cfg_lds = enc.cfg_lds;
+    uint32_t* const d_sizes = enc.d_sizes;
+    uint64_t* const d_block_sums = enc.d_block_sums;
     fg::DevTables dt = to_dev(*tables);
     if (n == 0) {
         FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));

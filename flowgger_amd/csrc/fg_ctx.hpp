@@ -147,7 +147,7 @@ extern "C" int fg_launch_calib(int mode, const uint8_t* d_src, uint8_t* d_dst, u
 struct fg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // the pipelined host paths (created on first use): uploads / second lane
+    hipStream_t stream2 = nullptr;  // the pipelined host paths (created on first use): uploads
     hipStream_t stream3 = nullptr;  // ... downloads
     std::vector<hipEvent_t> ev_slice;  // ... two events per slice: uploaded, decoded
     hipStream_t s_up = nullptr, s_down = nullptr, s_run = nullptr;  // ... which of the three does what
@@ -170,7 +170,7 @@ struct fg_ctx {
     // per-wave scratch where entries (SD pairs / LTSV pairs / GELF extras) are parked between the
     // parse and the copy into the entry table (allocated on the first decode; 8 waves on every CU)
     uint64_t* d_stash = nullptr;
-    uint64_t* d_stash2 = nullptr;  // the second lane's (fg_transcode_batch)
+    uint64_t* d_stash2 = nullptr;  // ... of the launches with lane = 1 (fg_decode_frames_impl)
     uint32_t stash_blocks = 0;
     static constexpr uint32_t kPendingRing = 1024;
     uint32_t* d_pending = nullptr;  // ring of kPendingRing hand-over words (DevTables::pending), zeroed once
@@ -373,6 +373,66 @@ int grow_pinned(fg_ctx* ctx, void** p, uint64_t* cap, uint64_t need) {
     return FG_OK;
 }
 
+// One framing scan of d_bytes[0 .. nbytes) on s, shared by fg_frame_device and the host paths' frame_stage: the one-pass scan, launched
+// again in its classic three-kernel form when its look-back gave up (FG_FRAME_ABORTED).  *total = the delimiters = the terminated
+// frames; more of them (and a possible tail) than `cap` holds -> FG_ERR_ENT_OVERFLOW, nothing else is read; else *last_end = where the
+// last terminated frame ends (short of nbytes: an unterminated tail follows, whose end the scan has written behind it).
+int frame_scan(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, uint64_t* d_offsets, uint8_t* d_bad, uint64_t cap,
+               hipStream_t s, uint64_t* total, uint64_t* last_end) {
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
+    for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0;; classic = 1) {
+        uint64_t* d_total = nullptr;
+        FG_LAUNCH(ctx, fg_launch_frame(d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, ctx->d_frame, d_offsets, d_bad, cap, &d_total, s, classic));
+        FG_HIP(ctx, hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        if (*total != FG_FRAME_ABORTED || classic == 1) break;  // (the one-pass scan gave up waiting on a tile: the three-kernel form)
+    }
+    if (*total + 1 > cap) return FG_ERR_ENT_OVERFLOW;
+    FG_HIP(ctx, hipMemcpyAsync(last_end, d_offsets + *total, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+
+// The encoder kernels' configuration staged for n lines (fg_encode_device, fg_encode_device_async, the sliced fg_transcode_batch).
+// ctx->d_enc holds [static keys | blob] -- the IMAGE, image_bytes of it --, then a size per line, then `sum_words` block sums.  The
+// image is written to host memory of the caller's (write_image), and the caller copies it to ctx->d_enc: from where, on which stream
+// and whether anything waits for it is its business.
+struct EncStage {
+    fg::EncCfgHost host;
+    fg::EncCfg cfg{};              // keys / blob point into ctx->d_enc
+    uint32_t cfg_lds = 0;          // the bytes of [static keys | blob] the kernels mirror in LDS when it is small (it nearly always is), else 0
+    uint32_t* d_sizes = nullptr;
+    uint64_t* d_block_sums = nullptr;
+    uint64_t image_bytes = 0, keys_bytes = 0;
+    void write_image(uint8_t* dst) const {
+        memset(dst, 0, image_bytes);
+        if (!host.keys.empty()) memcpy(dst, host.keys.data(), host.keys.size() * sizeof(fg::StaticKey));
+        if (!host.blob.empty()) memcpy(dst + keys_bytes, host.blob.data(), host.blob.size());
+    }
+};
+int stage_encoder(fg_ctx* ctx, fg_format src_fmt, const fg_encode_cfg* ecfg, uint64_t n, uint64_t sum_words, EncStage* st) {
+    if (!fg::build_enc_cfg(src_fmt, ecfg, ctx->suffix, ctx->has_suffix, &st->host)) return FG_ERR_ARG;
+    st->keys_bytes = up(st->host.keys.size() * sizeof(fg::StaticKey), 16);
+    st->image_bytes = up(st->keys_bytes + up(st->host.blob.size() + 16, 256), 256);
+    const uint64_t sizes_bytes = up(n * 4 + 4, 256);
+    const int rc = grow_dev(ctx, (void**)&ctx->d_enc, &ctx->d_enc_cap, st->image_bytes + sizes_bytes + up(sum_words * 8, 256));
+    if (rc != FG_OK) return rc;
+    st->cfg = st->host.cfg;
+    st->cfg.keys = reinterpret_cast<const fg::StaticKey*>(ctx->d_enc);
+    st->cfg.blob = ctx->d_enc + st->keys_bytes;
+    const uint64_t text = st->keys_bytes + st->host.blob.size();
+    st->cfg_lds = text <= 4096 ? (uint32_t)up(text, 16) : 0u;
+    st->d_sizes = reinterpret_cast<uint32_t*>(ctx->d_enc + st->image_bytes);
+    st->d_block_sums = reinterpret_cast<uint64_t*>(ctx->d_enc + st->image_bytes + sizes_bytes);
+    return FG_OK;
+}
+// the GELF ranking scratch is sized by the pairs per line: `entries` of them in `lines` lines (~0: not known, the largest)
+inline void pick_sort_slots(fg::EncCfg* cfg, uint64_t entries, uint64_t lines) {
+    if (entries == 0) cfg->sort_slots = 1;                   // no pairs at all (e.g. RFC5424 without structured data)
+    else if (entries <= 2 * lines) cfg->sort_slots = 8;      // on average <= 2 pairs per line
+}
+
 // ctx->h_cnt: one pinned 64 KiB block of words the pipelined host paths read small results through.  Who owns which words:
 constexpr uint32_t kCntWords = 8192;
 constexpr uint32_t kCntSlices = 0, kMaxFrameSlices = 4096;  // frame_decode_sliced: the frame count after slice k, one word more for a tail's end
@@ -409,8 +469,10 @@ int copy_table(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, uint64_t
 }  // namespace
 
 // one decode launch on `stream` (fg_capi.cpp).  reset_counter = false: a further slice of a batch whose entry counter is already live;
-// span_bytes = the bytes the n lines cover (launch geometry is planned from the average line); lane = 1: a second launch that may be in
-// flight at the same time (its own entry stash)
+// span_bytes = the bytes the n lines cover (launch geometry is planned from the average line); lane = 1: the launch parks its entries
+// in the ctx's second stash and never regroups RFC3164 lines.  (The sliced fg_transcode_batch gives its slices lanes 0 and 1 in turn.
+// Its slices once ran on two lanes of streams; they are queued on one stream now, and the argument stays because it also decides
+// which RFC3164 kernel runs.)
 extern "C" int fg_finish_deferred_general(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                                const uint8_t* d_bad_utf8, const fg_tables* tables, void* stream);
 // one fused launch on `stream` (fg_capi.cpp): *d_total = its result words in ctx scratch.  FG_ERR_UNSUPPORTED: nothing was launched

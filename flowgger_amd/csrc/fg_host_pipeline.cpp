@@ -183,19 +183,21 @@ static int ensure_pipeline(fg_ctx* ctx, uint32_t slices) {
     ctx->s_down = ctx->stream3;
     return FG_OK;
 }
-// wait for everything a pipelined call has queued (its error paths: copies of earlier slices may still be in flight into the ctx's buffers)
-static void drain(fg_ctx* ctx) {
-    if (ctx->s_up) (void)hipStreamSynchronize(ctx->s_up);
-    (void)hipStreamSynchronize(ctx->stream);  // (s_run, and the one stream of a batch too small to be sliced)
-    if (ctx->s_down) (void)hipStreamSynchronize(ctx->s_down);
+// wait for everything a pipelined call has queued, on all three streams whatever the first of them reports: -> the first error
+static hipError_t drain(fg_ctx* ctx) {
+    hipError_t first = ctx->s_up ? hipStreamSynchronize(ctx->s_up) : hipSuccess;
+    const hipError_t run = hipStreamSynchronize(ctx->stream);  // (s_run, and the one stream of a batch too small to be sliced)
+    const hipError_t down = ctx->s_down ? hipStreamSynchronize(ctx->s_down) : hipSuccess;
+    if (first == hipSuccess) first = run;
+    return first != hipSuccess ? first : down;
 }
+// the bytes of a slice: a `parts`-th of the batch, 8 MiB at least, 32 MiB at most
+static uint64_t slice_bytes(uint64_t nbytes, uint32_t parts) { return std::min<uint64_t>(std::max<uint64_t>(nbytes / parts, 8ull << 20), 32ull << 20); }
 // slices of a host batch: small enough that filling and draining the pipeline costs little (1/8 of the batch at most), large
 // enough that a slice's fourteen API calls stay far below its transfer time
 static uint32_t slice_count(uint64_t nbytes, uint64_t n) {
     if (nbytes < (32ull << 20)) return 1;  // small batches: one stream, no events (a batch of one line costs what it did)
-    uint64_t slice = nbytes / 8;
-    if (slice < (8ull << 20)) slice = 8ull << 20;
-    if (slice > (32ull << 20)) slice = 32ull << 20;
+    const uint64_t slice = slice_bytes(nbytes, 8);
     uint64_t k = (nbytes + slice - 1) / slice;
     if (k < 1) k = 1;
     if (k > kMaxDecodeSlices) k = kMaxDecodeSlices;
@@ -312,6 +314,62 @@ struct LinkBoundGrid {  // (a per-call cap beside the caller's launch options, n
     explicit LinkBoundGrid(fg_ctx* c, uint32_t waves = 8) : ctx(c) { ctx->link_bound_waves = waves; }
     ~LinkBoundGrid() { ctx->link_bound_waves = 0; }
 };
+// GELF's exact form (k_gelf_general: the lines the fast form hands back) runs ONCE, behind the last slice, over all rows -- it is a
+// chain of dependent steps of ~170 us however few lines it gets, and launched per slice it was a quarter of the sliced raw-stream
+// path's GPU time
+struct DeferGeneral {
+    fg_ctx* ctx;
+    DeferGeneral(fg_ctx* c, bool on) : ctx(c) {
+        ctx->defer_general = on;
+        ctx->batch_epoch = 0;
+    }
+    ~DeferGeneral() {  // (also on every error path: nothing of this batch is left pending in the ctx)
+        ctx->defer_general = false;
+        ctx->batch_epoch = 0;
+    }
+};
+// Whatever way a pipelined call leaves, it first waits for what it queued: copies of earlier slices may still be in flight into the
+// ctx's buffers and out of the caller's bytes.  Constructed where the call may first have queued something (the exits before that pay
+// no synchronisation), BEHIND the locals that asynchronous copies read or write, so that those outlive the wait.  The success path
+// ends with done(), which reports what the wait reports.
+struct DrainGuard {
+    fg_ctx* ctx;
+    bool armed = true;
+    explicit DrainGuard(fg_ctx* c) : ctx(c) {}
+    ~DrainGuard() {
+        if (armed) (void)drain(ctx);
+    }
+    int done() {
+        FG_HIP(ctx, drain(ctx));  // (a wait that failed is repeated by the destructor)
+        armed = false;
+        return FG_OK;
+    }
+};
+// The slice loops keep a few slices queued beyond the one they collect: fill(k, issue) calls issue(slice) until `ahead` slices from
+// slice k on are out (k = slices: all of them); -> the first result that is not FG_OK.
+extern "C++" {  // (a template cannot stand in the extern "C" block around it)
+struct LookAhead {
+    uint32_t slices, ahead, issued = 0;
+    LookAhead(uint32_t slices_, uint32_t ahead_) : slices(slices_), ahead(ahead_) {}
+    template <class Issue>
+    int fill(uint32_t k, Issue&& issue) {
+        for (; issued < slices && issued < k + ahead; ++issued) {
+            const int rc = issue(issued);
+            if (rc != FG_OK) return rc;
+        }
+        return FG_OK;
+    }
+};
+}
+// a packed batch as fg_decode_batch and fg_transcode_batch take it: n + 1 offsets that lie within the buffer
+static int check_packed_batch(fg_format fmt, uint64_t nbytes, const uint64_t* offsets, uint64_t n) {
+    if (n == 0) return FG_OK;
+    if (!offsets || offsets[n] > nbytes || offsets[0] > offsets[n]) return FG_ERR_ARG;
+    if (fmt == FG_CAPNP)  // a message is an array of 8-byte words (include/fg_hip.h)
+        for (uint64_t i = 0; i <= n; ++i)
+            if (offsets[i] & 7u) return FG_ERR_ARG;
+    return FG_OK;
+}
 
 static int decode_batch_zero_copy(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, uint64_t n,
                                   fg_tables* out) {
@@ -354,11 +412,8 @@ static int decode_batch_zero_copy(fg_ctx* ctx, fg_format fmt, const uint8_t* byt
 
 int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets,
                     uint64_t n, fg_tables* out) {
-    if (!ctx || !out || (n && !offsets) || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
-    if (fmt == FG_CAPNP)  // a message is an array of 8-byte words (include/fg_hip.h)
-        for (uint64_t i = 0; i <= n && n; ++i)
-            if (offsets[i] & 7u) return FG_ERR_ARG;
+    if (!ctx || !out || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (check_packed_batch(fmt, nbytes, offsets, n) != FG_OK) return FG_ERR_ARG;
     DeviceGuard g(ctx->device);
     int rc;
     if ((rc = decode_batch_zero_copy(ctx, fmt, bytes, nbytes, offsets, n, out)) != FG_ERR_UNSUPPORTED) return rc;
@@ -373,6 +428,8 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
     const bool piped = slices > 1;
     const hipStream_t s_down = piped ? ctx->s_down : ctx->stream, s_up = piped ? ctx->s_up : s_down, s_run = piped ? ctx->s_run : s_down;
     uint64_t ent_cap = first_ent_cap(fmt, nbytes);  // grown on overflow
+    uint64_t used = 0;
+    DrainGuard drained(ctx);
     for (;;) {
         const uint64_t total = carved_bytes(n, ent_cap);
         if ((rc = grow_dev(ctx, (void**)&ctx->d_tab, &ctx->d_tab_cap, total)) != FG_OK) return rc;
@@ -414,65 +471,43 @@ int fg_decode_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t n
             }
             return FG_OK;
         };
-        uint64_t used = 0;
+        used = 0;
         bool overflow = false;
-        uint32_t issued = 0;
+        LookAhead window(slices, 16);
         for (uint32_t k = 0; k < slices && n; ++k) {
-            while (issued < slices && issued < k + 16) {
-                if ((rc = issue(issued)) != FG_OK) {  // copies of earlier slices may still be in flight into h_tab / d_tab
-                    drain(ctx);
-                    return rc;
-                }
-                ++issued;
-            }
+            if ((rc = window.fill(k, issue)) != FG_OK) return rc;
             const uint64_t l0 = cut[k], rows = cut[k + 1] - l0;
             if (rows == 0) continue;
             if (piped) {
-                if (hipEventSynchronize(ctx->ev_slice[2 * k + 1]) != hipSuccess) {
-                    drain(ctx);
-                    return FG_ERR_HIP;
-                }
+                FG_HIP(ctx, hipEventSynchronize(ctx->ev_slice[2 * k + 1]));
                 const uint64_t cnt = ent_cnt[k];  // the counter after this slice's kernels: its entries are [used, cnt)
                 if (cnt > ent_cap) {
                     overflow = true;
                     break;
                 }
-                if ((rc = copy_rows(ctx, ht, dt, l0, rows, s_down)) != FG_OK || (rc = copy_entries(ctx, ht, dt, used, cnt, s_down)) != FG_OK) {
-                    drain(ctx);
-                    return rc;
-                }
+                if ((rc = copy_rows(ctx, ht, dt, l0, rows, s_down)) != FG_OK || (rc = copy_entries(ctx, ht, dt, used, cnt, s_down)) != FG_OK) return rc;
                 used = cnt;
             } else if ((rc = copy_rows(ctx, ht, dt, l0, rows, s_down)) != FG_OK) {
-                drain(ctx);
                 return rc;
             }
         }
         if (!piped || overflow) {  // one stream (a small batch), or the entry table ran out: the counter's final value
-            while (overflow && issued < slices) {  // (kernels past the capacity still count: the counter then says what the batch needs)
-                if ((rc = issue(issued)) != FG_OK) {
-                    drain(ctx);
-                    return rc;
-                }
-                ++issued;
+            if (overflow) {  // (kernels past the capacity still count: the counter then says what the batch needs)
+                if ((rc = window.fill(slices, issue)) != FG_OK) return rc;
+                FG_HIP(ctx, drain(ctx));
             }
-            if (overflow) drain(ctx);
             FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s_run));
             FG_HIP(ctx, hipStreamSynchronize(s_run));
             overflow = used > ent_cap;
         }
-        if (overflow) {
-            drain(ctx);
+        if (overflow) {  // (nothing is in flight: the tables may be grown)
             if (ent_cap >= kEntCapMax) return FG_ERR_ENT_OVERFLOW;
             ent_cap = next_ent_cap(used);
             continue;
         }
-        if (!piped && (rc = copy_entries(ctx, ht, dt, 0, used, s_down)) != FG_OK) {
-            drain(ctx);
-            return rc;
-        }
+        if (!piped && (rc = copy_entries(ctx, ht, dt, 0, used, s_down)) != FG_OK) return rc;
         *ht.ent_used = used;
-        FG_HIP(ctx, hipStreamSynchronize(s_down));
-        FG_HIP(ctx, hipStreamSynchronize(s_run));
+        if ((rc = drained.done()) != FG_OK) return rc;
         *out = ht;
         ctx->last_host_path = FG_PATH_DECODE_SLICED;
         return FG_OK;
@@ -691,25 +726,11 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
                                fg_tables* out, const uint64_t** out_offsets, uint64_t* n_frames, uint64_t* consumed) {
     int rc;
     LinkBoundGrid grid(ctx);
-    // GELF's exact form (k_gelf_general: the lines the fast form hands back) runs ONCE, behind the last slice, over all rows -- it is a
-    // chain of dependent steps of ~170 us however few lines it gets, and launched per slice it was a quarter of this path's GPU time
-    struct DeferGeneral {
-        fg_ctx* ctx;
-        explicit DeferGeneral(fg_ctx* c, bool on) : ctx(c) {
-            ctx->defer_general = on;
-            ctx->batch_epoch = 0;
-        }
-        ~DeferGeneral() {  // (also on every error path: nothing of this batch is left pending in the ctx)
-            ctx->defer_general = false;
-            ctx->batch_epoch = 0;
-        }
-    } defer(ctx, fmt == FG_GELF);
+    DeferGeneral defer(ctx, fmt == FG_GELF);
     const uint64_t blk = fg_frame_block_bytes();
-    // (sixteen slices or more: the first upload and the last decode + download run alone -- a sixteenth of the batch each, not an eighth)
-    uint64_t slice = nbytes / 16;
-    if (slice < (8ull << 20)) slice = 8ull << 20;
-    if (slice > (32ull << 20)) slice = 32ull << 20;
-    slice = slice / fg_frame_slice_align() * fg_frame_slice_align();  // (whole 64 KiB tiles of the one-pass scan)
+    // (sixteen slices or more: the first upload and the last decode + download run alone -- a sixteenth of the batch each, not an eighth;
+    //  whole 64 KiB tiles of the one-pass scan)
+    const uint64_t slice = slice_bytes(nbytes, 16) / fg_frame_slice_align() * fg_frame_slice_align();
     const uint32_t slices = (uint32_t)((nbytes + slice - 1) / slice);
     TableShares shares(ctx, slices);
     const uint64_t nblk_total = nbytes / blk + 1;
@@ -732,6 +753,8 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
     fg_tables ht, kt;
     carve(ctx->h_tab, cap, ent_cap, &ht, nullptr);
     if ((rc = pinned_tables_for_kernels(ctx, ht, &kt)) != FG_OK) return rc;
+    uint64_t last_end = 0, used = 0;  // (read back from the device)
+    DrainGuard drained(ctx);
     FG_HIP(ctx, hipMemsetAsync(kt.ent_used, 0, 8, s_run));
     FG_HIP(ctx, hipMemsetAsync(ctx->d_bad, 0, cap + 1, s_run));
     FG_HIP(ctx, hipEventRecord(ctx->ev_ready, s_run));
@@ -766,13 +789,9 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
         else if (k + 1 == slices) FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + up(nbytes, 16), 0, 16, s_up));
         uint64_t* d_total = nullptr;
         const uint64_t blk0 = b0 / blk, blk1 = k + 1 == slices ? nblk_total : b1 / blk;
-        int lrc = fg_launch_frame_slice(ctx->d_bytes, nbytes, delim, ctx->d_frame, ctx->d_offsets, ctx->d_bad, cap, blk0, blk1, &d_total, s_frame, src_dv,
-                                        (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0);
-        if (lrc == 0) lrc = fg_launch_poke64(d_total, cnt_dv + k, s_frame);
-        if (lrc != 0) {
-            ctx->last_hip = lrc;
-            return FG_ERR_HIP;
-        }
+        FG_LAUNCH(ctx, fg_launch_frame_slice(ctx->d_bytes, nbytes, delim, ctx->d_frame, ctx->d_offsets, ctx->d_bad, cap, blk0, blk1, &d_total, s_frame, src_dv,
+                                             (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0));
+        FG_LAUNCH(ctx, fg_launch_poke64(d_total, cnt_dv + k, s_frame));
         FG_HIP(ctx, hipEventRecord(ev[2 * k + 1], s_frame));
         if (src_dv) FG_HIP(ctx, hipStreamWaitEvent(s_run, ev[2 * k + 1], 0));
         return FG_OK;
@@ -790,40 +809,23 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
         FG_HIP(ctx, hipMemcpyAsync(ctx->h_off + f0 + (f0 ? 1 : 0), ctx->d_offsets + f0 + (f0 ? 1 : 0), (rows + (f0 ? 0 : 1)) * 8, hipMemcpyDeviceToHost, s_down));
         return FG_OK;
     };
-    uint32_t queued = 0;
+    LookAhead window(slices, src_dv ? 4u : 2u);  // framing queued ahead of the decode being issued
     for (uint32_t k = 0; k < slices; ++k) {
-        while (queued < slices && queued < k + (src_dv ? 4u : 2u)) {  // framing queued ahead of the decode being issued
-            if ((rc = enqueue(queued)) != FG_OK) {
-                drain(ctx);
-                return rc;
-            }
-            ++queued;
-        }
-        if (hipEventSynchronize(ev[2 * k + 1]) != hipSuccess) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
+        if ((rc = window.fill(k, enqueue)) != FG_OK) return rc;
+        FG_HIP(ctx, hipEventSynchronize(ev[2 * k + 1]));
         const uint64_t total = h_slice_cnt[k];  // delimiters up to the end of slice k = frames that are complete
-        if (total == FG_FRAME_ABORTED) {  // the one-pass scan gave up waiting on a tile (never seen): the one-piece path frames classically
-            drain(ctx);
-            return FG_ERR_UNSUPPORTED;
-        }
+        if (total == FG_FRAME_ABORTED) return FG_ERR_UNSUPPORTED;  // the one-pass scan gave up waiting on a tile (never seen): the one-piece path frames classically
         if (total + 1 > cap) {
-            drain(ctx);
             ctx->frames_per_byte = (double)(total + 1) / (double)(((uint64_t)k + 1) * slice);
             return FG_ERR_UNSUPPORTED;
         }
         const uint64_t b1 = k + 1 == slices ? nbytes : ((uint64_t)k + 1) * slice;
         if (k + 1 < slices) {
-            if ((rc = decode_rows(done, total, b1 - (uint64_t)k * slice)) != FG_OK) {
-                drain(ctx);
-                return rc;
-            }
+            if ((rc = decode_rows(done, total, b1 - (uint64_t)k * slice)) != FG_OK) return rc;
             done = total;
             continue;
         }
         // the last slice: an unterminated tail is one more frame when the stream ends here, else it stays with the caller
-        uint64_t last_end = 0;
         FG_HIP(ctx, hipMemcpyAsync(&last_end, ctx->d_offsets + total, 8, hipMemcpyDeviceToHost, s_run));
         FG_HIP(ctx, hipStreamSynchronize(s_run));
         const bool tail = last_end != nbytes;
@@ -834,25 +836,18 @@ static int frame_decode_sliced(fg_ctx* ctx, fg_format fmt, fg_framing framing, c
             n = total + 1;
         }
         *consumed = (tail && !final) ? last_end : nbytes;
-        if ((rc = decode_rows(done, n, *consumed > (uint64_t)k * slice ? *consumed - (uint64_t)k * slice : 1)) != FG_OK) {
-            drain(ctx);
-            return rc;
-        }
+        if ((rc = decode_rows(done, n, *consumed > (uint64_t)k * slice ? *consumed - (uint64_t)k * slice : 1)) != FG_OK) return rc;
         done = n;
     }
     {
         fg_tables all = kt;
         all.n = done;
-        if ((rc = fg_finish_deferred_general(ctx, framing, ctx->d_bytes, ctx->d_offsets, done, ctx->d_bad, &all, (void*)s_run)) != FG_OK) {
-            drain(ctx);
-            return rc;
-        }
+        if ((rc = fg_finish_deferred_general(ctx, framing, ctx->d_bytes, ctx->d_offsets, done, ctx->d_bad, &all, (void*)s_run)) != FG_OK) return rc;
     }
-    uint64_t used = 0;
     FG_HIP(ctx, hipMemcpyAsync(&used, kt.ent_used, 8, hipMemcpyDeviceToHost, s_run));
     FG_HIP(ctx, hipStreamSynchronize(s_run));
     if (done) ctx->frames_per_byte = (double)done / (double)nbytes;
-    drain(ctx);
+    if ((rc = drained.done()) != FG_OK) return rc;
     if (used > ent_cap) return FG_ERR_UNSUPPORTED;
     *ht.ent_used = used;
     ht.n = done;
@@ -1035,30 +1030,15 @@ int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
 // (zero padded); fills ctx->d_offsets / ctx->d_bad and says how many frames the chunk holds and how many of its bytes
 // they cover (an unterminated tail is a frame only when `final`).
 static int frame_stage(fg_ctx* ctx, fg_framing framing, uint64_t nbytes, int final, uint64_t* n_frames, uint64_t* consumed) {
-    hipStream_t s = ctx->stream;
-    int rc;
-    uint64_t cap = nbytes / 32 + 1024, total = 0, last_end = 0;
-    for (;;) {  // capacity: one frame per 32 bytes to start with, exact on retry
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return rc;
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return rc;
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_frame, &ctx->d_frame_cap, fg_frame_scratch_bytes(nbytes))) != FG_OK) return rc;
-        for (int classic = (ctx->lo.flags & FG_LO_FRAME_CLASSIC) ? 1 : (ctx->lo.flags & FG_LO_FRAME_SELFTEST_STALL) ? 2 : 0;; classic = 1) {
-            uint64_t* d_total = nullptr;
-            int lrc = fg_launch_frame(ctx->d_bytes, nbytes, framing == FG_FRAME_LINE ? 0x0Au : 0x00u, ctx->d_frame, ctx->d_offsets,
-                                      ctx->d_bad, cap, &d_total, s, classic);
-            if (lrc != 0) {
-                ctx->last_hip = lrc;
-                return FG_ERR_HIP;
-            }
-            FG_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipStreamSynchronize(s));
-            if (total != FG_FRAME_ABORTED || classic == 1) break;  // (the one-pass scan gave up waiting on a tile: the three-kernel form)
-        }
-        if (total + 1 <= cap) break;
-        cap = total + 16;
-    }
-    FG_HIP(ctx, hipMemcpyAsync(&last_end, ctx->d_offsets + total, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
+    uint64_t total = 0, last_end = 0;
+    // capacity: one frame per 32 bytes to start with, exact on retry
+    const int rc = frame_with_retry(nbytes / 32 + 1024, &total, [&](uint64_t cap) {
+        int r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (cap + 2) * 8)) != FG_OK) return r;
+        if ((r = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, cap + 1)) != FG_OK) return r;
+        return frame_scan(ctx, framing, ctx->d_bytes, nbytes, ctx->d_offsets, ctx->d_bad, cap, ctx->stream, &total, &last_end);
+    });
+    if (rc != FG_OK) return rc;
     const bool tail = last_end != nbytes;  // terminated frames = total
     *n_frames = total + ((tail && final) ? 1 : 0);
     *consumed = (tail && !final) ? last_end : nbytes;
@@ -1339,6 +1319,21 @@ extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* byt
     return b.finish(n, FG_PATH_FRAME_CAPNP_MULTI_HOST, FG_CAPNP, FG_FRAME_NONE, nbytes, ctx->d_bytes);
 }
 
+// The fixed arrays of an fg_transcoded -- out_offsets | meta | enc_status [| frame offsets] -- from byte `base` of the pinned block h:
+// *out's pointers name them (h null: only their size is asked for); -> the byte behind them.  The messages lie in front of them in
+// the one-piece form and behind them in the sliced one, where they grow slice by slice.
+static uint64_t transcoded_arrays(uint8_t* h, uint64_t base, uint64_t n, bool frames, fg_transcoded* out) {
+    const uint64_t offs_bytes = up((n + 1) * 8, 256);
+    const uint64_t o_meta = base + offs_bytes, o_st = o_meta + up(n * 4, 256), o_frames = o_st + up(n, 256);
+    if (h) {
+        out->out_offsets = reinterpret_cast<const uint64_t*>(h + base);
+        out->meta = reinterpret_cast<const uint32_t*>(h + o_meta);
+        out->enc_status = h + o_st;
+        out->frame_offsets = frames ? reinterpret_cast<const uint64_t*>(h + o_frames) : nullptr;
+    }
+    return o_frames + (frames ? offs_bytes : 0);
+}
+
 // fg_transcode_batch for a LARGE batch of framed lines: the batch goes through H2D -> decode -> encode -> D2H as slices of ~32 MiB
 // on the ctx's two streams, so that the upload of slice k+1 and the (2-3x larger) download of slice k's messages share the
 // full-duplex link, and the kernels hide behind both.  The host only waits for one small number per slice (its encoded size:
@@ -1380,8 +1375,7 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     // (three streams, not four: with a fourth the runtime put it on the hardware queue of s_down and every download waited for the
     //  last upload -- profiles/r06ai_transcode_timeline.json)
     if ((rc = ensure_pipeline(ctx, slices * 2u)) != FG_OK) return rc;  // (four events per slice)
-    const hipStream_t s_up = ctx->s_up, s_run = ctx->s_run, s_down = ctx->s_down, s_ahead = ctx->s_up;
-    hipStream_t lanes[1] = {s_run};
+    const hipStream_t s_up = ctx->s_up, s_run = ctx->s_run, s_down = ctx->s_down;
     if ((rc = ensure_h_cnt(ctx)) != FG_OK) return rc;
     std::vector<hipEvent_t>& ev = ctx->ev_slice;  // [4k + 1] slice k is decoded and counted, [4k + 2] its messages are written
     TableShares shares(ctx, slices);
@@ -1396,156 +1390,107 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     if ((rc = grow_dev(ctx, (void**)&ctx->d_tmeta, &ctx->d_tmeta_cap, offs_bytes + up(n, 256))) != FG_OK) return rc;
     uint64_t* d_out_offsets = reinterpret_cast<uint64_t*>(ctx->d_tmeta);
     uint8_t* d_enc_status = ctx->d_tmeta + offs_bytes;
-    fg::EncCfgHost h;
-    if (!fg::build_enc_cfg(fmt, ecfg, ctx->suffix, ctx->has_suffix, &h)) return FG_ERR_ARG;
-    const uint64_t keys_bytes = up(h.keys.size() * sizeof(fg::StaticKey), 16), blob_bytes = up(h.blob.size() + 16, 256);
-    const uint64_t cfg_bytes = up(keys_bytes + blob_bytes, 256);
-    const uint64_t sizes_bytes = up(n * 4 + 4, 256), sums_bytes = up((n / 64 + slices + 2) * 8, 256);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_enc, &ctx->d_enc_cap, cfg_bytes + sizes_bytes + sums_bytes)) != FG_OK) return rc;
-    std::vector<uint8_t> host(cfg_bytes, 0);
-    if (!h.keys.empty()) memcpy(host.data(), h.keys.data(), h.keys.size() * sizeof(fg::StaticKey));
-    if (!h.blob.empty()) memcpy(host.data() + keys_bytes, h.blob.data(), h.blob.size());
-    FG_HIP(ctx, hipMemcpyAsync(ctx->d_enc, host.data(), host.size(), hipMemcpyHostToDevice, lanes[0]));
-    FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, lanes[0]));
-    FG_HIP(ctx, hipMemsetAsync(dt.ent_used, 0, 8, lanes[0]));
-    FG_HIP(ctx, hipStreamSynchronize(lanes[0]));  // (`host` is a local; lane 1 may start)
-    fg::EncCfg cfg = h.cfg;
-    cfg.keys = reinterpret_cast<const fg::StaticKey*>(ctx->d_enc);
-    cfg.blob = ctx->d_enc + keys_bytes;
-    const uint32_t cfg_lds = keys_bytes + h.blob.size() <= 4096 ? (uint32_t)up(keys_bytes + h.blob.size(), 16) : 0u;
-    uint32_t* d_sizes = reinterpret_cast<uint32_t*>(ctx->d_enc + cfg_bytes);
-    uint64_t* d_block_sums = reinterpret_cast<uint64_t*>(ctx->d_enc + cfg_bytes + sizes_bytes);
+    EncStage enc;  // (a run of block sums per slice: one word more each)
+    if ((rc = stage_encoder(ctx, fmt, ecfg, n, n / 64 + slices + 2, &enc)) != FG_OK) return rc;
+    std::vector<uint8_t> image(enc.image_bytes);
+    enc.write_image(image.data());
+    uint64_t first_used = ~0ull, used = 0;  // (read back from the device)
+    DrainGuard drained(ctx);
+    FG_HIP(ctx, hipMemcpyAsync(ctx->d_enc, image.data(), image.size(), hipMemcpyHostToDevice, s_run));
+    FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s_run));
+    FG_HIP(ctx, hipMemsetAsync(dt.ent_used, 0, 8, s_run));
+    FG_HIP(ctx, hipStreamSynchronize(s_run));  // (the decodes on s_up read the offsets)
+    fg::EncCfg& cfg = enc.cfg;
+    const uint32_t cfg_lds = enc.cfg_lds;
+    uint32_t* const d_sizes = enc.d_sizes;
+    uint64_t* const d_block_sums = enc.d_block_sums;
     const uint32_t tile_cap = pick_tile_cap(ctx, nbytes, n, 40 * 1024, 1);
     fg::DevTables ddt = to_dev(dt);
     // ---- host buffer: fixed-size arrays first, the messages behind them (they grow slice by slice) ----
-    const uint64_t o_offs = 0, o_meta = o_offs + offs_bytes, o_st = o_meta + up(n * 4, 256), o_msgs = o_st + up(n, 256);
+    fg_transcoded res{};
+    const uint64_t o_msgs = transcoded_arrays(nullptr, 0, n, false, &res);
     uint64_t base = 0;  // encoded bytes of the slices finished so far
     auto sl_tables = [&](uint64_t l0, uint64_t l1) { return fg::rows_of(dt, l0, l1 - l0); };
     auto blocks_before = [&](uint32_t k) { return cut[k] / 64 + k; };  // first scratch sum of slice k (disjoint per slice)
     // queue a slice's upload, decode and count kernel (sixteen-byte aligned cuts: a slice starts with the sixteen bytes its first line begins in)
     auto enqueue = [&](uint32_t k) -> int {
-        hipStream_t s = s_ahead;
         const uint64_t l0 = cut[k], l1 = cut[k + 1];
         if (l1 == l0) return FG_OK;
         const uint64_t b0 = offsets[l0] & ~15ull, b1 = offsets[l1];
-        if (b1 > b0) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes + b0, bytes + b0, b1 - b0, hipMemcpyHostToDevice, s));
+        if (b1 > b0) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes + b0, bytes + b0, b1 - b0, hipMemcpyHostToDevice, s_up));
         const fg_tables sl = sl_tables(l0, l1);
-        // (the two lanes' kernels may be in flight at the same time: each lane parks its entries in its own stash)
-        int r = fg_decode_frames_impl(ctx, fmt, FG_FRAME_NONE, ctx->d_bytes, nbytes, ctx->d_offsets + l0, l1 - l0, nullptr, &sl, (void*)s, false,
+        int r = fg_decode_frames_impl(ctx, fmt, FG_FRAME_NONE, ctx->d_bytes, nbytes, ctx->d_offsets + l0, l1 - l0, nullptr, &sl, (void*)s_up, false,
                                    offsets[l1] - offsets[l0], k & 1u);
         if (r != FG_OK) return r;
         if (k == 0 && ecfg->encoder == FG_ENC_GELF) {  // the GELF ranking scratch is sized by the pairs per line: look at the first slice
-            uint64_t used = ~0ull;
-            FG_HIP(ctx, hipMemcpyAsync(&used, dt.ent_used, 8, hipMemcpyDeviceToHost, s));
-            FG_HIP(ctx, hipStreamSynchronize(s));
-            if (used == 0) cfg.sort_slots = 1;
-            else if (used <= 2 * (l1 - l0)) cfg.sort_slots = 8;
+            FG_HIP(ctx, hipMemcpyAsync(&first_used, dt.ent_used, 8, hipMemcpyDeviceToHost, s_up));
+            FG_HIP(ctx, hipStreamSynchronize(s_up));
+            pick_sort_slots(&cfg, first_used, l1 - l0);
         }
         fg::DevTables sdt = to_dev(sl);
         sdt.ent_cap = ddt.ent_cap;
-        if (fg_launch_encode_count(ctx->d_bytes, ctx->d_offsets + l0, l1 - l0, &sdt, &cfg, tile_cap, cfg_lds, d_sizes + l0,
-                                   d_block_sums + blocks_before(k), d_enc_status + l0, s) != 0)
-            return FG_ERR_HIP;
-        FG_HIP(ctx, hipEventRecord(ev[4 * k + 1], s));
+        FG_LAUNCH(ctx, fg_launch_encode_count(ctx->d_bytes, ctx->d_offsets + l0, l1 - l0, &sdt, &cfg, tile_cap, cfg_lds, d_sizes + l0,
+                                              d_block_sums + blocks_before(k), d_enc_status + l0, s_up));
+        FG_HIP(ctx, hipEventRecord(ev[4 * k + 1], s_up));
         return FG_OK;
     };
     // (a few slices ahead of the one being finished, not all at once: the forty API calls of a slice take the host a tenth of a
     //  millisecond, and thirty slices queued before the first scan kept the first download waiting for four)
-    uint32_t queued = 0;
+    LookAhead window(slices, 3);
     for (uint32_t k = 0; k < slices; ++k) {
-        while (queued < slices && queued < k + 3u) {
-            if ((rc = enqueue(queued)) != FG_OK) {
-                drain(ctx);
-                return rc;
-            }
-            ++queued;
-        }
+        if ((rc = window.fill(k, enqueue)) != FG_OK) return rc;
 
         // ---- finish slice k: offsets from `base`, its size (the host waits for that one number), the write kernel, the download ----
-        hipStream_t s = s_run;
         const uint64_t l0 = cut[k], l1 = cut[k + 1], rows = l1 - l0;
         if (rows == 0) continue;
-        if (hipStreamWaitEvent(s, ev[4 * k + 1], 0) != hipSuccess) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
-        if (fg_launch_encode_scan(d_sizes + l0, d_block_sums + blocks_before(k), rows, d_out_offsets + l0, base, s) != 0) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
+        FG_HIP(ctx, hipStreamWaitEvent(s_run, ev[4 * k + 1], 0));
+        FG_LAUNCH(ctx, fg_launch_encode_scan(d_sizes + l0, d_block_sums + blocks_before(k), rows, d_out_offsets + l0, base, s_run));
         uint64_t* const h_end = ctx->h_cnt + kCntEnd;
-        if (hipMemcpyAsync(h_end, d_out_offsets + l1, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipEventRecord(ctx->ev_ready, s) != hipSuccess) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
-        if (hipEventSynchronize(ctx->ev_ready) != hipSuccess) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
+        FG_HIP(ctx, hipMemcpyAsync(h_end, d_out_offsets + l1, 8, hipMemcpyDeviceToHost, s_run));
+        FG_HIP(ctx, hipEventRecord(ctx->ev_ready, s_run));
+        FG_HIP(ctx, hipEventSynchronize(ctx->ev_ready));
         const uint64_t end = *h_end;
         if (k == 0) {
             // size the output buffers from the first slice (+ 12 %); a batch that outgrows the estimate takes the one-piece path
             const uint64_t in0 = offsets[l1] - offsets[l0];
             const uint64_t est = (uint64_t)((double)end * ((double)nbytes / (double)(in0 ? in0 : 1)) * 1.12) + (4ull << 20);
-            if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, est)) != FG_OK || (rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, o_msgs + est)) != FG_OK) {
-                drain(ctx);
-                return rc;
-            }
+            if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, est)) != FG_OK) return rc;
+            if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, o_msgs + est)) != FG_OK) return rc;
         }
-        if (end > ctx->d_tout_cap || o_msgs + end > ctx->h_tout_cap) {
-            drain(ctx);
-            return FG_ERR_UNSUPPORTED;
-        }
+        if (end > ctx->d_tout_cap || o_msgs + end > ctx->h_tout_cap) return FG_ERR_UNSUPPORTED;
         const fg_tables sl = sl_tables(l0, l1);
         fg::DevTables sdt = to_dev(sl);
         sdt.ent_cap = ddt.ent_cap;
-        if (fg_launch_encode_write(ctx->d_bytes, ctx->d_offsets + l0, rows, &sdt, &cfg, tile_cap, cfg_lds, d_out_offsets + l0, ctx->d_tout, d_sizes + l0, s) != 0) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
-        uint8_t* hh = ctx->h_tout;
+        FG_LAUNCH(ctx, fg_launch_encode_write(ctx->d_bytes, ctx->d_offsets + l0, rows, &sdt, &cfg, tile_cap, cfg_lds, d_out_offsets + l0, ctx->d_tout, d_sizes + l0, s_run));
         // (the downloads stay with hipMemcpyAsync: a copy kernel of the library's own through the buffer's device view -- one wave per
         //  CU, eight 16-byte accesses in flight per lane -- moved a slice no faster than the runtime's blit kernel, 50 vs 52 GB/s, and
         //  slowed the kernels beside it just the same: it is the link's write queue that holds them up, not the CUs the copy takes)
         // at most three downloads queued: a stream's packets share a hardware queue with another stream's, and two dozen downloads
         // queued ahead held the uploads behind them up for 45 ms (4 M lines, profiles/r06al_transcode_host_trace.log)
-        bool ok = k < 3u || hipEventSynchronize(ev[4 * (k - 3u) + 3]) == hipSuccess;
-        ok = ok && hipEventRecord(ev[4 * k + 2], s) == hipSuccess && hipStreamWaitEvent(s_down, ev[4 * k + 2], 0) == hipSuccess;
-        if (ok && end > base) ok = hipMemcpyAsync(hh + o_msgs + base, ctx->d_tout + base, end - base, hipMemcpyDeviceToHost, s_down) == hipSuccess;
-        ok = ok && hipEventRecord(ev[4 * k + 3], s_down) == hipSuccess;
-        if (!ok) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
+        if (k >= 3u) FG_HIP(ctx, hipEventSynchronize(ev[4 * (k - 3u) + 3]));
+        FG_HIP(ctx, hipEventRecord(ev[4 * k + 2], s_run));
+        FG_HIP(ctx, hipStreamWaitEvent(s_down, ev[4 * k + 2], 0));
+        if (end > base) FG_HIP(ctx, hipMemcpyAsync(ctx->h_tout + o_msgs + base, ctx->d_tout + base, end - base, hipMemcpyDeviceToHost, s_down));
+        FG_HIP(ctx, hipEventRecord(ev[4 * k + 3], s_down));
         base = end;
     }
     // the fixed-size arrays -- offsets, meta, status of every line -- in three copies behind the last slice's messages (per slice they
     // were three more launches between two downloads: a tenth of a millisecond of an idle link per slice)
-    {
-        uint8_t* hh = ctx->h_tout;
-        bool ok = hipStreamWaitEvent(s_down, ev[4 * (slices - 1u) + 2], 0) == hipSuccess;
-        ok = ok && hipMemcpyAsync(hh + o_offs, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s_down) == hipSuccess;
-        ok = ok && hipMemcpyAsync(hh + o_meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s_down) == hipSuccess;
-        ok = ok && hipMemcpyAsync(hh + o_st, d_enc_status, n, hipMemcpyDeviceToHost, s_down) == hipSuccess;
-        if (!ok) {
-            drain(ctx);
-            return FG_ERR_HIP;
-        }
-    }
-    drain(ctx);
+    uint8_t* const hh = ctx->h_tout;
+    transcoded_arrays(hh, 0, n, false, &res);
+    FG_HIP(ctx, hipStreamWaitEvent(s_down, ev[4 * (slices - 1u) + 2], 0));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s_down));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s_down));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s_down));
+    if ((rc = drained.done()) != FG_OK) return rc;
     // an entry table that was too small shows up as FG_ST_OVERFLOW rows: the one-piece path sizes it exactly
-    uint64_t used = 0;
     FG_HIP(ctx, hipMemcpy(&used, dt.ent_used, 8, hipMemcpyDeviceToHost));
     if (used > ent_cap) return FG_ERR_UNSUPPORTED;
-    uint8_t* hh = ctx->h_tout;
-    out->n = n;
-    out->consumed = nbytes;
-    out->out = hh + o_msgs;
-    out->out_bytes = base;
-    out->out_offsets = reinterpret_cast<const uint64_t*>(hh + o_offs);
-    out->meta = reinterpret_cast<const uint32_t*>(hh + o_meta);
-    out->enc_status = hh + o_st;
-    out->frame_offsets = nullptr;
+    res.n = n;
+    res.consumed = nbytes;
+    res.out = hh + o_msgs;
+    res.out_bytes = base;
+    *out = res;
     return FG_OK;
 }
 
@@ -1559,11 +1504,7 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     if (syslen) ctx->last_syslen_stop = FG_SYSLEN_CLEAN;
     if (capnp) ctx->last_capnp_stop = FG_CAPNP_CLEAN;
     if (framing == FG_FRAME_NONE) {
-        if (n && !offsets) return FG_ERR_ARG;
-        if (n && (offsets[n] > nbytes || offsets[0] > offsets[n])) return FG_ERR_ARG;
-        if (fmt == FG_CAPNP)  // a message is an array of 8-byte words (include/fg_hip.h)
-            for (uint64_t i = 0; i <= n && n; ++i)
-                if (offsets[i] & 7u) return FG_ERR_ARG;
+        if (check_packed_batch(fmt, nbytes, offsets, n) != FG_OK) return FG_ERR_ARG;
     } else if (offsets) {
         return FG_ERR_ARG;  // a raw stream chunk is framed here; it does not come with offsets
     }
@@ -1635,24 +1576,22 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
                               d_enc_status, &total, FG_STREAM_OWN);
     }
     if (rc != FG_OK) return rc;
-    // 4. only the encoded stream and the per-line verdicts cross PCIe back
-    const uint64_t o_msgs = 0, o_offs = up(total, 256), o_meta = o_offs + offs_bytes, o_st = o_meta + up(n * 4, 256),
-                   o_frames = o_st + up(n, 256), h_total = o_frames + (framing != FG_FRAME_NONE ? offs_bytes : 0);
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, h_total)) != FG_OK) return rc;
+    // 4. only the encoded stream and the per-line verdicts cross PCIe back: the messages, the fixed arrays behind them
+    const bool frames = framing != FG_FRAME_NONE;
+    fg_transcoded res = *out;  // (n and consumed)
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, up(total, 256), n, frames, &res))) != FG_OK) return rc;
     uint8_t* h = ctx->h_tout;
-    if (total) FG_HIP(ctx, hipMemcpyAsync(h + o_msgs, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + o_offs, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + o_meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + o_st, d_enc_status, n, hipMemcpyDeviceToHost, s));
-    if (syslen) memcpy(h + o_frames, ctx->h_off, (n + 1) * 8);  // (the frame starts in the caller's chunk, prefix included)
-    else if (framing != FG_FRAME_NONE) FG_HIP(ctx, hipMemcpyAsync(h + o_frames, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    transcoded_arrays(h, up(total, 256), n, frames, &res);
+    if (total) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res.enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s));
+    if (syslen) memcpy((void*)res.frame_offsets, ctx->h_off, (n + 1) * 8);  // (the frame starts in the caller's chunk, prefix included)
+    else if (frames) FG_HIP(ctx, hipMemcpyAsync((void*)res.frame_offsets, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
-    out->out = h + o_msgs;
-    out->out_bytes = total;
-    out->out_offsets = reinterpret_cast<const uint64_t*>(h + o_offs);
-    out->meta = reinterpret_cast<const uint32_t*>(h + o_meta);
-    out->enc_status = h + o_st;
-    out->frame_offsets = framing != FG_FRAME_NONE ? reinterpret_cast<const uint64_t*>(h + o_frames) : nullptr;
+    res.out = h;
+    res.out_bytes = total;
+    *out = res;
     return FG_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <map>
 #include <vector>
 
 #define __device__
@@ -33,6 +34,31 @@ inline long long& fail_malloc_after() { static long long v = -1; return v; }  //
 inline unsigned long long& copies() { static unsigned long long v = 0; return v; }
 inline unsigned long long& bytes_h2d() { static unsigned long long v = 0; return v; }
 inline unsigned long long& bytes_d2h() { static unsigned long long v = 0; return v; }
+// The calls that can fail once work is queued -- copies and memsets, event record / wait / synchronise, stream synchronise, and the
+// fake kernel launchers (tests/native/host_pipeline_fake.cpp) -- are COUNTED, and the n-th next of them can be made to fail: it
+// returns an error and does nothing else.  Every injected error has a value of its own (1001, 1002, ...: a launcher returns it
+// negated), so that a test can tell the error a call recorded from one an earlier call left behind.  Per stream, what was queued since its last hipStreamSynchronize is counted too: a host
+// path that returns with that sum above zero has left work in flight.
+inline unsigned long long& calls() { static unsigned long long v = 0; return v; }
+inline long long& fail_call_after() { static long long v = -1; return v; }  // > 0: that many more counted calls, the last of them fails
+inline std::map<const void*, unsigned long long>& queued() { static std::map<const void*, unsigned long long> v; return v; }
+inline int& last_injected() { static int v = 1000; return v; }
+inline int call_fails() {  // 0, or the injected error
+    ++calls();
+    if (fail_call_after() <= 0 || --fail_call_after() != 0) return 0;
+    fail_call_after() = -1;
+    return ++last_injected();
+}
+inline int queue_fails(const void* stream) {  // an asynchronous call on `stream`
+    if (const int e = call_fails()) return e;
+    ++queued()[stream];
+    return 0;
+}
+inline unsigned long long in_flight() {
+    unsigned long long sum = 0;
+    for (const auto& kv : queued()) sum += kv.second;
+    return sum;
+}
 }  // namespace fakehip
 
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "ok" : "fake hip error"; }
@@ -47,7 +73,7 @@ static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     strcpy(p->name, "fake MI355X");
     return hipSuccess;
 }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
+static inline hipError_t hipDeviceSynchronize() { fakehip::queued().clear(); return hipSuccess; }
 static inline hipError_t hipMalloc(void** p, size_t n) {
     if (fakehip::fail_malloc_after() == 0) { *p = nullptr; return hipErrorOutOfMemory; }
     if (fakehip::fail_malloc_after() > 0) --fakehip::fail_malloc_after();
@@ -94,25 +120,47 @@ static inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const
     a->devicePointer = nullptr;
     return hipErrorInvalidValue;
 }
-static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
+namespace fakehip {
+inline void copy(void* d, const void* s, size_t n, hipMemcpyKind k) {
     memmove(d, s, n);
-    ++fakehip::copies();
-    if (k == hipMemcpyHostToDevice) fakehip::bytes_h2d() += n;
-    if (k == hipMemcpyDeviceToHost) fakehip::bytes_d2h() += n;
+    ++copies();
+    if (k == hipMemcpyHostToDevice) bytes_h2d() += n;
+    if (k == hipMemcpyDeviceToHost) bytes_d2h() += n;
+}
+}  // namespace fakehip
+static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
+    if (const int e = fakehip::call_fails()) return (hipError_t)e;
+    fakehip::copy(d, s, n, k);
     return hipSuccess;
 }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return hipMemcpy(d, s, n, k); }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    if (const int e = fakehip::queue_fails(st)) return (hipError_t)e;
+    fakehip::copy(d, s, n, k);
+    return hipSuccess;
+}
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    if (const int e = fakehip::queue_fails(st)) return (hipError_t)e;
+    memset(d, v, n);
+    return hipSuccess;
+}
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new fakehip_stream{0}; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+static inline hipError_t hipStreamDestroy(hipStream_t s) { fakehip::queued().erase(s); delete s; return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t s) {
+    if (const int e = fakehip::call_fails()) return (hipError_t)e;
+    fakehip::queued().erase(s);
+    return hipSuccess;
+}
+static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t, unsigned) { return (hipError_t)fakehip::queue_fails(s); }
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new fakehip_event{0}; return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->recorded = 1; return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    if (const int e = fakehip::queue_fails(s)) return (hipError_t)e;
+    e->recorded = 1;
+    return hipSuccess;
+}
+static inline hipError_t hipEventSynchronize(hipEvent_t) { return (hipError_t)fakehip::call_fails(); }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 1.0f; return hipSuccess; }
 
 // the few device builtins that non-template inline code of the shared headers names

@@ -12,6 +12,13 @@
 #include "../../flowgger_amd/csrc/fg_gather.cpp"
 #include "../../flowgger_amd/csrc/fg_materialize.cpp"
 
+// every fake launcher is a counted call of the fake runtime, queued on the stream it was given: it can be made to fail (it then does
+// nothing), and it is in flight until that stream is synchronised
+#define FAKE_LAUNCH(stream)                                        \
+    do {                                                           \
+        if (const int e_ = fakehip::queue_fails(stream)) return -e_; \
+    } while (0)
+
 namespace {
 unsigned long long g_launches = 0;
 unsigned long long g_kernel_uploaded = 0;  // bytes the fake framing scan copied itself (the raw-stream path without the copy engine)
@@ -87,27 +94,48 @@ extern "C" void fgf_counters(unsigned long long out[3], int reset) {
     if (reset) fakehip::copies() = fakehip::bytes_h2d() = fakehip::bytes_d2h() = 0;
 }
 extern "C" void fgf_fail_malloc_after(long long n) { fakehip::fail_malloc_after() = n; }
+// the counted calls (fakehip/hip/hip_runtime.h) so far; the n-th next of them fails (-1: none does); operations queued on streams that
+// have not been synchronised since
+extern "C" unsigned long long fgf_calls(void) { return fakehip::calls(); }
+extern "C" void fgf_fail_call_after(long long n) { fakehip::fail_call_after() = n; }
+extern "C" unsigned long long fgf_in_flight(void) { return fakehip::in_flight(); }
+extern "C" int fgf_last_injected(void) { return fakehip::last_injected(); }  // the value of the last error that was injected
 
 extern "C" uint64_t fg_stash_bytes(uint32_t blocks) { return 64ull * blocks; }
-extern "C" int fg_launch_poke64(const uint64_t* src, uint64_t* dst, hipStream_t) {
+extern "C" int fg_launch_poke64(const uint64_t* src, uint64_t* dst, hipStream_t s) {
+    FAKE_LAUNCH(s);
     *dst = *src;
     return 0;
 }
-extern "C" int fg_launch_calib(int mode, const uint8_t* src, uint8_t* dst, uint64_t nbytes, uint32_t*, hipStream_t) {
+extern "C" int fg_launch_calib(int mode, const uint8_t* src, uint8_t* dst, uint64_t nbytes, uint32_t*, hipStream_t s) {
+    FAKE_LAUNCH(s);
     if (mode != 1) memcpy(dst, src, nbytes / 16 * 16);
     return 0;
 }
-extern "C" int fg_launch_rfc5424(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t, uint64_t*, uint32_t,
-                                 uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) { return fake_decode(b, o, n, t, strip, bad); }
-extern "C" int fg_launch_ltsv(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::LtsvDevCfg*, uint64_t, hipStream_t,
-                              uint64_t*, uint32_t, uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) { return fake_decode(b, o, n, t, strip, bad); }
-extern "C" int fg_launch_gelf_general(const uint8_t*, const uint64_t*, uint64_t, const fg::DevTables*, hipStream_t, uint32_t, const uint8_t*) {
+extern "C" int fg_launch_rfc5424(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t s, uint64_t*, uint32_t,
+                                 uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) {
+    FAKE_LAUNCH(s);
+    return fake_decode(b, o, n, t, strip, bad);
+}
+extern "C" int fg_launch_ltsv(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::LtsvDevCfg*, uint64_t, hipStream_t s,
+                              uint64_t*, uint32_t, uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) {
+    FAKE_LAUNCH(s);
+    return fake_decode(b, o, n, t, strip, bad);
+}
+extern "C" int fg_launch_gelf_general(const uint8_t*, const uint64_t*, uint64_t, const fg::DevTables*, hipStream_t s, uint32_t, const uint8_t*) {
+    FAKE_LAUNCH(s);
     return 0;  // (the fake fast form leaves nothing pending)
 }
-extern "C" int fg_launch_gelf(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t, uint64_t*, uint32_t,
-                              uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) { return fake_decode(b, o, n, t, strip, bad); }
-extern "C" int fg_launch_rfc3164(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::r3164::Cfg*, uint32_t, hipStream_t,
-                                 uint32_t strip, const uint8_t* bad, uint8_t*, int) { return fake_decode(b, o, n, t, strip, bad); }
+extern "C" int fg_launch_gelf(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t s, uint64_t*, uint32_t,
+                              uint32_t strip, const uint8_t* bad, const fg_launch_opts*, fg::TicketSlot*) {
+    FAKE_LAUNCH(s);
+    return fake_decode(b, o, n, t, strip, bad);
+}
+extern "C" int fg_launch_rfc3164(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::r3164::Cfg*, uint32_t, hipStream_t s,
+                                 uint32_t strip, const uint8_t* bad, uint8_t*, int) {
+    FAKE_LAUNCH(s);
+    return fake_decode(b, o, n, t, strip, bad);
+}
 extern "C" uint64_t fg_rfc3164_scratch_bytes(uint64_t n) { return n * 17 + 4096; }
 extern "C" uint64_t fg_rfc3164_regroup_from(void) { return 1u << 20; }
 // ---- the fake encoder: an Ok row's message = its line + one '#' per entry + '\n' (so rows AND entry counts of the right slice matter);
@@ -116,8 +144,7 @@ extern "C" uint64_t fg_rfc3164_regroup_from(void) { return 1u << 20; }
 static uint32_t fake_size(const uint64_t* o, const fg::DevTables* t, uint64_t i) {
     return (t->meta[i] & 0xFFu) == 0u ? (uint32_t)(o[i + 1] - o[i]) + t->ent_count[i] + 1u : 0u;
 }
-extern "C" int fg_launch_encode_count(const uint8_t*, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::EncCfg*, uint32_t, uint32_t,
-                                      uint32_t* d_sizes, uint64_t* d_block_sums, uint8_t* d_status, hipStream_t) {
+static int fake_count(const uint64_t* o, uint64_t n, const fg::DevTables* t, uint32_t* d_sizes, uint64_t* d_block_sums, uint8_t* d_status) {
     for (uint64_t i = 0; i < n; ++i) {
         d_sizes[i] = fake_size(o, t, i);
         d_status[i] = (t->meta[i] & 0xFFu) == 0u ? 0 : 1;
@@ -126,7 +153,7 @@ extern "C" int fg_launch_encode_count(const uint8_t*, const uint64_t* o, uint64_
     }
     return 0;
 }
-extern "C" int fg_launch_encode_scan(const uint32_t* d_sizes, uint64_t* d_block_sums, uint64_t n, uint64_t* d_out_offsets, uint64_t base, hipStream_t) {
+static int fake_scan(const uint32_t* d_sizes, uint64_t* d_block_sums, uint64_t n, uint64_t* d_out_offsets, uint64_t base) {
     uint64_t at = base, check = 0;
     for (uint64_t i = 0; i < n; ++i) {
         d_out_offsets[i] = at;
@@ -136,13 +163,24 @@ extern "C" int fg_launch_encode_scan(const uint32_t* d_sizes, uint64_t* d_block_
     for (uint64_t j = 0; j < (n + 63) / 64; ++j) check += d_block_sums[j];  // (the sums the count step left must be this slice's)
     return check == at - base ? 0 : -7;
 }
-extern "C" int fg_launch_encode_sizes(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::EncCfg* c, uint32_t tc, uint32_t cl,
+extern "C" int fg_launch_encode_count(const uint8_t*, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::EncCfg*, uint32_t, uint32_t,
+                                      uint32_t* d_sizes, uint64_t* d_block_sums, uint8_t* d_status, hipStream_t s) {
+    FAKE_LAUNCH(s);
+    return fake_count(o, n, t, d_sizes, d_block_sums, d_status);
+}
+extern "C" int fg_launch_encode_scan(const uint32_t* d_sizes, uint64_t* d_block_sums, uint64_t n, uint64_t* d_out_offsets, uint64_t base, hipStream_t s) {
+    FAKE_LAUNCH(s);
+    return fake_scan(d_sizes, d_block_sums, n, d_out_offsets, base);
+}
+extern "C" int fg_launch_encode_sizes(const uint8_t*, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::EncCfg*, uint32_t, uint32_t,
                                       uint32_t* d_sizes, uint64_t* d_block_sums, uint8_t* d_status, uint64_t* d_out_offsets, hipStream_t s) {
-    const int rc = fg_launch_encode_count(b, o, n, t, c, tc, cl, d_sizes, d_block_sums, d_status, s);
-    return rc ? rc : fg_launch_encode_scan(d_sizes, d_block_sums, n, d_out_offsets, 0, s);
+    FAKE_LAUNCH(s);
+    const int rc = fake_count(o, n, t, d_sizes, d_block_sums, d_status);
+    return rc ? rc : fake_scan(d_sizes, d_block_sums, n, d_out_offsets, 0);
 }
 extern "C" int fg_launch_encode_write(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, const fg::EncCfg*, uint32_t, uint32_t,
-                                      const uint64_t* d_out_offsets, uint8_t* d_out, const uint32_t* d_sizes, hipStream_t) {
+                                      const uint64_t* d_out_offsets, uint8_t* d_out, const uint32_t* d_sizes, hipStream_t s) {
+    FAKE_LAUNCH(s);
     for (uint64_t i = 0; i < n; ++i) {
         if ((t->meta[i] & 0xFFu) != 0u) continue;
         if (!d_sizes || (d_sizes[i] & 0x7FFFFFFFu) != fake_size(o, t, i)) return -8;  // (the write step is handed the count step's sizes of ITS slice)
@@ -157,7 +195,8 @@ extern "C" int fg_launch_encode_write(const uint8_t* b, const uint64_t* o, uint6
 // ---- the device merge (fg_merge.hip), on "device" memory that is host memory here
 extern "C" uint64_t fg_merge_scratch_bytes(uint64_t rows) { return rows + 64; }
 extern "C" int fg_launch_merge_device(const fg_tables* parts, uint32_t g, const uint64_t* const* d_index, const fg_tables* out, uint8_t* d_src_part,
-                                      uint64_t, uint8_t* scratch, hipStream_t) {
+                                      uint64_t, uint8_t* scratch, hipStream_t s) {
+    FAKE_LAUNCH(s);
     // the real kernels' contract: rows at their arrival positions, entries DENSE in arrival order
     uint8_t* src = d_src_part ? d_src_part : scratch;
     std::vector<uint32_t> local(out->n, 0);
@@ -233,7 +272,8 @@ static bool fake_aborts(int classic, uint8_t* scratch, uint64_t blk1, uint64_t**
     return true;
 }
 extern "C" int fg_launch_frame(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_bad, uint64_t cap,
-                               uint64_t** d_total_out, hipStream_t, int classic) {
+                               uint64_t** d_total_out, hipStream_t s, int classic) {
+    FAKE_LAUNCH(s);
     memset(d_bad, 0, cap);
     if (fake_aborts(classic, scratch, nbytes / 16384 + 1, d_total_out)) return 0;
     const int rc = frame_blocks_fake(d_bytes, nbytes, delim, scratch, d_offsets, d_bad, cap, 0, nbytes / 16384 + 1, d_total_out);
@@ -242,7 +282,8 @@ extern "C" int fg_launch_frame(const uint8_t* d_bytes, uint64_t nbytes, uint32_t
     return rc;
 }
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_bad,
-                                     uint64_t cap, uint64_t blk0, uint64_t blk1, uint64_t** d_total_out, hipStream_t, const uint8_t* src, int classic) {
+                                     uint64_t cap, uint64_t blk0, uint64_t blk1, uint64_t** d_total_out, hipStream_t s, const uint8_t* src, int classic) {
+    FAKE_LAUNCH(s);
     if (blk1 > nbytes / 16384 + 1 || blk0 >= blk1) return -1;
     if (fake_aborts(classic, scratch, blk1, d_total_out)) return 0;
     if (src) {  // the scan uploads its blocks itself (whole 16-byte chunks, as the kernel's bounded buffer stores do)
@@ -260,7 +301,8 @@ extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, ui
 extern "C" uint64_t fg_frame_multi_scratch_bytes(uint64_t, uint64_t) { return 64; }
 extern "C" int fg_launch_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, const uint64_t* d_seg_starts, const uint8_t* d_seg_final,
                                      uint64_t n_segs, uint8_t* scratch, uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first,
-                                     uint64_t* d_seg_consumed, uint64_t** d_result, hipStream_t, int classic) {
+                                     uint64_t* d_seg_consumed, uint64_t** d_result, hipStream_t s, int classic) {
+    FAKE_LAUNCH(s);
     if (nbytes == 0 || n_segs == 0) return -1;
     uint64_t* res = reinterpret_cast<uint64_t*>(scratch);
     res[1] = 0;
@@ -331,15 +373,25 @@ static int fake_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t,
     fg::DevTables tt = *t;
     return fake_decode(b, offs.data(), rows, &tt, strip, bad.data());
 }
-extern "C" int fg_launch_rfc5424_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom*, hipStream_t, uint64_t*, uint32_t,
+extern "C" int fg_launch_rfc5424_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom*, hipStream_t s, uint64_t*, uint32_t,
                                        uint32_t strip, int final_, uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts*,
-                                       unsigned long long** d_total) { return fake_fused(b, nbytes, t, strip, final_, d_offsets, cap, scratch, d_total); }
-extern "C" int fg_launch_ltsv_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::LtsvDevCfg*, const fg::FusedGeom*, hipStream_t, uint64_t*,
-                                    uint32_t, uint32_t strip, int final_, uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts*,
-                                    unsigned long long** d_total) { return fake_fused(b, nbytes, t, strip, final_, d_offsets, cap, scratch, d_total); }
-extern "C" int fg_launch_gelf_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom*, hipStream_t, uint32_t strip, int final_,
-                                    uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts*, unsigned long long** d_total) {
+                                       unsigned long long** d_total) {
+    FAKE_LAUNCH(s);
     return fake_fused(b, nbytes, t, strip, final_, d_offsets, cap, scratch, d_total);
 }
-extern "C" int fg_launch_gelf_general_dev(const uint8_t*, const uint64_t*, uint64_t, const fg::DevTables*, hipStream_t, uint32_t, const uint8_t*,
-                                          const unsigned long long*) { return 0; }
+extern "C" int fg_launch_ltsv_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::LtsvDevCfg*, const fg::FusedGeom*, hipStream_t s, uint64_t*,
+                                    uint32_t, uint32_t strip, int final_, uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts*,
+                                    unsigned long long** d_total) {
+    FAKE_LAUNCH(s);
+    return fake_fused(b, nbytes, t, strip, final_, d_offsets, cap, scratch, d_total);
+}
+extern "C" int fg_launch_gelf_fused(const uint8_t* b, uint64_t nbytes, const fg::DevTables* t, const fg::FusedGeom*, hipStream_t s, uint32_t strip, int final_,
+                                    uint64_t* d_offsets, uint64_t cap, uint8_t* scratch, const fg_launch_opts*, unsigned long long** d_total) {
+    FAKE_LAUNCH(s);
+    return fake_fused(b, nbytes, t, strip, final_, d_offsets, cap, scratch, d_total);
+}
+extern "C" int fg_launch_gelf_general_dev(const uint8_t*, const uint64_t*, uint64_t, const fg::DevTables*, hipStream_t s, uint32_t, const uint8_t*,
+                                          const unsigned long long*) {
+    FAKE_LAUNCH(s);
+    return 0;
+}

@@ -3,7 +3,8 @@
 // answers FG_ERR_UNSUPPORTED and the call walks the segments on the host.  Test infrastructure.
 #include "host_pipeline_fake.cpp"
 
-extern "C" int fg_launch_capnp(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t, const uint8_t* bad,
+extern "C" int fg_launch_capnp(const uint8_t* b, const uint64_t* o, uint64_t n, const fg::DevTables* t, uint64_t, hipStream_t s, const uint8_t* bad,
                                const fg_launch_opts*, fg::TicketSlot*) {
+    FAKE_LAUNCH(s);
     return fake_decode(b, o, n, t, FG_FRAME_NONE, bad);
 }

@@ -37,9 +37,26 @@ def fake():
     lib.fg_decode_batch_device.argtypes = [vp, C.c_int, vp, u64, vp, u64, C.POINTER(L.fg_tables), vp]
     lib.fg_decode_batch.argtypes = [vp, C.c_int, vp, u64, vp, u64, C.POINTER(L.fg_tables)]
     lib.fg_frame_decode_batch.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, C.POINTER(L.fg_tables), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    lib.fg_transcode_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(L.fg_encode_cfg), vp, u64, vp, u64, C.c_int, C.POINTER(L.fg_transcoded)]
+    lib.fg_last_hip_error.argtypes = [vp]
     lib.fgf_launches.restype = C.c_ulonglong
     lib.fgf_fail_malloc_after.argtypes = [C.c_longlong]
+    lib.fgf_fail_call_after.argtypes = [C.c_longlong]
+    lib.fgf_calls.restype = lib.fgf_in_flight.restype = C.c_ulonglong
+    # NO IN-FLIGHT WORK ON ANY EXIT: after every successful call of the three host-buffer entries, in every test of this module -- the
+    # FG_ERR_UNSUPPORTED fall-backs inside them included (an entry table too small mid-batch, a scan that gives up) -- no stream of the
+    # fake runtime holds an operation queued since its last synchronise
+    for name in ("fg_decode_batch", "fg_frame_decode_batch", "fg_transcode_batch"):
+        setattr(lib, name, _idle_after(lib, getattr(lib, name)))
     return lib
+
+
+def _idle_after(lib, fn):
+    def call(*args):
+        rc = fn(*args)
+        assert rc != 0 or lib.fgf_in_flight() == 0, f"{fn.__name__} returned FG_OK with {lib.fgf_in_flight()} operations in flight"
+        return rc
+    return call
 
 
 class Ctx:
@@ -79,7 +96,8 @@ def device_reference(lib, data, offsets, ent_cap):
         setattr(st, name, b.ctypes.data)
     c = Ctx(lib)
     pad = np.concatenate([data, np.zeros(64, np.uint8)])
-    assert lib.fg_decode_batch_device(c.h, 0, pad.ctypes.data, data.size, offsets.ctypes.data, n, C.byref(st), None) == 0
+    # (on the ctx's own stream, FG_STREAM_OWN: the entry point is asynchronous, and closing the ctx waits for that stream)
+    assert lib.fg_decode_batch_device(c.h, 0, pad.ctypes.data, data.size, offsets.ctypes.data, n, C.byref(st), vp(-1)) == 0
     snap = snapshot(st, n)
     c.close()
     snap["_keep"] = bufs
@@ -471,7 +489,6 @@ def test_transcode_sliced_equals_one_piece(fake, dense):
     scan from the running base, write / downloads, the fixed-size arrays once at the end), output buffers sized from the first
     slice; same stream, offsets, row meta and encoder status as the one-piece
     form -- also when the entry table is too small for the sliced form (it then hands the batch to the one-piece form)."""
-    fake.fg_transcode_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(L.fg_encode_cfg), vp, u64, vp, u64, C.c_int, C.POINTER(L.fg_transcoded)]
     rng = np.random.default_rng(6)
     lines = corpus(300_000, rng, 30 if dense else 0, 40 if dense else 5, 300 if dense else 240)
     data, offsets = pack(lines)
@@ -506,6 +523,123 @@ def test_transcode_sliced_equals_one_piece(fake, dense):
     assert a[0][int(a[1][i]):int(a[1][i + 1])].tobytes() == lines[i] + b"#" * lines[i].count(b"=") + b"\n"
     if not dense:
         assert a[4] > b[4] >= 1  # the sliced form launched one decode per slice
+
+
+# ---- the failure sweep: a runtime call or a launch that fails anywhere inside a sliced host path
+
+@pytest.fixture(scope="module")
+def sweep_corpus():
+    """one corpus for the three entries, at the sizes that reach their sliced forms from pageable memory: > 64 MiB of framed lines
+    (fg_decode_batch, fg_transcode_batch), and the same lines as a raw stream >= 48 MiB with an unterminated tail (fg_frame_decode_batch:
+    a pageable chunk does not qualify for the fused form)"""
+    lines = corpus(300_000, np.random.default_rng(21))
+    data, offsets = pack(lines)
+    raw = np.frombuffer(b"".join(ln + b"\n" for ln in lines) + b"<1>tail without a terminator a=1", np.uint8).copy()
+    assert data.size > (64 << 20) and raw.size > (48 << 20)
+    return data, offsets, np.concatenate([raw, np.zeros(64, np.uint8)]), raw.size
+
+
+def _table_state(st, n):
+    snap = snapshot(st, n)
+    return [snap[k] for k in sorted(snap) if k != "used"] + [np.array([snap["used"], n])]
+
+
+def _entry_decode(fake, c, corp):
+    data, offsets, _, _ = corp
+    n = len(offsets) - 1
+    st = L.fg_tables()
+    rc = fake.fg_decode_batch(c.h, 0, data.ctypes.data, data.size, offsets.ctypes.data, n, C.byref(st))
+    return rc, (lambda: _table_state(st, n))
+
+
+def _entry_frame(fake, c, corp):
+    _, _, pad, nbytes = corp
+    st, po, nf, cons = L.fg_tables(), vp(), u64(), u64()
+    rc = fake.fg_frame_decode_batch(c.h, 0, 1, pad.ctypes.data, nbytes, 1, C.byref(st), C.byref(po), C.byref(nf), C.byref(cons))
+
+    def state():
+        n = int(nf.value)
+        return _table_state(st, n) + [np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), (n + 1,)).copy(), np.array([int(cons.value)])]
+    return rc, state
+
+
+def _entry_transcode(fake, c, corp):
+    data, offsets, _, _ = corp
+    n = len(offsets) - 1
+    ecfg = L.fg_encode_cfg()
+    ecfg.encoder, ecfg.merger = L.FG_ENC_GELF, L.FG_MERGE_LINE
+    out = L.fg_transcoded()
+    rc = fake.fg_transcode_batch(c.h, 0, 0, C.byref(ecfg), data.ctypes.data, data.size, offsets.ctypes.data, n, 1, C.byref(out))
+
+    def state():
+        get = lambda p, dt, cnt: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (cnt * np.dtype(dt).itemsize,)).view(dt).copy()  # noqa: E731
+        return [get(out.out, np.uint8, int(out.out_bytes)), get(out.out_offsets, np.uint64, n + 1), get(out.meta, np.uint32, n), get(out.enc_status, np.uint8, n),
+                np.array([int(out.n), int(out.consumed)])]
+    return rc, state
+
+
+# the clean run of each entry on the corpus above: (host path, kernel launches, H2D bytes, D2H bytes).  Measured before the slice
+# loops were given their drain guard and look-ahead window; the order and the volume of the work they queue is to stay what it was.
+CLEAN_RUNS = {"decode": (9, 74628250, 36596022), "frame": (9, 72528222, 2400032), "transcode": (4, 74628972, 77327715)}
+
+
+@pytest.mark.parametrize("entry", ["decode", "frame", "transcode"])
+def test_a_failed_runtime_call_anywhere_in_a_sliced_path_drains_and_leaves_the_ctx_usable(fake, sweep_corpus, entry):
+    """Every counted call of the fake runtime (asynchronous copies and memsets, event record / wait / synchronise, stream synchronise,
+    kernel launches) that a sliced host path makes is a place where the real runtime can fail with copies of earlier slices still in
+    flight into the ctx's buffers and out of the caller's bytes.  The call is run once clean (C counted calls: some 200, 110 and 70
+    for the three entries), then with call i failing for EVERY i of 1 .. C -- setup, uploads, every slice, the closing read-backs
+    and the last wait (were C to grow beyond 220: the first and last sixteen and 188 spread between them, about a minute per entry
+    either way).  Each failing run must return FG_ERR_HIP, leave the injected
+    error in fg_last_hip_error and NOTHING queued on any stream; the same call on the same ctx must then succeed with the result of a
+    ctx that never failed (table_shares, link_bound_waves, defer_general and batch_epoch were reset)."""
+    run = {"decode": _entry_decode, "frame": _entry_frame, "transcode": _entry_transcode}[entry]
+    path = {"decode": L.FG_PATH_DECODE_SLICED, "frame": L.FG_PATH_FRAME_SLICED, "transcode": 0}[entry]
+    fake.fg_last_host_path.argtypes = [vp]
+    ref = Ctx(fake)
+    rc, state = run(fake, ref, sweep_corpus)
+    assert rc == 0
+    want = state()
+    ref.close()
+    c = Ctx(fake)
+    assert run(fake, c, sweep_corpus)[0] == 0  # (the ctx's streams, events and buffers exist from here on: what follows allocates nothing)
+    cnt = (C.c_ulonglong * 3)()
+    fake.fgf_launches(1)
+    fake.fgf_counters(cnt, 1)
+    c0 = fake.fgf_calls()
+    rc, state = run(fake, c, sweep_corpus)
+    calls = int(fake.fgf_calls() - c0)
+    launches = int(fake.fgf_launches(1))
+    fake.fgf_counters(cnt, 1)
+    assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(state(), want))
+    if path:
+        assert fake.fg_last_host_path(c.h) == path
+    clean = (launches, int(cnt[1]), int(cnt[2]))
+    print(f"clean run of {entry}: {calls} counted calls, launches / H2D / D2H bytes = {clean}")
+    assert clean == CLEAN_RUNS[entry]
+    assert calls > 60
+    points = sorted(set(range(1, 17)) | set(range(calls - 15, calls + 1)) | {int(x) for x in np.linspace(17, calls - 16, 188)})
+    bad = []
+    for i in points:
+        fake.fgf_fail_call_after(i)
+        rc, _ = run(fake, c, sweep_corpus)
+        fake.fgf_fail_call_after(-1)
+        why = []
+        if rc != -2:
+            why.append(f"rc {rc}, not FG_ERR_HIP")
+        if abs(fake.fg_last_hip_error(c.h)) != fake.fgf_last_injected():
+            why.append(f"fg_last_hip_error {fake.fg_last_hip_error(c.h)}, injected {fake.fgf_last_injected()}")
+        if fake.fgf_in_flight() != 0:
+            why.append(f"{fake.fgf_in_flight()} operations in flight")
+        rc, state = run(fake, c, sweep_corpus)
+        if rc != 0:
+            why.append(f"the call after it: rc {rc}")
+        elif not all(np.array_equal(a, b) for a, b in zip(state(), want)):
+            why.append("the call after it: another result")
+        if why:
+            bad.append((i, why))
+    c.close()
+    assert not bad, f"{entry}: {len(bad)} of {len(points)} points of {calls} calls: {bad}"
 
 
 def test_the_timeline_probe_runs_against_the_fake_runtime(fake, tmp_path):
