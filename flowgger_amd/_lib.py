@@ -100,13 +100,19 @@ FG_PATH_FRAME_CAPNP_DEVICE, FG_PATH_FRAME_CAPNP_HOST = 8, 9
 FG_PATH_FRAME_MULTI = 10
 FG_PATH_FRAME_SYSLEN_MULTI_DEVICE, FG_PATH_FRAME_SYSLEN_MULTI_HOST = 11, 12
 FG_PATH_FRAME_CAPNP_MULTI_DEVICE, FG_PATH_FRAME_CAPNP_MULTI_HOST = 13, 14
-FG_SLOT_FRAME, FG_SLOT_BAD_UTF8, FG_SLOT_CARRY = 0, 1, 2  # fg_slot_kind
+FG_SLOT_FRAME, FG_SLOT_BAD_UTF8, FG_SLOT_CARRY, FG_SLOT_UNREACHED = 0, 1, 2, 3  # fg_slot_kind (UNREACHED: fg_transcode_multi_batch, SYSLEN)
 FG_LO_RESERVED = 0x40000000  # the library's own (fg_set_launch_opts clears it)
 
 
 class fg_transcoded(C.Structure):
     _fields_ = [("out", C.c_void_p), ("out_bytes", C.c_uint64), ("out_offsets", C.c_void_p), ("meta", C.c_void_p),
                 ("enc_status", C.c_void_p), ("frame_offsets", C.c_void_p), ("n", C.c_uint64), ("consumed", C.c_uint64)]
+
+
+class fg_transcoded_multi(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("out_bytes", C.c_uint64), ("out_offsets", C.c_void_p), ("meta", C.c_void_p),
+                ("enc_status", C.c_void_p), ("slot_offsets", C.c_void_p), ("slot_kind", C.c_void_p), ("seg_first", C.c_void_p),
+                ("seg_consumed", C.c_void_p), ("seg_stop", C.c_void_p), ("n", C.c_uint64)]
 
 
 class fg_tz_table(C.Structure):
@@ -212,6 +218,7 @@ def lib() -> C.CDLL:
     L.fg_frame_capnp_multi_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
     L.fg_frame_decode_capnp_multi_batch.argtypes = [vp, vp, u64, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    L.fg_transcode_multi_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(fg_encode_cfg), vp, u64, vp, vp, u64, C.POINTER(fg_transcoded_multi)]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

@@ -247,6 +247,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         if " fg_launch_syslen_multi\n" not in syms:
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without fg_launch_syslen_multi (fg_syslen_multi.hip)")
+        if " fg_launch_syslen_cut\n" not in syms:
+            LIB.unlink()
+            raise RuntimeError("libfg_hip was linked without fg_launch_syslen_cut (fg_syslen_multi.hip)")
         if " fg_launch_capnp_frame\n" not in syms:
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without fg_launch_capnp_frame (fg_capnp_frame.hip)")

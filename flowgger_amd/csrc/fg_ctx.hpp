@@ -103,6 +103,12 @@ extern "C" int fg_launch_syslen_multi(const uint8_t* d_bytes, uint64_t nbytes, c
                                       uint8_t* d_packed, uint64_t* d_offsets, uint64_t* d_starts, uint8_t* d_bad, uint64_t cap,
                                       uint64_t* d_seg_first, uint64_t* d_seg_consumed, uint8_t* d_seg_stop, uint32_t** d_hdr_out,
                                       hipStream_t stream) __attribute__((weak));
+// ... and the per-segment cut behind the first payload that is not UTF-8 (fg_syslen_multi.hip: d_bad 0 / 1 -> FG_SLOT_UNREACHED behind
+// each segment's first 1; d_cut = fg_syslen_cut_scratch_bytes(n_segs) bytes).  (WEAK references: without the kernels
+// fg_transcode_multi_batch computes the cut on the host from the mirrored verdicts.  The product library always has them.)
+extern "C" uint64_t fg_syslen_cut_scratch_bytes(uint64_t n_segs) __attribute__((weak));
+extern "C" int fg_launch_syslen_cut(uint8_t* d_bad, uint64_t n, const uint64_t* d_seg_first, uint64_t n_segs, uint32_t* d_cut,
+                                    hipStream_t stream) __attribute__((weak));
 // the segmented Cap'n Proto framer (fg_capnp_frame_multi.hip): *d_hdr_out = its result words in device memory (fg::capnpf H_DECLINE,
 // H_NFRAMES = the slots, H_DONE).  (WEAK references, as fg_launch_syslen above: without the kernels fg_frame_capnp_multi_device answers
 // FG_ERR_UNSUPPORTED and fg_frame_decode_capnp_multi_batch walks the segments on the host.  The product library always has them:

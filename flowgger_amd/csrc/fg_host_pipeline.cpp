@@ -1088,8 +1088,21 @@ static int decode_stage_to_host(fg_ctx* ctx, fg_format fmt, fg_framing framing, 
 // segment as its own stream, decode every slot, tables and per-segment / per-slot lists back.  One piece: a batch of connection chunks is
 // far below the sizes from which the sliced forms pay.  What the three entries share lives here; each keeps its format check, its
 // first capacity, its device call, its host hop and what its decode reads.
-//   ctx->d_ms: seg_starts | seg_first | seg_consumed | a byte per segment (seg_final going in, or seg_stop coming out)
+//   ctx->d_ms: seg_starts | seg_first | seg_consumed | a byte per segment (seg_final going in, or seg_stop coming out) | the cut's words
 //   ctx->h_ms: seg_first | seg_consumed | seg_stop | a u64 per slot (n + 1) | a byte per slot (n)     <- what the out_* pointers name
+// A front half (upload, device framer with retry, host hop on decline, the mirror) leaves a SegFramed; SegBatch::finish decodes it into
+// host tables (the fg_frame_decode_*multi_batch entries), SegBatch::finish_transcode runs the transcode tail on it
+// (fg_transcode_multi_batch).
+static int transcode_tail(fg_ctx* ctx, fg_format fmt, fg_framing dec_framing, const fg_encode_cfg* ecfg, const uint8_t* d_src, uint64_t src_bytes,
+                          uint64_t n, const uint8_t* d_bad, uint64_t in_bytes, bool frames, fg_transcoded* res);
+static uint64_t transcoded_arrays(uint8_t* h, uint64_t base, uint64_t n, bool frames, fg_transcoded* out);
+// what is to be decoded: n slots, ctx->d_offsets in d_src[0 .. used), ctx->d_bad nonzero -> FG_ST_BAD_UTF8 (not decoded)
+struct SegFramed {
+    uint64_t n = 0, used = 0;
+    const uint8_t* d_src = nullptr;
+    fg_framing framing = FG_FRAME_NONE;  // what the decode strips
+    int path = 0;                        // FG_PATH_*
+};
 struct SegBatch {
     fg_ctx* ctx;
     uint64_t n_segs;
@@ -1103,6 +1116,7 @@ struct SegBatch {
     hipStream_t s = nullptr;
     uint64_t *d_starts = nullptr, *d_first = nullptr, *d_cons = nullptr;
     uint8_t* d_seg8 = nullptr;
+    uint32_t* d_cut = nullptr;  // n_segs + 1 words (fg_launch_syslen_cut)
     uint64_t *h_first = nullptr, *h_cons = nullptr, *h_slot64 = nullptr;
     uint8_t *h_stop = nullptr, *h_slot8 = nullptr;
 
@@ -1130,12 +1144,13 @@ struct SegBatch {
         s = ctx->stream;
         int rc;
         const uint64_t w = up((n_segs + 1) * 8, 256);
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, 3 * w + up(n_segs + 1, 256))) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_ms, &ctx->d_ms_cap, 3 * w + up(n_segs + 1, 256) + up((n_segs + 1) * 4, 256))) != FG_OK) return rc;
         if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
         d_starts = reinterpret_cast<uint64_t*>(ctx->d_ms);
         d_first = reinterpret_cast<uint64_t*>(ctx->d_ms + w);
         d_cons = reinterpret_cast<uint64_t*>(ctx->d_ms + 2 * w);
         d_seg8 = ctx->d_ms + 3 * w;
+        d_cut = reinterpret_cast<uint32_t*>(d_seg8 + up(n_segs + 1, 256));
         if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
         FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
         if (n_segs) FG_HIP(ctx, hipMemcpyAsync(d_starts, seg_starts, (n_segs + 1) * 8, hipMemcpyHostToDevice, s));
@@ -1166,15 +1181,42 @@ struct SegBatch {
         if ((rc = put(h_slot64, slot64, n64 * 8)) != FG_OK) return rc;
         return o_slot8 ? put(h_slot8, slot8, n) : FG_OK;
     }
-    // the mirror goes out, and the n slots are decoded from d_src (ctx->d_offsets; ctx->d_bad nonzero -> FG_ST_BAD_UTF8, not decoded)
-    int finish(uint64_t n, int path, fg_format fmt, fg_framing framing, uint64_t used_bytes, const uint8_t* d_src) {
-        publish(n);
-        ctx->last_host_path = path;
-        if (n == 0) {
+    // the mirror goes out, and the slots are decoded into host tables
+    int finish(const SegFramed& f, fg_format fmt) {
+        publish(f.n);
+        ctx->last_host_path = f.path;
+        if (f.n == 0) {
             FG_HIP(ctx, hipStreamSynchronize(s));  // (the mirror's copies)
             return FG_OK;
         }
-        const int rc = decode_stage_to_host(ctx, fmt, framing, used_bytes, n, ctx->d_bad, d_src, out);
+        const int rc = decode_stage_to_host(ctx, fmt, f.framing, f.used, f.n, ctx->d_bad, f.d_src, out);
+        if (rc != FG_OK) ctx->last_host_path = 0;
+        return rc;
+    }
+    // ... or decoded into HBM and encoded from there: *res = the stream and the verdicts in ctx->h_tout, complete when the call returns
+    // (in_bytes: the buffer's size, from which the first output buffer of a ctx is sized)
+    int finish_transcode(const SegFramed& f, fg_format fmt, const fg_encode_cfg* ecfg, uint64_t in_bytes, fg_transcoded* res) {
+        publish(f.n);
+        ctx->last_host_path = f.path;
+        *res = fg_transcoded{};
+        res->n = f.n;
+        int rc;
+        if (f.n == 0) {  // an empty stream: out_offsets[0] = 0
+            if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, 0, 0, false, res))) == FG_OK) {
+                transcoded_arrays(ctx->h_tout, 0, 0, false, res);
+                *reinterpret_cast<uint64_t*>(ctx->h_tout) = 0;
+                res->out = ctx->h_tout;
+            }
+        } else {
+            rc = transcode_tail(ctx, fmt, f.framing, ecfg, f.d_src, f.used, f.n, ctx->d_bad, in_bytes, false, res);
+        }
+        if (rc == FG_OK) {
+            const hipError_t e = hipStreamSynchronize(s);  // (the mirror's copies, the tail's downloads)
+            if (e != hipSuccess) {
+                ctx->last_hip = (int)e;
+                rc = FG_ERR_HIP;
+            }
+        }
         if (rc != FG_OK) ctx->last_host_path = 0;
         return rc;
     }
@@ -1182,15 +1224,14 @@ struct SegBatch {
 static bool text_format(fg_format fmt) { return fmt == FG_RFC5424 || fmt == FG_LTSV || fmt == FG_GELF || fmt == FG_RFC3164; }
 
 // Lines / NUL: CARRY and BAD_UTF8 slots are skipped rows; the slots are decoded where they lie (terminators stripped in-kernel).
-extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
-                                           const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs, fg_tables* out,
-                                           const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
-                                           const uint64_t** out_seg_consumed, uint64_t* n_slots) {
-    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !n_slots || (nbytes && !bytes)) return FG_ERR_ARG;
+static int lines_multi_args(fg_format fmt, fg_framing framing, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs) {
     if ((framing != FG_FRAME_LINE && framing != FG_FRAME_NUL) || !text_format(fmt)) return FG_ERR_ARG;
-    if (!SegBatch::list_ok(seg_starts, n_segs, nbytes, 0)) return FG_ERR_ARG;
-    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, nullptr, out_offsets, out_kind};
-    DeviceGuard g(ctx->device);
+    return SegBatch::list_ok(seg_starts, n_segs, nbytes, 0) ? FG_OK : FG_ERR_ARG;
+}
+static int lines_multi_front(SegBatch& b, fg_framing framing, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, const uint8_t* seg_final,
+                             SegFramed* f) {
+    fg_ctx* const ctx = b.ctx;
+    const uint64_t n_segs = b.n_segs;
     int rc;
     if ((rc = b.upload(bytes, nbytes, seg_starts, seg_final)) != FG_OK) return rc;
     // capacity: one slot per 32 bytes and one tail per segment to start with (as frame_stage)
@@ -1205,21 +1246,46 @@ extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framin
     if (rc != FG_OK) return rc;
     // (an empty buffer: the device entry leaves the offsets alone)
     if ((rc = b.mirror(n, nbytes && n_segs ? n + 1 : 0, b.d_first, b.d_cons, nullptr, ctx->d_offsets, ctx->d_bad, true)) != FG_OK) return rc;
-    return b.finish(n, FG_PATH_FRAME_MULTI, fmt, framing, nbytes, ctx->d_bytes);
+    *f = SegFramed{n, nbytes, ctx->d_bytes, framing, FG_PATH_FRAME_MULTI};
+    return FG_OK;
+}
+extern "C" int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
+                                           const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs, fg_tables* out,
+                                           const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
+                                           const uint64_t** out_seg_consumed, uint64_t* n_slots) {
+    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !n_slots || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (lines_multi_args(fmt, framing, nbytes, seg_starts, n_segs) != FG_OK) return FG_ERR_ARG;
+    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, nullptr, out_offsets, out_kind};
+    DeviceGuard g(ctx->device);
+    SegFramed f;
+    const int rc = lines_multi_front(b, framing, bytes, nbytes, seg_starts, seg_final, &f);
+    return rc != FG_OK ? rc : b.finish(f, fmt);
 }
 
 // OCTET-COUNTED chunks (a SyslenSplitter per connection, syslen_splitter.rs:42-57): framed AND packed on the device; what is decoded is the
 // packed batch (FG_FRAME_NONE, with the UTF-8 flags).  When the device framer declines (fg_frame_syslen_multi_device: FG_ERR_UNSUPPORTED)
 // or a segment meets a prefix beyond the device parser's bound, the whole buffer is hopped on the host, segment by segment, and the
 // packed batch is uploaded: the same results either way (the two simplifications of syslen_stage hold here too).
-extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
-                                                  uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts,
-                                                  const uint64_t** out_seg_first, const uint64_t** out_seg_consumed,
-                                                  const uint8_t** out_seg_stop, uint64_t* n_frames) {
-    if (!ctx || !out || !out_frame_starts || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_frames || (nbytes && !bytes)) return FG_ERR_ARG;
-    if (!text_format(fmt) || !SegBatch::list_ok(seg_starts, n_segs, nbytes, 0)) return FG_ERR_ARG;
-    SegBatch b{ctx, n_segs, out, n_frames, out_seg_first, out_seg_consumed, out_seg_stop, out_frame_starts, nullptr};
-    DeviceGuard g(ctx->device);
+// THE CUT (fg_transcode_multi_batch, whose mirror has the byte per slot; the decode entry flags every bad payload and leaves the rest to
+// its caller): SyslenSplitter::run unwraps String::from_utf8 (syslen_splitter.rs:33), so a segment's first payload that is not UTF-8 ends
+// its connection -- it stays FG_SLOT_BAD_UTF8 and every frame of the segment behind it becomes FG_SLOT_UNREACHED, a skipped row like it.
+// On the device between the framer and the mirror (fg_launch_syslen_cut), on the host in the hop.
+static void syslen_cut_host(uint8_t* bad, const uint64_t* first, uint64_t n_segs) {
+    for (uint64_t k = 0; k < n_segs; ++k) {
+        bool over = false;
+        for (uint64_t i = first[k]; i < first[k + 1]; ++i) {
+            if (over) bad[i] = FG_SLOT_UNREACHED;
+            else over = bad[i] != 0;
+        }
+    }
+}
+static int syslen_multi_args(fg_format fmt, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs) {
+    return text_format(fmt) && SegBatch::list_ok(seg_starts, n_segs, nbytes, 0) ? FG_OK : FG_ERR_ARG;
+}
+static int syslen_multi_front(SegBatch& b, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, SegFramed* f) {
+    fg_ctx* const ctx = b.ctx;
+    const uint64_t n_segs = b.n_segs;
+    const bool cut = b.o_slot8 != nullptr;
     hipStream_t s = ctx->stream;
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
@@ -1240,11 +1306,17 @@ extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, co
     if (rc != FG_OK && rc != FG_ERR_UNSUPPORTED) return rc;
     bool device = rc == FG_OK;
     if (device) {
-        if ((rc = b.mirror(n, n, b.d_first, b.d_cons, b.d_seg8, ctx->d_sl_starts, nullptr, true)) != FG_OK) return rc;
+        const bool cut_here = cut && fg_launch_syslen_cut;  // (on the ctx's stream, in front of the mirror's copy of the verdicts)
+        if (cut_here) FG_LAUNCH(ctx, fg_launch_syslen_cut(ctx->d_bad, n, b.d_first, n_segs, b.d_cut, s));
+        if ((rc = b.mirror(n, n, b.d_first, b.d_cons, b.d_seg8, ctx->d_sl_starts, cut ? ctx->d_bad : nullptr, true)) != FG_OK) return rc;
         // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
         FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + payload, 0, up(payload, 16) + 16 - payload, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         for (uint64_t k = 0; k < n_segs && device; ++k) device = b.h_stop[k] != FG_SYSLEN_LONG_PREFIX;
+        if (device && cut && !cut_here && n) {  // a build without the kernel: from the mirrored verdicts, and back (pinned: may stay in flight)
+            syslen_cut_host(b.h_slot8, b.h_first, n_segs);
+            FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, b.h_slot8, n, hipMemcpyHostToDevice, s));
+        }
     }
     if (!device) {
         SyslenHop hop;
@@ -1256,28 +1328,39 @@ extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, co
         }
         n = hop.starts.size();
         payload = hop.packed.size();
+        if (cut) syslen_cut_host(hop.bad.data(), first.data(), n_segs);  // (before the verdicts are mirrored and uploaded)
         if ((rc = ensure(n)) != FG_OK) return rc;
-        if ((rc = b.mirror(n, n, first.data(), cons.data(), stop.data(), hop.starts.data(), nullptr, false)) != FG_OK) return rc;
+        if ((rc = b.mirror(n, n, first.data(), cons.data(), stop.data(), hop.starts.data(), cut ? hop.bad.data() : nullptr, false)) != FG_OK) return rc;
         if ((rc = hop.upload(ctx, s)) != FG_OK) return rc;
         FG_HIP(ctx, hipStreamSynchronize(s));  // (the vectors go out of scope)
     }
     if (n && nbytes >= (1u << 20)) ctx->frames_per_byte = (double)n / (double)nbytes;
-    return b.finish(n, device ? FG_PATH_FRAME_SYSLEN_MULTI_DEVICE : FG_PATH_FRAME_SYSLEN_MULTI_HOST, fmt, FG_FRAME_NONE, payload, ctx->d_sl_packed);
+    *f = SegFramed{n, payload, ctx->d_sl_packed, FG_FRAME_NONE, device ? FG_PATH_FRAME_SYSLEN_MULTI_DEVICE : FG_PATH_FRAME_SYSLEN_MULTI_HOST};
+    return FG_OK;
+}
+extern "C" int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
+                                                  uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts,
+                                                  const uint64_t** out_seg_first, const uint64_t** out_seg_consumed,
+                                                  const uint8_t** out_seg_stop, uint64_t* n_frames) {
+    if (!ctx || !out || !out_frame_starts || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_frames || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (syslen_multi_args(fmt, nbytes, seg_starts, n_segs) != FG_OK) return FG_ERR_ARG;
+    SegBatch b{ctx, n_segs, out, n_frames, out_seg_first, out_seg_consumed, out_seg_stop, out_frame_starts, nullptr};
+    DeviceGuard g(ctx->device);
+    SegFramed f;
+    const int rc = syslen_multi_front(b, bytes, nbytes, seg_starts, &f);
+    return rc != FG_OK ? rc : b.finish(f, fmt);
 }
 
 // CAP'N PROTO chunks (a CapnpSplitter per connection, capnp_splitter.rs:24-46): the messages are decoded where they lie, with the slot
 // kinds as the skip array (a CARRY slot is a skipped row).  When the device framer declines (fg_frame_capnp_multi_device:
 // FG_ERR_UNSUPPORTED) the segments are walked on the host over the caller's bytes and the slots are uploaded: the same results either way.
-extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
-                                                 fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
-                                                 const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop,
-                                                 uint64_t* n_slots) {
-    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_slots || (nbytes && !bytes))
-        return FG_ERR_ARG;
+static int capnp_multi_args(uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs) {
     if (!SegBatch::list_ok(seg_starts, n_segs, nbytes, 7)) return FG_ERR_ARG;  // (the framer works on words of the buffer)
-    if (nbytes > FG_CAPNP_FRAME_MAX_BYTES || n_segs > (1ull << 24)) return FG_ERR_ARG;
-    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, out_seg_stop, out_offsets, out_kind};
-    DeviceGuard g(ctx->device);
+    return nbytes > FG_CAPNP_FRAME_MAX_BYTES || n_segs > (1ull << 24) ? FG_ERR_ARG : FG_OK;
+}
+static int capnp_multi_front(SegBatch& b, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, SegFramed* f) {
+    fg_ctx* const ctx = b.ctx;
+    const uint64_t n_segs = b.n_segs;
     hipStream_t s = ctx->stream;
     int rc;
     if ((rc = b.upload(bytes, nbytes, seg_starts, nullptr)) != FG_OK) return rc;
@@ -1294,7 +1377,8 @@ extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* byt
     });
     if (rc == FG_OK) {
         if ((rc = b.mirror(n, n + 1, b.d_first, b.d_cons, b.d_seg8, ctx->d_offsets, ctx->d_bad, true)) != FG_OK) return rc;
-        return b.finish(n, FG_PATH_FRAME_CAPNP_MULTI_DEVICE, FG_CAPNP, FG_FRAME_NONE, nbytes, ctx->d_bytes);
+        *f = SegFramed{n, nbytes, ctx->d_bytes, FG_FRAME_NONE, FG_PATH_FRAME_CAPNP_MULTI_DEVICE};
+        return FG_OK;
     }
     if (rc != FG_ERR_UNSUPPORTED) return rc;
     std::vector<uint64_t> offs, first{0}, cons(n_segs);
@@ -1316,7 +1400,21 @@ extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* byt
     // (from the pinned mirror: the vectors may go out of scope while these are in flight)
     FG_HIP(ctx, hipMemcpyAsync(ctx->d_offsets, b.h_slot64, (n + 1) * 8, hipMemcpyHostToDevice, s));
     if (n) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bad, b.h_slot8, n, hipMemcpyHostToDevice, s));
-    return b.finish(n, FG_PATH_FRAME_CAPNP_MULTI_HOST, FG_CAPNP, FG_FRAME_NONE, nbytes, ctx->d_bytes);
+    *f = SegFramed{n, nbytes, ctx->d_bytes, FG_FRAME_NONE, FG_PATH_FRAME_CAPNP_MULTI_HOST};
+    return FG_OK;
+}
+extern "C" int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
+                                                 fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
+                                                 const uint64_t** out_seg_first, const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop,
+                                                 uint64_t* n_slots) {
+    if (!ctx || !out || !out_offsets || !out_kind || !out_seg_first || !out_seg_consumed || !out_seg_stop || !n_slots || (nbytes && !bytes))
+        return FG_ERR_ARG;
+    if (capnp_multi_args(nbytes, seg_starts, n_segs) != FG_OK) return FG_ERR_ARG;
+    SegBatch b{ctx, n_segs, out, n_slots, out_seg_first, out_seg_consumed, out_seg_stop, out_offsets, out_kind};
+    DeviceGuard g(ctx->device);
+    SegFramed f;
+    const int rc = capnp_multi_front(b, bytes, nbytes, seg_starts, &f);
+    return rc != FG_OK ? rc : b.finish(f, FG_CAPNP);
 }
 
 // The fixed arrays of an fg_transcoded -- out_offsets | meta | enc_status [| frame offsets] -- from byte `base` of the pinned block h:
@@ -1494,6 +1592,48 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     return FG_OK;
 }
 
+// Steps 2 - 4 of a one-piece transcode, shared by fg_transcode_batch and fg_transcode_multi_batch -- nothing here depends on where the
+// frames came from: the n frames ctx->d_offsets names in d_src[0 .. src_bytes) (d_bad nonzero: a skipped row) are decoded into tables
+// that stay in HBM, encoded + framed from them (the output buffer grows to the batch: steady state is one count + one write; sized from
+// in_bytes the first time), and the stream and the per-line verdicts are downloaded into ctx->h_tout: the messages, the fixed arrays
+// behind them (`frames`: with room for frame offsets, which the caller fills).  *res gets the pointers and out_bytes; the downloads
+// are queued on the ctx's stream and NOT waited for.
+static int transcode_tail(fg_ctx* ctx, fg_format fmt, fg_framing dec_framing, const fg_encode_cfg* ecfg, const uint8_t* d_src, uint64_t src_bytes,
+                          uint64_t n, const uint8_t* d_bad, uint64_t in_bytes, bool frames, fg_transcoded* res) {
+    hipStream_t s = ctx->stream;
+    int rc;
+    // 2. decode (tables stay in HBM)
+    fg_tables dt{};
+    uint64_t ent_used = 0;
+    if ((rc = decode_stage(ctx, fmt, dec_framing, src_bytes, n, d_bad, &dt, &ent_used, d_src)) != FG_OK) return rc;
+    // 3. encode + frame from the tables
+    const uint64_t offs_bytes = up((n + 1) * 8, 256);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_tmeta, &ctx->d_tmeta_cap, offs_bytes + up(n, 256))) != FG_OK) return rc;
+    uint64_t* d_out_offsets = reinterpret_cast<uint64_t*>(ctx->d_tmeta);
+    uint8_t* d_enc_status = ctx->d_tmeta + offs_bytes;
+    if (!ctx->d_tout && (rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, in_bytes + in_bytes / 2 + 4096)) != FG_OK) return rc;
+    uint64_t total = 0;
+    rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
+                          d_enc_status, &total, FG_STREAM_OWN);
+    if (rc == FG_ERR_ENT_OVERFLOW) {
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, total + 4096)) != FG_OK) return rc;
+        rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
+                              d_enc_status, &total, FG_STREAM_OWN);
+    }
+    if (rc != FG_OK) return rc;
+    // 4. the messages, the fixed arrays behind them
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, up(total, 256), n, frames, res))) != FG_OK) return rc;
+    uint8_t* h = ctx->h_tout;
+    transcoded_arrays(h, up(total, 256), n, frames, res);
+    if (total) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res->out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res->meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync((void*)res->enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s));
+    res->out = h;
+    res->out_bytes = total;
+    return FG_OK;
+}
+
 int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* ecfg, const uint8_t* bytes,
                        uint64_t nbytes, const uint64_t* offsets, uint64_t n, int final, fg_transcoded* out) {
     if (!ctx || !ecfg || !out || (nbytes && !bytes)) return FG_ERR_ARG;
@@ -1553,45 +1693,55 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
         FG_HIP(ctx, hipStreamSynchronize(s));
         return FG_OK;
     }
-    // 2. decode (tables stay in HBM)
-    fg_tables dt{};
-    uint64_t ent_used = 0;
     if (!syslen) {
         d_src = ctx->d_bytes;
         src_bytes = consumed;
     }
-    if ((rc = decode_stage(ctx, fmt, dec_framing, src_bytes, n, d_bad, &dt, &ent_used, d_src)) != FG_OK) return rc;
-    // 3. encode + frame from the tables; the output buffer grows to the batch (steady state: one count + one write)
-    const uint64_t offs_bytes = up((n + 1) * 8, 256);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_tmeta, &ctx->d_tmeta_cap, offs_bytes + up(n, 256))) != FG_OK) return rc;
-    uint64_t* d_out_offsets = reinterpret_cast<uint64_t*>(ctx->d_tmeta);
-    uint8_t* d_enc_status = ctx->d_tmeta + offs_bytes;
-    if (!ctx->d_tout && (rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, consumed + consumed / 2 + 4096)) != FG_OK) return rc;
-    uint64_t total = 0;
-    rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
-                          d_enc_status, &total, FG_STREAM_OWN);
-    if (rc == FG_ERR_ENT_OVERFLOW) {
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_tout, &ctx->d_tout_cap, total + 4096)) != FG_OK) return rc;
-        rc = fg_encode_device(ctx, fmt, ecfg, d_src, src_bytes, ctx->d_offsets, n, &dt, ctx->d_tout, ctx->d_tout_cap, d_out_offsets,
-                              d_enc_status, &total, FG_STREAM_OWN);
-    }
-    if (rc != FG_OK) return rc;
-    // 4. only the encoded stream and the per-line verdicts cross PCIe back: the messages, the fixed arrays behind them
+    // 2. - 4. decode, encode, and only the encoded stream and the per-line verdicts cross PCIe back
     const bool frames = framing != FG_FRAME_NONE;
     fg_transcoded res = *out;  // (n and consumed)
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, up(total, 256), n, frames, &res))) != FG_OK) return rc;
-    uint8_t* h = ctx->h_tout;
-    transcoded_arrays(h, up(total, 256), n, frames, &res);
-    if (total) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync((void*)res.out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync((void*)res.meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync((void*)res.enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s));
+    if ((rc = transcode_tail(ctx, fmt, dec_framing, ecfg, d_src, src_bytes, n, d_bad, consumed, frames, &res)) != FG_OK) return rc;
     if (syslen) memcpy((void*)res.frame_offsets, ctx->h_off, (n + 1) * 8);  // (the frame starts in the caller's chunk, prefix included)
     else if (frames) FG_HIP(ctx, hipMemcpyAsync((void*)res.frame_offsets, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
-    res.out = h;
-    res.out_bytes = total;
     *out = res;
+    return FG_OK;
+}
+
+// fg_transcode_batch for the chunks of MANY connections: the front half of the matching fg_frame_decode_*multi_batch entry (upload,
+// segmented framing, the mirror of the per-segment and per-slot lists -- with the per-segment cut for octet-counted input), then the
+// transcode tail over every slot.  One piece, as those entries.
+int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* ecfg, const uint8_t* bytes, uint64_t nbytes,
+                             const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs, fg_transcoded_multi* out) {
+    if (!ctx || !ecfg || !out || (nbytes && !bytes)) return FG_ERR_ARG;
+    const bool lines = framing == FG_FRAME_LINE || framing == FG_FRAME_NUL, syslen = framing == FG_FRAME_SYSLEN, capnp = framing == FG_FRAME_CAPNP;
+    if (!lines && !syslen && !capnp) return FG_ERR_ARG;        // (FG_FRAME_NONE: a packed batch has no segments -- fg_transcode_batch)
+    if ((fmt == FG_CAPNP) != capnp) return FG_ERR_ARG;         // (a capnp stream has its own framing, and nothing else has it)
+    if (!lines && seg_final) return FG_ERR_ARG;
+    if ((lines ? lines_multi_args(fmt, framing, nbytes, seg_starts, n_segs)
+               : syslen ? syslen_multi_args(fmt, nbytes, seg_starts, n_segs) : capnp_multi_args(nbytes, seg_starts, n_segs)) != FG_OK)
+        return FG_ERR_ARG;
+    *out = fg_transcoded_multi{};
+    fg_tables none{};  // (SegBatch::upload clears the decode entries' tables)
+    SegBatch b{ctx, n_segs, &none, &out->n, &out->seg_first, &out->seg_consumed, lines ? nullptr : &out->seg_stop, &out->slot_offsets, &out->slot_kind};
+    DeviceGuard g(ctx->device);
+    DrainGuard drained(ctx);  // (every exit from here on waits for what it queued)
+    SegFramed f;
+    fg_transcoded res{};
+    int rc = lines ? lines_multi_front(b, framing, bytes, nbytes, seg_starts, seg_final, &f)
+                   : syslen ? syslen_multi_front(b, bytes, nbytes, seg_starts, &f) : capnp_multi_front(b, bytes, nbytes, seg_starts, &f);
+    if (rc == FG_OK) rc = b.finish_transcode(f, fmt, ecfg, nbytes, &res);
+    if (rc == FG_OK) rc = drained.done();
+    if (rc != FG_OK) {
+        *out = fg_transcoded_multi{};
+        ctx->last_host_path = 0;
+        return rc;
+    }
+    out->out = res.out;
+    out->out_bytes = res.out_bytes;
+    out->out_offsets = res.out_offsets;
+    out->meta = res.meta;
+    out->enc_status = res.enc_status;
     return FG_OK;
 }
 

@@ -12,9 +12,15 @@
 //   k_slm_collect   one lane per node
 //   k_slm_scan      one wave over the segments
 //   k_slm_emit      one wave per tile, 3088 B of LDS (a strip of 64 frames)
+// and, for fg_transcode_multi_batch, the per-segment cut behind the first payload that is not UTF-8:
+//   k_slm_cut_find  one lane per frame, no LDS
+//   k_slm_cut_mark  one lane per frame, no LDS
 #include <hip/hip_runtime.h>
 
+#include "../../include/fg_hip.h"
 #include "fg_syslen_multi.hpp"
+
+static_assert(fg::syslen::kCutMark == FG_SLOT_UNREACHED, "the cut writes fg_slot_kind values");
 
 namespace fg {
 namespace syslen {
@@ -43,6 +49,16 @@ __global__ __launch_bounds__(64) void k_slm_emit(const uint8_t* __restrict__ byt
                                                  uint64_t* __restrict__ offsets, uint64_t* __restrict__ starts, uint8_t* __restrict__ bad, uint64_t cap) {
     __shared__ uint32_t lds[kEmitLdsWords];
     m_emit(bytes, blockIdx.x, sc, packed, offsets, starts, bad, cap, lds);
+}
+__global__ __launch_bounds__(64) void k_slm_cut_find(const uint8_t* __restrict__ bad, uint64_t n, const uint64_t* __restrict__ seg_first,
+                                                     uint64_t n_segs, uint32_t* __restrict__ cut) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (i < n) cut_find(bad, i, seg_first, n_segs, cut);
+}
+__global__ __launch_bounds__(64) void k_slm_cut_mark(uint8_t* __restrict__ bad, uint64_t n, const uint64_t* __restrict__ seg_first, uint64_t n_segs,
+                                                     const uint32_t* __restrict__ cut) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (i < n) cut_mark(bad, i, seg_first, n_segs, cut);
 }
 
 }  // namespace syslen
@@ -76,5 +92,19 @@ extern "C" int fg_launch_syslen_multi(const uint8_t* d_bytes, uint64_t nbytes, c
     hipLaunchKernelGGL(k_slm_scan, dim3(1), dim3(64), 0, stream, sc, cap, d_offsets, d_seg_first, d_seg_consumed, d_seg_stop);
     hipLaunchKernelGGL(k_slm_emit, dim3(sc.tiles), dim3(64), 0, stream, d_bytes, sc, d_packed, d_offsets, d_starts, d_bad, cap);
     *d_hdr_out = sc.hdr;
+    return (int)hipGetLastError();
+}
+
+extern "C" uint64_t fg_syslen_cut_scratch_bytes(uint64_t n_segs) { return fg::syslen::cut_words(n_segs) * 4u; }
+// Queues the cut on `stream`: d_bad[n] (0 / 1) and d_seg_first[n_segs + 1] as the framer above left them, d_cut =
+// fg_syslen_cut_scratch_bytes(n_segs) bytes.  Nothing to do without frames or segments.  -1: more frames than a 32-bit word numbers.
+extern "C" int fg_launch_syslen_cut(uint8_t* d_bad, uint64_t n, const uint64_t* d_seg_first, uint64_t n_segs, uint32_t* d_cut, hipStream_t stream) {
+    using namespace fg::syslen;
+    if (n == 0 || n_segs == 0) return 0;
+    if (n >= kCutNone || n_segs > kMaxSegs) return -1;
+    (void)hipMemsetAsync(d_cut, 0xFF, cut_words(n_segs) * 4u, stream);
+    const uint32_t groups = (uint32_t)((n + 63u) / 64u);
+    hipLaunchKernelGGL(k_slm_cut_find, dim3(groups), dim3(64), 0, stream, d_bad, n, d_seg_first, n_segs, d_cut);
+    hipLaunchKernelGGL(k_slm_cut_mark, dim3(groups), dim3(64), 0, stream, d_bad, n, d_seg_first, n_segs, d_cut);
     return (int)hipGetLastError();
 }

@@ -171,5 +171,37 @@ FG_WV void m_emit(const uint8_t* bytes, uint32_t tile, const MScratch& sc, uint8
         if (sg.c[k + 1u] > sg.c[k]) emit_chain(bytes, sg.c[k + 1u], end, sg.c[k], sc.sg_f[k], sc.sg_b[k], packed, offsets, starts, bad, cap, lds);
 }
 
+// ---- the per-segment CUT (fg_transcode_multi_batch) ---------------------------------------------------------------------------------
+// SyslenSplitter::run unwraps String::from_utf8 (syslen_splitter.rs:33): the first payload of a connection that is not valid UTF-8 ends
+// its thread, and no frame behind it is ever decoded.  bad[n] holds 0 / 1 per frame, seg_first[n_segs + 1] the first frame of every
+// segment (non-decreasing, seg_first[n_segs] = n); with c_k the first flagged frame of segment k, every frame of k behind c_k becomes
+// kCutMark.  Two passes, one lane per frame each, over cut[n_segs + 1] words that start as kCutNone: cut[k] = c_k, cut[n_segs] = the
+// first flagged frame of the whole batch.  A batch without a flagged payload -- the everyday case -- costs the first pass its read of
+// `bad` and the second one word per wave: no search runs.
+constexpr uint32_t kCutNone = 0xFFFFFFFFu;  // (also what bounds n: frame numbers are 32-bit words here)
+constexpr uint8_t kCutMark = 3u;            // FG_SLOT_UNREACHED (include/fg_hip.h; fg_syslen_multi.hip asserts it)
+FG_WVH uint64_t cut_words(uint64_t n_segs) { return n_segs + 1u; }
+#if defined(__HIPCC__)
+FG_WV void g_min32(uint32_t* p, uint32_t v) { atomicMin(p, v); }
+#else
+FG_WV void g_min32(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
+#endif
+// the segment that holds frame i < n: the last k with seg_first[k] <= i (empty segments are runs of equal values: the upper bound
+// steps over them)
+FG_WV uint64_t cut_segment(const uint64_t* seg_first, uint64_t n_segs, uint64_t i) {
+    return fmulti::upper_bound_u64(seg_first, 0, n_segs + 1u, i) - 1u;
+}
+// pass 1, frame i < n: the rare flagged lane finds its segment and reports its number
+FG_WV void cut_find(const uint8_t* bad, uint64_t i, const uint64_t* seg_first, uint64_t n_segs, uint32_t* cut) {
+    if (bad[i] == 0u) return;
+    g_min32(cut + cut_segment(seg_first, n_segs, i), (uint32_t)i);
+    g_min32(cut + n_segs, (uint32_t)i);
+}
+// pass 2 (a launch of its own: pass 1 has ended), frame i < n
+FG_WV void cut_mark(uint8_t* bad, uint64_t i, const uint64_t* seg_first, uint64_t n_segs, const uint32_t* cut) {
+    if (i <= cut[n_segs]) return;  // (nothing flagged: every lane of every wave leaves here; else the frames in front of the first one)
+    if (i > cut[cut_segment(seg_first, n_segs, i)]) bad[i] = kCutMark;
+}
+
 }  // namespace syslen
 }  // namespace fg

@@ -587,6 +587,22 @@ class _MultiSplitter:
         """the connection is over for good: it may not push, and closing it again means nothing"""
         return False
 
+    @staticmethod
+    def _trimmed(frame: bytes) -> str:
+        """str::trim of a frame: what the reference prints between the brackets of its stderr line"""
+        return frame.decode("utf-8").strip(_RUST_WS)
+
+    @staticmethod
+    def _unterminated(line: bytes, framing: int) -> bytes:
+        """a LINE / NUL slot without its terminator ("\n" or "\r\n": BufRead::lines; the NUL)"""
+        if framing == L.FG_FRAME_LINE:
+            return line[:-2] if line.endswith(b"\r\n") else line[:-1] if line.endswith(b"\n") else line
+        return line[:-1] if line.endswith(b"\0") else line
+
+    def _decode_error(self, r, frame: bytes) -> DecodeError:
+        """"<the decoder's or the encoder's error>: [<trimmed frame>]" (line_splitter.rs:37-39, syslen_splitter.rs:35-37)"""
+        return DecodeError(f"{r}: [{self._trimmed(frame)}]")
+
     def push(self, conn_id, chunk: bytes) -> list:
         """park a chunk; -> flush()'s result when the policy says the batch is due, else []"""
         import time
@@ -633,6 +649,26 @@ class _EndingSplitter(_MultiSplitter):
     def _ended(self, conn_id) -> bool:
         return conn_id in self._over
 
+    def _empty_message(self) -> list:
+        """what handling an empty octet-counted message yields"""
+        r = self.decoder.decode_batch([b""])[0]
+        return [self._decode_error(r, b"") if isinstance(r, DecodeError) else r]
+
+    def _eof(self, tail: bytes) -> list:
+        """what SyslenSplitter::run reports when the stream ends with `tail` behind the last whole frame (fg_decoder.hpp's Syslen
+        branch: read_until drops the last byte of a length that no ' ' follows)"""
+        sp = tail.find(b" ")
+        if sp >= 0:  # a whole prefix (a bad one ended the connection before): EOF inside its payload
+            return [DecodeError(SYSLEN_SHORT_READ)]
+        num = tail[:-1]
+        body = num[1:] if num[:1] == b"+" else num
+        if len(tail) <= 1 or not body or not body.isdigit() or int(body) >= 1 << 64:
+            return [DecodeError(SYSLEN_BAD_LENGTH)]
+        if int(body) != 0:
+            return [DecodeError(SYSLEN_SHORT_READ)]
+        # "0?" + EOF: an empty message is handled, then the next read_msglen sees Ok(0)
+        return self._empty_message() + [DecodeError(SYSLEN_BAD_LENGTH)]
+
 
 class MultiStreamSplitter(_MultiSplitter):
     """The stream-side sibling of the UDP batcher: parks the chunks of MANY connections and hands them to the GPU together -- one
@@ -673,15 +709,10 @@ class MultiStreamSplitter(_MultiSplitter):
                 else:
                     r = parse_canonical(can[int(coffs[i]):int(coffs[i + 1])])
                     if isinstance(r, DecodeError):
-                        line = raw[a:b]
-                        if self.framing == L.FG_FRAME_LINE:
-                            line = line[:-2] if line.endswith(b"\r\n") else line[:-1] if line.endswith(b"\n") else line
-                        elif line.endswith(b"\0"):
-                            line = line[:-1]
-                        text = line.decode("utf-8").strip(_RUST_WS)
-                        if self.framing == L.FG_FRAME_NUL and not text:
+                        line = self._unterminated(raw[a:b], self.framing)
+                        if self.framing == L.FG_FRAME_NUL and not self._trimmed(line):
                             continue
-                        r = DecodeError(f"{r}: [{text}]")
+                        r = self._decode_error(r, line)
                     res.append(r)
             out.append((c, res))
         return out
@@ -701,24 +732,6 @@ class MultiSyslenSplitter(_EndingSplitter):
     be read ends the connection with DecodeError("Can't read message's length"), the first payload that is not valid UTF-8 with the
     reference's panic text (its `unwrap()`): later pushes raise.  close(conn) is its EOF: "Can't read message's length" with nothing
     carried, else what the reference reports for an EOF inside a length or a payload."""
-
-    def _decode_error(self, r: DecodeError, payload: bytes) -> DecodeError:
-        return DecodeError(f"{r}: [{payload.decode('utf-8').strip(_RUST_WS)}]")
-
-    def _eof(self, tail: bytes) -> list:
-        """what SyslenSplitter::run reports when the stream ends with `tail` behind the last whole frame (fg_decoder.hpp's Syslen
-        branch: read_until drops the last byte of a length that no ' ' follows)"""
-        sp = tail.find(b" ")
-        if sp >= 0:  # a whole prefix (a bad one ended the connection before): EOF inside its payload
-            return [DecodeError(SYSLEN_SHORT_READ)]
-        num = tail[:-1]
-        body = num[1:] if num[:1] == b"+" else num
-        if len(tail) <= 1 or not body or not body.isdigit() or int(body) >= 1 << 64:
-            return [DecodeError(SYSLEN_BAD_LENGTH)]
-        if int(body) != 0:
-            return [DecodeError(SYSLEN_SHORT_READ)]
-        r = self.decoder.decode_batch([b""])[0]  # "0?" + EOF: an empty message is handled, then the next read_msglen sees Ok(0)
-        return [self._decode_error(r, b"") if isinstance(r, DecodeError) else r, DecodeError(SYSLEN_BAD_LENGTH)]
 
     def flush(self) -> list:
         """-> [(conn_id, [Record | DecodeError, ...]), ...] for every connection that had chunks parked or was closed, in arrival order"""
@@ -1006,6 +1019,112 @@ class CapnpTranscodingSplitter:
         if len(offsets) < 2:  # no whole message yet
             return Transcoded(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), None, 0)
         return self.pipeline.run_packed(data, offsets, now_ts=self.now_ts)
+
+
+class MultiTranscodingSplitter(_EndingSplitter):
+    """MultiStreamSplitter / MultiSyslenSplitter / MultiCapnpSplitter WITH the encoder: parks the chunks of many connections and hands
+    them to the GPU together -- one fg_transcode_multi_batch call frames every connection's bytes as its own stream, decodes the
+    frames, encodes the Records and frames them for the output; the tables never leave the device.  flush() returns the bytes for the
+    output -- what the connection threads of the reference would have sent for the bytes pushed so far, connection after connection in
+    arrival order -- and per connection what they would have printed to stderr: DecodeError("<the decoder's or the encoder's error>:
+    [<trimmed frame>]") per dropped frame (FG_FRAME_CAPNP: the error alone, capnp_splitter.rs:48-58), "Invalid UTF-8 input", and what
+    ends a connection, as the decode-side classes state it: carry-over, close() and the end of a connection are theirs."""
+
+    def __init__(self, decoder: Decoder, encoder, framing: int, policy: Optional[FlushPolicy] = None, now_ts: float = 0.0):
+        from .encoder import Pipeline
+
+        if framing not in (L.FG_FRAME_LINE, L.FG_FRAME_NUL, L.FG_FRAME_SYSLEN, L.FG_FRAME_CAPNP):
+            raise ValueError("MultiTranscodingSplitter frames FG_FRAME_LINE, FG_FRAME_NUL, FG_FRAME_SYSLEN or FG_FRAME_CAPNP streams")
+        if (framing == L.FG_FRAME_CAPNP) != (decoder.fmt == L.FG_CAPNP):
+            raise ValueError("FG_FRAME_CAPNP streams are what a CapnpDecoder reads, and nothing else is")
+        super().__init__(decoder, policy)
+        self.pipeline, self.framing, self.now_ts = Pipeline(decoder, encoder), framing, now_ts
+        self._extra = b""
+
+    def _empty_message(self) -> list:
+        """an empty octet-counted message in front of an EOF goes through the pipeline like any other: its bytes to the output, or
+        its error"""
+        t = self.pipeline.run_packed(np.zeros(16, np.uint8), np.zeros(2, np.uint64), now_ts=self.now_ts)
+        if t.enc_status[0] == 0:
+            self._extra = t.out.tobytes()
+            return []
+        return [self._decode_error(self._error(t, 0), b"")]
+
+    def _error(self, t, i: int) -> str:
+        from .encoder import Encoder
+
+        st = int(t.dec_status[i])
+        return self.decoder.error_string(st) if st else Encoder.error_string(int(t.enc_status[i]))
+
+    def flush(self):
+        """-> (bytes for the output, [(conn_id, [DecodeError | CapnpStreamError, ...]), ...] for every connection that had chunks parked
+        or was closed, in arrival order)"""
+        lines, syslen, capnp = self.framing in (L.FG_FRAME_LINE, L.FG_FRAME_NUL), self.framing == L.FG_FRAME_SYSLEN, self.framing == L.FG_FRAME_CAPNP
+        # (a Cap'n Proto segment starts on a word of the buffer: the last len % 8 bytes can never complete a message and stay here)
+        conns, segs, raw, starts = self._take(align=8 if capnp else 1)
+        if not conns:
+            return b"", []
+        final = [1 if c in self._closed else 0 for c in conns] if lines else None  # (close(conn): its unterminated tail is a frame)
+        t = self.pipeline.run_multi(raw, starts, final, self.framing, now_ts=self.now_ts)
+        so, pieces, out = t.slot_offsets, [], []
+        for k, c in enumerate(conns):
+            a, b = int(t.seg_first[k]), int(t.seg_first[k + 1])
+            pieces.append(t.out[int(t.out_offsets[a]):int(t.out_offsets[b])].tobytes())
+            res: list = []
+            over = False
+            for i in range(a, b):
+                kind = t.slot_kind[i]
+                if kind == L.FG_SLOT_CARRY:
+                    if lines:
+                        self._carry[c] = raw[int(so[i]):int(so[i + 1])]
+                elif kind == L.FG_SLOT_BAD_UTF8 and syslen:  # the reference's unwrap(): this connection's thread ends here
+                    res.append(DecodeError(SYSLEN_PANIC))
+                    over = True
+                    break
+                elif kind == L.FG_SLOT_BAD_UTF8:
+                    res.append(DecodeError("Invalid UTF-8 input"))
+                elif t.enc_status[i] != 0:
+                    if capnp:
+                        res.append(DecodeError(self._error(t, i)))
+                        continue
+                    if syslen:
+                        sp = raw.index(b" ", int(so[i]))
+                        frame = raw[sp + 1:sp + 1 + int(raw[int(so[i]):sp])]
+                    else:
+                        frame = self._unterminated(raw[int(so[i]):int(so[i + 1])], self.framing)
+                    if self.framing == L.FG_FRAME_NUL and not self._trimmed(frame):
+                        continue
+                    res.append(self._decode_error(self._error(t, i), frame))
+            if lines:  # (a closed connection is forgotten: MultiStreamSplitter)
+                self._closed.discard(c)
+                out.append((c, res))
+                continue
+            tail = segs[k][int(t.seg_consumed[k]):]
+            if capnp:
+                over = c in self._closed
+                if t.seg_stop[k] in (L.FG_CAPNP_TOO_MANY_SEGMENTS, L.FG_CAPNP_TOO_LARGE):
+                    try:
+                        CapnpFramer.frame(tail)  # (the text of the error: the few words of the table at `consumed`)
+                        raise AssertionError("the framer stopped at a table the host walk accepts")
+                    except CapnpStreamError as e:
+                        res.append(e)
+                    over = True
+            else:
+                if not over and t.seg_stop[k] == L.FG_SYSLEN_BAD_LEN:
+                    res.append(DecodeError(SYSLEN_BAD_LENGTH))
+                    over = True
+                if not over and c in self._closed:
+                    res += self._eof(tail) if tail else [DecodeError(SYSLEN_BAD_LENGTH)]
+                    pieces.append(self._extra)
+                    self._extra = b""
+                    over = True
+            self._closed.discard(c)
+            if over:
+                self._over.add(c)
+            elif tail:
+                self._carry[c] = tail
+            out.append((c, res))
+        return b"".join(pieces), out
 
 
 class RFC3164Decoder(Decoder):

@@ -143,6 +143,17 @@ class Transcoded:
         return self.out[int(self.out_offsets[i]):int(self.out_offsets[i + 1])].tobytes()
 
 
+class TranscodedMulti(Transcoded):
+    """Result of Pipeline.run_multi: Transcoded (one verdict per SLOT, no frame_offsets / consumed) plus the lists of the segmented
+    framers -- slot_offsets (LINE / NUL / CAPNP: n + 1 slot bounds in the buffer; SYSLEN: n frame starts, prefix included), slot_kind
+    (FG_SLOT_*), seg_first [K + 1], seg_consumed [K], seg_stop [K] (FG_SYSLEN_* / FG_CAPNP_*; None for LINE / NUL)."""
+
+    def __init__(self, out, out_offsets, meta, enc_status, slot_offsets, slot_kind, seg_first, seg_consumed, seg_stop):
+        super().__init__(out, out_offsets, meta, enc_status, None, None)
+        self.slot_offsets, self.slot_kind = slot_offsets, slot_kind
+        self.seg_first, self.seg_consumed, self.seg_stop = seg_first, seg_consumed, seg_stop
+
+
 class Pipeline:
     """decoder -> encoder -> merger for whole batches with HOST buffers (fg_transcode_batch): what
     ``handle_line`` (splitter/line_splitter.rs:44-54) does per line.  Only the encoded bytes and the per-line
@@ -192,3 +203,35 @@ class Pipeline:
             data = np.zeros(1, np.uint8)
             return self._call(framing, data, 0, None, 0, final, now_ts)
         return self._call(framing, data, len(data), None, 0, final, now_ts)
+
+    def run_multi(self, raw, seg_starts, seg_final, framing: int, now_ts: float = 0.0) -> TranscodedMulti:
+        """fg_transcode_multi_batch: the chunks of K connections back to back (connection k = raw[seg_starts[k]:seg_starts[k + 1]]),
+        every one framed as a stream of its own ("\\n" / NUL with seg_final[k] != 0: its unterminated tail is a frame; FG_FRAME_SYSLEN;
+        FG_FRAME_CAPNP with a CapnpDecoder, starts on multiples of 8 -- seg_final must be None for both), decoded and encoded: `.out`
+        is what the K connection threads of the reference would have sent, in buffer order.  An octet-counted connection ends at its
+        first payload that is not UTF-8 (FG_SLOT_BAD_UTF8); its later frames are FG_SLOT_UNREACHED and produce nothing."""
+        import numpy as np
+
+        data = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
+        starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+        K = len(starts) - 1
+        final = None if seg_final is None else np.ascontiguousarray(seg_final, dtype=np.uint8)
+        cfg, _keep = self.encoder._cfg_struct(now_ts)
+        res = L.fg_transcoded_multi()
+        rc = L.lib().fg_transcode_multi_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data if data.size else None,
+                                              data.size, starts.ctypes.data, final.ctypes.data if final is not None and K else None, K,
+                                              C.byref(res))
+        L.check(rc, "fg_transcode_multi_batch")
+        m = int(res.n)
+
+        def view(ptr, count, dt):
+            if not count or not ptr:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        syslen = framing == L.FG_FRAME_SYSLEN
+        return TranscodedMulti(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, m + 1, np.uint64),
+                               view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
+                               view(res.slot_offsets, m if syslen else m + 1, np.uint64), view(res.slot_kind, m, np.uint8),
+                               view(res.seg_first, K + 1, np.uint64), view(res.seg_consumed, K, np.uint64),
+                               view(res.seg_stop, K, np.uint8) if res.seg_stop else None)

@@ -369,7 +369,13 @@ int fg_frame_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uin
  * With n_segs == 1 and seg_final[0] != 0 the slots, offsets and flags are those of fg_frame_device on the same bytes.
  * Returns FG_ERR_ENT_OVERFLOW when cap_slots is too small (*n_slots holds the need; nothing beyond the capacity is written and the
  * per-segment outputs are not).  Honours FG_LO_FRAME_CLASSIC. */
-typedef enum fg_slot_kind { FG_SLOT_FRAME = 0, FG_SLOT_BAD_UTF8 = 1, FG_SLOT_CARRY = 2 } fg_slot_kind;
+typedef enum fg_slot_kind {
+    FG_SLOT_FRAME = 0,
+    FG_SLOT_BAD_UTF8 = 1,
+    FG_SLOT_CARRY = 2,
+    FG_SLOT_UNREACHED = 3 /* fg_transcode_multi_batch, FG_FRAME_SYSLEN only: a frame behind its segment's first FG_SLOT_BAD_UTF8 frame, which the
+                             reference's connection thread never reads (additive under the same FG_ABI_VERSION) */
+} fg_slot_kind;
 int fg_frame_multi_device(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
                           const uint64_t* d_seg_starts, const uint8_t* d_seg_final, uint64_t n_segs,
                           uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap_slots,
@@ -606,7 +612,7 @@ int fg_frame_decode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const 
  *   out_seg_first     n_segs + 1 entries;    out_seg_consumed: n_segs entries
  * Everything returned is ctx-owned and stays valid until the next call on this ctx.  fg_last_host_path says FG_PATH_FRAME_MULTI.
  * From which chunk size on a call per connection is as good has not been measured yet (tools/probe/multi_stream.py is the probe).
- * Out of scope here: slicing over streams, the zero-copy fused launch, fg_transcode_batch for segmented input. */
+ * Out of scope here: slicing over streams, the zero-copy fused launch. */
 int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* bytes, uint64_t nbytes,
                                 const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs,
                                 fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind,
@@ -624,7 +630,7 @@ int fg_frame_decode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, 
  * When the device framer declines, or any segment stops with FG_SYSLEN_LONG_PREFIX, the whole buffer is hopped on the host, segment by
  * segment, with prefixes of any length: the same results (and no LONG_PREFIX).  fg_last_host_path says
  * FG_PATH_FRAME_SYSLEN_MULTI_DEVICE or FG_PATH_FRAME_SYSLEN_MULTI_HOST.  Everything returned is ctx-owned and stays valid until the
- * next call on this ctx.  Out of scope here: slicing over streams, the fused launch, fg_transcode_batch for segmented input. */
+ * next call on this ctx.  Out of scope here: slicing over streams, the fused launch. */
 int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts,
                                        uint64_t n_segs, fg_tables* out, const uint64_t** out_frame_starts, const uint64_t** out_seg_first,
                                        const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop, uint64_t* n_frames);
@@ -639,7 +645,7 @@ int fg_frame_decode_syslen_multi_batch(fg_ctx* ctx, fg_format fmt, const uint8_t
  *   out_seg_first     n_segs + 1 entries;  out_seg_consumed: n_segs entries;  out_seg_stop: n_segs bytes (fg_capnp_stop)
  * When the device framer declines, every segment is walked on the host: the same results.  fg_last_host_path says
  * FG_PATH_FRAME_CAPNP_MULTI_DEVICE or FG_PATH_FRAME_CAPNP_MULTI_HOST.  Everything returned is ctx-owned and stays valid until the next
- * call on this ctx.  Out of scope here: slicing over streams, fg_transcode_batch for segmented input. */
+ * call on this ctx.  Out of scope here: slicing over streams. */
 int fg_frame_decode_capnp_multi_batch(fg_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const uint64_t* seg_starts, uint64_t n_segs,
                                       fg_tables* out, const uint64_t** out_offsets, const uint8_t** out_kind, const uint64_t** out_seg_first,
                                       const uint64_t** out_seg_consumed, const uint8_t** out_seg_stop, uint64_t* n_slots);
@@ -787,6 +793,43 @@ typedef struct fg_transcoded {
 } fg_transcoded;
 int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* cfg, const uint8_t* bytes,
                        uint64_t nbytes, const uint64_t* offsets, uint64_t n, int final, fg_transcoded* out);
+
+/* THE SAME FOR THE CHUNKS OF MANY CONNECTIONS IN ONE CALL (additive under the same FG_ABI_VERSION): what fg_frame_decode_multi_batch,
+ * fg_frame_decode_syslen_multi_batch and fg_frame_decode_capnp_multi_batch frame and decode -- K connections feeding one output,
+ * input/tcp/tcp_input.rs:39-47 -- is encoded and framed for the output too; the tables stay in HBM, and what returns is the stream the
+ * reference's K connection threads would have sent for these bytes, in buffer order, with one verdict per slot.
+ *   framing   FG_FRAME_LINE / FG_FRAME_NUL (fmt: a text format), FG_FRAME_SYSLEN (a text format), FG_FRAME_CAPNP (FG_CAPNP, and only
+ *             it); FG_FRAME_NONE is FG_ERR_ARG (a packed batch has no segments: fg_transcode_batch)
+ *   seg_final LINE / NUL only (may be NULL = all zero); must be NULL otherwise (FG_ERR_ARG)
+ * Argument rules, the tiling check of seg_starts and the size limits are those of the matching fg_frame_decode_*multi_batch, and so is
+ * the contract of segments, slots, kinds, seg_first, seg_consumed and seg_stop -- with one addition for FG_FRAME_SYSLEN: in every segment
+ * the first frame whose payload is not valid UTF-8 keeps FG_SLOT_BAD_UTF8 (the unwrap() of syslen_splitter.rs:33 that ends the
+ * connection's thread) and every later frame of that segment, valid or not, is FG_SLOT_UNREACHED; both are skipped rows (status
+ * FG_ST_BAD_UTF8, nothing encoded).  Other segments are not affected.
+ * Results (pinned host memory owned by ctx, valid until the next host-buffer call on it):
+ *   out / out_bytes / out_offsets[n + 1]   message i = out[out_offsets[i] .. out_offsets[i + 1]), empty when slot i produced nothing
+ *   meta[n], enc_status[n]                 as fg_transcoded
+ *   slot_offsets   LINE / NUL / CAPNP: n + 1 slot bounds in `bytes`; SYSLEN: n frame starts, "<len> " prefix included
+ *   slot_kind[n]   fg_slot_kind
+ *   seg_first[n_segs + 1], seg_consumed[n_segs], seg_stop[n_segs] (fg_syslen_stop / fg_capnp_stop; NULL for LINE / NUL)
+ * fg_last_host_path says which framing form ran (FG_PATH_FRAME_MULTI .. FG_PATH_FRAME_CAPNP_MULTI_HOST); fg_last_syslen_stop and
+ * fg_last_capnp_stop are not touched.  Out of scope here: slicing over streams, the fused launch, datagrams. */
+typedef struct fg_transcoded_multi {
+    const uint8_t* out;
+    uint64_t out_bytes;
+    const uint64_t* out_offsets;
+    const uint32_t* meta;
+    const uint8_t* enc_status;
+    const uint64_t* slot_offsets;
+    const uint8_t* slot_kind;
+    const uint64_t* seg_first;
+    const uint64_t* seg_consumed;
+    const uint8_t* seg_stop;
+    uint64_t n;
+} fg_transcoded_multi;
+int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* cfg, const uint8_t* bytes,
+                             uint64_t nbytes, const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs,
+                             fg_transcoded_multi* out);
 
 /* Host memory for the framer's batch buffers (bytes, offsets): PAGE-LOCKED, through a process-wide pool -- a freed block is kept
  * (up to idle_bytes in total) and handed to the next request it fits, so a framer per connection does not pin and unpin megabytes per

@@ -12,6 +12,12 @@ spaced ones beyond); then windows of at least --window seconds, the sides altern
 spread (min .. max) of lines/s end to end.  Framing alone: device time between two events around fg_frame_multi_device (K segments)
 and around fg_frame_device (the same bytes as one stream), both HBM-resident, median of 15 -- what the boundary handling costs.
 (fg_set_timing covers the decode launches only, so events around the calls stand in for it.)  One JSON line at the end.
+    --transcode  the same cells (--transcode-cells) through the encoder too (GELF + line merger), three sides alternated in one process:
+               T    ONE fg_transcode_multi_batch call on side B's pinned buffer
+               A-t  one fg_transcode_batch(final = 0) call per connection chunk on side A's pinned buffer
+               B    as above: the tables of ONE fg_frame_decode_multi_batch call cross the link
+               T's stream is asserted equal to A-t's streams back to back.  Per side: lines/s end to end, median and spread, and the
+               bytes that cross the link each way per batch, computed from the sizes the calls return.
     --syslen   octet-counted chunks instead ("<len> <line>\\n" frames, a connection's chunk ends inside a frame), HBM-resident: the time
                between two events around ONE fg_frame_syslen_multi_device call against K fg_frame_syslen_device calls on the same bytes
                (every chunk 16-byte aligned in a buffer of its own; each call synchronises, as it must to return its counts), for
@@ -135,6 +141,100 @@ class SideB:
         kind = np.ctypeslib.as_array(C.cast(v[1], C.POINTER(C.c_uint8)), (n,)).copy()
         first = np.ctypeslib.as_array(C.cast(v[2], u64p), (self.K + 1,)).copy()
         return HostTables.from_struct(st), offsets, kind, first
+
+
+class SideT:
+    """ONE fg_transcode_multi_batch call on side B's pinned buffer"""
+
+    def __init__(self, b: SideB, ecfg):
+        self.b, self.ecfg, self.res = b, ecfg, L.fg_transcoded_multi()
+
+    def run(self):
+        b = self.b
+        L.check(L.lib().fg_transcode_multi_batch(b.dec._ctx, b.dec.fmt, L.FG_FRAME_LINE, C.byref(self.ecfg), b.p, b.n, b.starts.ctypes.data, None, b.K,
+                                                 C.byref(self.res)), "fg_transcode_multi_batch")
+        return int(self.res.n) - b.K  # (every chunk ends in a CARRY slot)
+
+    def out(self):
+        self.run()
+        return np.ctypeslib.as_array(C.cast(self.res.out, C.POINTER(C.c_uint8)), (int(self.res.out_bytes),)).tobytes()
+
+    def link_bytes(self):
+        """(up, down) of one call, from what it returned: the buffer and the starts; the stream, its offsets, meta and enc_status, and
+        the mirror of the per-segment and per-slot lists"""
+        n, K = int(self.res.n), self.b.K
+        return self.b.n + (K + 1) * 8, int(self.res.out_bytes) + (n + 1) * 8 + 5 * n + (K + 1) * 8 + K * 8 + (n + 1) * 8 + n
+
+
+class SideAt:
+    """one fg_transcode_batch(FG_FRAME_LINE, final = 0) call per connection chunk on side A's pinned buffer"""
+
+    def __init__(self, a: SideA, ecfg):
+        self.a, self.ecfg, self.res = a, ecfg, L.fg_transcoded()
+        self.up = self.down = 0
+
+    def one(self, k):
+        a = self.a
+        L.check(L.lib().fg_transcode_batch(a.dec._ctx, a.dec.fmt, L.FG_FRAME_LINE, C.byref(self.ecfg), a.p.value + int(a.offs[k]), a.lens[k], None, 0, 0,
+                                           C.byref(self.res)), "fg_transcode_batch")
+        n = int(self.res.n)
+        self.up += a.lens[k]
+        self.down += int(self.res.out_bytes) + 2 * (n + 1) * 8 + 5 * n  # (the stream, out_offsets and frame_offsets, meta and enc_status)
+        return n
+
+    def run(self):
+        return sum(self.one(k) for k in range(len(self.a.lens)))
+
+    def out(self):
+        parts = []
+        for k in range(len(self.a.lens)):
+            self.one(k)
+            parts.append(np.ctypeslib.as_array(C.cast(self.res.out, C.POINTER(C.c_uint8)), (max(int(self.res.out_bytes), 1),))[:int(self.res.out_bytes)].tobytes())
+        return b"".join(parts)
+
+    def link_bytes(self):
+        self.up = self.down = 0
+        self.run()
+        return self.up, self.down
+
+
+def transcode_mode(dec, lines, cells, seconds, rounds):
+    """sides T, A-t and B alternated in one process; per side the bytes that cross the link each way, from the sizes the calls return"""
+    from flowgger_amd import GelfEncoder
+
+    ecfg, _keep = GelfEncoder(None, merger="line")._cfg_struct(0.0)
+    results = []
+    for K0, chunk in cells:
+        K = max(1, min(K0, CAP_TOTAL // chunk))
+        chunks, counts = build_cell(lines, K, chunk)
+        a, b = SideA(dec, chunks), SideB(dec, chunks)
+        t, at = SideT(b, ecfg), SideAt(a, ecfg)
+        assert t.out() == at.out(), "one call and a call per chunk: the streams differ"
+        assert t.run() == at.run() == b.run() == sum(counts)
+        tab = b.tables()[0]
+        nb = int(tab.n)
+        link = {"T": t.link_bytes(), "A-t": at.link_bytes(),
+                "B": (b.n + (K + 1) * 8, 68 * nb + 18 * int(tab.ent_used) + (K + 1) * 8 + K * 8 + (nb + 1) * 8 + nb)}
+        sides = {"T": t.run, "A-t": at.run, "B": b.run}
+        for fn in sides.values():  # warm-up: every shape the windows use
+            fn(), fn()
+        rates, per_call = {s: [] for s in sides}, {}
+        for _ in range(rounds):
+            for s, fn in sides.items():
+                r, dt = window(fn, seconds)
+                rates[s].append(r)
+                per_call[s] = dt
+        row = {"K": K, "K_asked": K0, "chunk": chunk, "bytes": sum(len(c) for c in chunks), "lines": sum(counts)}
+        for s in sides:
+            row[s] = {"lines_per_s": statistics.median(rates[s]), "min": min(rates[s]), "max": max(rates[s]), "ms_per_batch": per_call[s] * 1e3,
+                      "bytes_up": link[s][0], "bytes_down": link[s][1]}
+        results.append(row)
+        print(f"K={K:5d} chunk={chunk:8d} total={row['bytes'] / 2**20:7.1f} MiB  " +
+              "  ".join(f"{s} {row[s]['lines_per_s'] / 1e6:7.2f} M lines/s ({row[s]['min'] / 1e6:.2f}..{row[s]['max'] / 1e6:.2f}; {row[s]['ms_per_batch']:.2f} ms; "
+                        f"up {link[s][0] / 2**20:.2f} MiB, down {link[s][1] / 2**20:.2f} MiB)" for s in sides), flush=True)
+        L.lib().fg_free_pinned(a.p)
+        L.lib().fg_free_pinned(b.p)
+    print(json.dumps({"probe": "multi_stream_transcode", "window_s": seconds, "rounds": rounds, "cells": results}))
 
 
 def window(fn, seconds):
@@ -316,6 +416,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--cells", default=",".join(f"{k}:{c}" for k in (16, 256, 4096) for c in (4 << 10, 64 << 10, 1 << 20)))
     ap.add_argument("--lines", type=int, default=200_000)
+    ap.add_argument("--transcode", action="store_true")
+    ap.add_argument("--transcode-cells", default=",".join(f"{k}:{c}" for k in (16, 256, 4096) for c in (4 << 10, 64 << 10)))
     ap.add_argument("--syslen", action="store_true")
     ap.add_argument("--syslen-cells", default="64:131072,4096:2048")
     ap.add_argument("--syslen-one", type=int, default=8 << 20)
@@ -332,6 +434,9 @@ def main():
     if args.syslen:
         lines = [ln if isinstance(ln, bytes) else ln.encode() for ln in lines]
         syslen_mode(dec, lines, dev, [tuple(int(x) for x in c.split(":")) for c in args.syslen_cells.split(",")], args.syslen_one)
+        return
+    if args.transcode:
+        transcode_mode(dec, lines, [tuple(int(x) for x in c.split(":")) for c in args.transcode_cells.split(",")], args.window, args.rounds)
         return
     results = []
     for cell in args.cells.split(","):
