@@ -208,6 +208,10 @@ def lib() -> C.CDLL:
     L.fg_udp_error_string.restype = C.c_char_p
     L.fg_udp_unpack_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
     L.fg_udp_decode_batch.argtypes = [vp, C.c_int, vp, u64, vp, u64, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.fg_udp_unpack_once_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, vp, C.POINTER(u64), vp]
+    L.fg_udp_last_spilled.argtypes = [vp]
+    L.fg_udp_last_spilled.restype = u64
+    L.fg_udp_transcode_batch.argtypes = [vp, C.c_int, C.POINTER(fg_encode_cfg), vp, u64, vp, u64, u64, C.POINTER(fg_transcoded), C.POINTER(vp)]
     L.fg_frame_decode_device.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, vp, u64, C.POINTER(fg_tables), u64, vp, vp]
     L.fg_frame_multi_device.argtypes = [vp, C.c_int, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.fg_frame_decode_multi_batch.argtypes = [vp, C.c_int, C.c_int, vp, u64, vp, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp),

@@ -259,7 +259,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         if " fg_launch_frame_multi\n" not in syms:
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without fg_launch_frame_multi (fg_frame_multi.hip)")
-        if any(f" {f}" not in syms for f in ("fg_launch_udp_count", "fg_launch_udp_write", "fg_launch_udp_finish")):
+        if any(f" {f}" not in syms for f in ("fg_launch_udp_count", "fg_launch_udp_write", "fg_launch_udp_finish", "fg_launch_udp_stage", "fg_launch_udp_write_spilled",
+                                                  "fg_launch_udp_pack", "fg_udp_stage_bytes")):
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without the launchers of fg_udp.hip")
     if not PROF and not VARIANT:

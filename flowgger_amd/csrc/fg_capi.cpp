@@ -282,6 +282,7 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_sl_packed) (void)hipFree(ctx->d_sl_packed);
     if (ctx->d_sl_starts) (void)hipFree(ctx->d_sl_starts);
     if (ctx->d_udp) (void)hipFree(ctx->d_udp);
+    if (ctx->d_udp_stage) (void)hipFree(ctx->d_udp_stage);
     if (ctx->d_udp_off) (void)hipFree(ctx->d_udp_off);
     if (ctx->d_udp_st) (void)hipFree(ctx->d_udp_st);
     if (ctx->h_udp) (void)hipHostFree(ctx->h_udp);
@@ -622,6 +623,81 @@ int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, c
     FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
 }
+
+// ---- the one-walk form.  ctx->d_udp holds, for n datagrams: sizes | their per-64 sums | stage capacities | their sums | stage offsets
+// [n + 1] | spilled flags | the spilled count; ctx->d_udp_stage the stages.
+namespace {
+struct UdpOnce {
+    uint32_t *d_sizes, *d_stage_sizes, *d_n_spilled;
+    uint64_t *d_sums, *d_stage_sums, *d_stage_off;
+    uint8_t* d_spilled;
+    static uint64_t bytes(uint64_t n) { return 2 * up(n * 4, 16) + 2 * ((n + 63) / 64) * 8 + (n + 2) * 8 + up(n, 16) + 16; }
+    UdpOnce(uint8_t* b, uint64_t n) {
+        const uint64_t nb = (n + 63) / 64;
+        d_sizes = (uint32_t*)b;
+        d_sums = (uint64_t*)(b += up(n * 4, 16));
+        d_stage_sizes = (uint32_t*)(b += nb * 8);
+        d_stage_sums = (uint64_t*)(b += up(n * 4, 16));
+        d_stage_off = (uint64_t*)(b += nb * 8);
+        d_spilled = (b += (n + 2) * 8);
+        d_n_spilled = (uint32_t*)(b += up(n, 16));
+    }
+};
+}  // namespace
+
+// The front half: every datagram walked once into its stage, d_out_offsets / d_drop / d_udp_status as fg_udp_unpack_device leaves them
+// except for what the back half settles (the checksums of spilled rows, UTF-8), *total = the packed bytes.  Synchronises s once.
+// n > 0, max_inflated checked by the caller.
+int fg_udp_once_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
+                      uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, hipStream_t s) {
+    ctx->udp_last_spilled = 0;
+    if (!fg_launch_udp_stage || !fg_launch_udp_write_spilled || !fg_launch_udp_pack || !fg_udp_stage_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, UdpOnce::bytes(n))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_stage, &ctx->d_udp_stage_cap, fg_udp_stage_bytes(nbytes, n))) != FG_OK) return rc;
+    const UdpOnce u(ctx->d_udp, n);
+    FG_LAUNCH(ctx, fg_launch_udp_stage(d_bytes, d_offsets, n, (uint32_t)max_inflated, u.d_stage_sizes, u.d_stage_sums, u.d_stage_off, ctx->d_udp_stage,
+                                       ctx->d_udp_stage_cap, u.d_sizes, u.d_sums, d_out_offsets, d_udp_status, d_drop, u.d_spilled, u.d_n_spilled, s));
+    FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->udp_last_spilled, u.d_n_spilled, 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+// The back half, into d_out[0 .. out_cap) with out_cap >= the front half's total: the write walk for the spilled rows (when there are
+// any), every other row from its stage or its datagram, UTF-8.  Queued on s, not waited for.
+int fg_udp_once_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                     uint64_t out_cap, uint8_t* d_drop, uint8_t* d_udp_status, hipStream_t s) {
+    const UdpOnce u(ctx->d_udp, n);
+    if (ctx->udp_last_spilled)
+        FG_LAUNCH(ctx, fg_launch_udp_write_spilled(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, u.d_spilled, s));
+    FG_LAUNCH(ctx, fg_launch_udp_pack(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, ctx->d_udp_stage, u.d_stage_off,
+                                      ctx->d_udp_stage_cap, u.d_spilled, s));
+    return FG_OK;
+}
+
+// fg_udp_unpack_device without the sizing call: one walk per stream (fg_udp.hip)
+int fg_udp_unpack_once_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
+                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total,
+                              void* stream) {
+    if (!ctx || !d_out || !d_offsets || !d_out_offsets || !d_drop || !d_udp_status || !total || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) != 0) return FG_ERR_ARG;
+    if (max_inflated == 0) max_inflated = FG_UDP_DEFAULT_MAX_INFLATED;
+    if (max_inflated > FG_UDP_MAX_MAX_INFLATED) return FG_ERR_ARG;
+    *total = 0;
+    ctx->udp_last_spilled = 0;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (n == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = fg_udp_once_front(ctx, d_bytes, nbytes, d_offsets, n, max_inflated, d_out_offsets, d_drop, d_udp_status, total, s)) != FG_OK) return rc;
+    if (*total > out_cap) return FG_ERR_ENT_OVERFLOW;
+    return fg_udp_once_pack(ctx, d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_drop, d_udp_status, s);
+}
+uint64_t fg_udp_last_spilled(const fg_ctx* ctx) { return ctx ? ctx->udp_last_spilled : 0; }
 
 int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
                             const uint64_t* d_offsets, uint64_t n, const uint8_t* d_bad_utf8, const fg_tables* tables,

@@ -87,6 +87,18 @@ extern "C" int fg_launch_udp_write(const uint8_t* d_bytes, const uint64_t* d_off
                                    uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
 extern "C" int fg_launch_udp_finish(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
                                     uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, hipStream_t stream) __attribute__((weak));
+// ... and its one-walk form: stage (capacities, their scan, the walk, the scan of the sizes), the write walk for the spilled rows, pack.
+// (WEAK references as above: without them fg_udp_unpack_once_device and fg_udp_transcode_batch answer FG_ERR_UNSUPPORTED.)
+extern "C" uint64_t fg_udp_stage_bytes(uint64_t nbytes, uint64_t n) __attribute__((weak));
+extern "C" int fg_launch_udp_stage(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, uint32_t max_inflated, uint32_t* d_stage_sizes,
+                                   uint64_t* d_stage_sums, uint64_t* d_stage_off, uint8_t* d_stage, uint64_t stage_cap, uint32_t* d_sizes,
+                                   uint64_t* d_block_sums, uint64_t* d_out_offsets, uint8_t* d_status, uint8_t* d_drop, uint8_t* d_spilled,
+                                   uint32_t* d_n_spilled, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_udp_write_spilled(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                                           uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, const uint8_t* d_spilled, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_udp_pack(const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                                  uint64_t out_cap, uint8_t* d_status, uint8_t* d_drop, const uint8_t* d_stage, const uint64_t* d_stage_off,
+                                  uint64_t stage_cap, const uint8_t* d_spilled, hipStream_t stream) __attribute__((weak));
 // the segmented framer (fg_frame_multi.hip): *d_result = two device words, the delimiter count (FG_FRAME_ABORTED: launch again, classic)
 // and the slot count.  (WEAK references, as fg_launch_syslen above: without the kernels fg_frame_multi_device answers
 // FG_ERR_UNSUPPORTED.  The product library always has them: build.py checks the link.)
@@ -208,6 +220,9 @@ struct fg_ctx {
     // so no two of them have these buffers in use at once.
     uint8_t* d_udp = nullptr;        // fg_udp_unpack_device: per-datagram sizes, then the per-64 sums of the scan
     uint64_t d_udp_cap = 0;
+    uint8_t* d_udp_stage = nullptr;  // fg_udp_unpack_once_device: the stages the one walk inflates into
+    uint64_t d_udp_stage_cap = 0;
+    uint32_t udp_last_spilled = 0;   // fg_udp_last_spilled (a word the front half downloads into)
     uint64_t* d_udp_off = nullptr;   // fg_udp_decode_batch: the datagrams' offsets
     uint64_t d_udp_off_cap = 0;
     uint8_t* d_udp_st = nullptr;     // ... their fg_udp_status
@@ -481,6 +496,12 @@ int copy_table(fg_ctx* ctx, const fg_tables& dst, const fg_tables& src, uint64_t
 // which RFC3164 kernel runs.)
 extern "C" int fg_finish_deferred_general(fg_ctx* ctx, fg_framing framing, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n,
                                const uint8_t* d_bad_utf8, const fg_tables* tables, void* stream);
+// the two halves of fg_udp_unpack_once_device (fg_capi.cpp), for fg_udp_transcode_batch, which sizes its buffer between them: the front
+// walks every datagram once and synchronises for *total, the pack fills d_out[0 .. out_cap) (out_cap >= *total) and is not waited for
+extern "C" int fg_udp_once_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
+                                 uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, hipStream_t s);
+extern "C" int fg_udp_once_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
+                                uint64_t out_cap, uint8_t* d_drop, uint8_t* d_udp_status, hipStream_t s);
 // one fused launch on `stream` (fg_capi.cpp): *d_total = its result words in ctx scratch.  FG_ERR_UNSUPPORTED: nothing was launched
 extern "C" int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                                     uint64_t* d_offsets, uint64_t cap, const fg_tables* tables, uint64_t avg_line, void* stream,

@@ -1745,4 +1745,55 @@ int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, con
     return FG_OK;
 }
 
+// fg_transcode_batch for a batch of UDP datagrams: the front half of fg_udp_decode_batch with the one-walk unpacker (which sizes the
+// packed buffer between its two halves, so no stream is walked for its size alone), then the transcode tail over every datagram with
+// the drop flags as the skipped rows.  One piece, as fg_udp_decode_batch.
+int fg_udp_transcode_batch(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecfg, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets,
+                           uint64_t n, uint64_t max_inflated, fg_transcoded* out, const uint8_t** udp_status) {
+    if (!ctx || !ecfg || !out || !udp_status || !offsets || (nbytes && !bytes)) return FG_ERR_ARG;
+    if (!text_format(fmt)) return FG_ERR_ARG;  // (FG_CAPNP: the reference has no Decoder for it, as fg_udp_decode_batch)
+    if (n && (offsets[0] != 0 || offsets[n] != nbytes)) return FG_ERR_ARG;
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i] > offsets[i + 1]) return FG_ERR_ARG;
+    if (max_inflated == 0) max_inflated = FG_UDP_DEFAULT_MAX_INFLATED;
+    if (max_inflated > FG_UDP_MAX_MAX_INFLATED) return FG_ERR_ARG;
+    *out = fg_transcoded{};
+    *udp_status = nullptr;
+    ctx->udp_last_spilled = 0;
+    out->consumed = nbytes;
+    if (n == 0) return FG_OK;
+    DeviceGuard g(ctx->device);
+    DrainGuard drained(ctx);  // (every exit from here on waits for what it queued)
+    hipStream_t s = ctx->stream;
+    int rc;
+    // 1. the datagrams and their offsets to HBM
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_off, &ctx->d_udp_off_cap, (n + 2) * 8)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_offsets, &ctx->d_offsets_cap, (n + 2) * 8)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_bad, &ctx->d_bad_cap, n + 1)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_st, &ctx->d_udp_st_cap, n + 1)) != FG_OK) return rc;
+    if (nbytes) FG_HIP(ctx, hipMemcpyAsync(ctx->d_bytes, bytes, nbytes, hipMemcpyHostToDevice, s));
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_bytes + nbytes, 0, up(nbytes, 16) + 16 - nbytes, s));
+    FG_HIP(ctx, hipMemcpyAsync(ctx->d_udp_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    // 2. one walk per stream; the packed buffer grows to the batch between the walk and the pack (the walk is never repeated)
+    uint64_t total = 0;
+    if ((rc = fg_udp_once_front(ctx, ctx->d_bytes, nbytes, ctx->d_udp_off, n, max_inflated, ctx->d_offsets, ctx->d_bad, ctx->d_udp_st, &total, s)) != FG_OK)
+        return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_sl_packed, &ctx->d_sl_packed_cap, up(total, 16) + 16)) != FG_OK) return rc;
+    if ((rc = fg_udp_once_pack(ctx, ctx->d_bytes, ctx->d_udp_off, n, ctx->d_offsets, ctx->d_sl_packed, total, ctx->d_bad, ctx->d_udp_st, s)) != FG_OK) return rc;
+    // (the decoders load 16 bytes at a time: the pad behind the last payload is zero, as behind an uploaded batch)
+    FG_HIP(ctx, hipMemsetAsync(ctx->d_sl_packed + total, 0, up(total, 16) + 16 - total, s));
+    // 3. decode, encode, frame; the stream, the verdicts and the reasons back
+    fg_transcoded res{};
+    res.n = n;
+    res.consumed = nbytes;
+    if ((rc = transcode_tail(ctx, fmt, FG_FRAME_NONE, ecfg, ctx->d_sl_packed, total, n, ctx->d_bad, nbytes, false, &res)) != FG_OK) return rc;
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_udp, &ctx->h_udp_cap, up(n, 16))) != FG_OK) return rc;
+    FG_HIP(ctx, hipMemcpyAsync(ctx->h_udp, ctx->d_udp_st, n, hipMemcpyDeviceToHost, s));
+    if ((rc = drained.done()) != FG_OK) return rc;
+    *out = res;
+    *udp_status = ctx->h_udp;
+    return FG_OK;
+}
+
 }  // extern "C"

@@ -10,9 +10,11 @@
 //   stored block whose LEN is not ~NLEN; block type 3; reserved gzip flag bits; a wrong FHCRC; input that ends before the final
 //   block's end or before the whole trailer.  Only the first gzip member is read; bytes behind either trailer are ignored.
 //
-// The walk runs in two forms.  WRITE = false produces no byte: lengths and distances need the symbol stream alone, so it yields the
+// The walk runs in three forms.  WRITE = false produces no byte: lengths and distances need the symbol stream alone, so it yields the
 // inflated size or a verdict.  WRITE = true produces the bytes (back-references read the lane's own earlier output), accumulates
-// Adler-32 / CRC-32 and compares the trailer.
+// Adler-32 / CRC-32 and compares the trailer.  STAGED is both in one walk: it writes and sums like WRITE while what the stream
+// produces fits a stage of `w` bytes, and from the first piece that would not fit it goes on like the count walk (nothing written,
+// nothing summed: the bytes are then owed, and the write walk produces them once the slot is known).
 //
 // Termination: every loop below either consumes input bits or produces output, the input is bounded by the datagram and the output
 // by `lim`; running out of either is a verdict.  Nothing here waits on anything.
@@ -246,11 +248,18 @@ FG_INF int build_dynamic(Bits& br, const Tabs& t, Lens* ln) {
     return R_OK;
 }
 
+// the forms of the walk (inflate_blocks<false> and <true> are the first two)
+enum { COUNT = 0, WRITE_ALL = 1, STAGED = 2 };
+
 // The deflate stream at the reader's position into out[0 .. lim): R_OK at the end of the final block (the reader stands at the next
-// whole byte), R_TOO_LARGE when a byte beyond `lim` was asked for.  *produced = the bytes produced (counted, when !WRITE).
-template <bool WRITE>
-FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, bool gz, Sums* sums, uint32_t* produced) {
+// whole byte), R_TOO_LARGE when a byte beyond `lim` was asked for.  *produced = the bytes produced (counted, when MODE == COUNT).
+// STAGED: out[0 .. w) is the stage and *live says whether every byte so far went into it (a piece -- literal, match, stored run --
+// that would end beyond w is not written at all, and nothing is after it; the sums then stop too).
+template <int MODE>
+FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, bool gz, Sums* sums, uint32_t* produced, uint32_t w = 0u,
+                          bool* live = nullptr) {
     uint32_t o = 0;
+    bool wr = MODE != COUNT;  // (a constant in the first two forms)
     Lens ln{0u, 0u, false};
     int rc = R_OK;
     for (;;) {  // (every block consumes its three header bits)
@@ -266,7 +275,8 @@ FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, b
             const uint32_t avail = br.end - br.pos, take = len < avail ? len : avail;
             if (take) {
                 if (take > lim - o) { rc = R_TOO_LARGE; break; }
-                if (WRITE)
+                if (MODE == STAGED && wr && (o > w || take > w - o)) wr = false;
+                if (MODE != COUNT && wr)
                     for (uint32_t k = 0; k < take; ++k) {
                         const uint32_t b = br.p[br.pos + k];
                         out[o + k] = (uint8_t)b;
@@ -290,7 +300,8 @@ FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, b
                 if (sym < 0) { rc = sym == -2 ? R_TRUNC : R_BAD; break; }
                 if (sym < 256) {
                     if (o == lim) { rc = R_TOO_LARGE; break; }
-                    if (WRITE) {
+                    if (MODE == STAGED && wr && o >= w) wr = false;
+                    if (MODE != COUNT && wr) {
                         out[o] = (uint8_t)sym;
                         sums->add((uint32_t)sym, gz);
                     }
@@ -325,7 +336,8 @@ FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, b
                 if (o == lim) { rc = R_TOO_LARGE; break; }  // (zlib stops for room before it looks at the distance)
                 if (dist > o) { rc = R_BAD; break; }
                 if (len > lim - o) { rc = R_TOO_LARGE; break; }
-                if (WRITE)
+                if (MODE == STAGED && wr && (o > w || len > w - o)) wr = false;
+                if (MODE != COUNT && wr)
                     for (uint32_t k = 0; k < len; ++k) {  // (overlapping on purpose: distance 1 repeats the last byte)
                         const uint32_t b = out[o + k - dist];
                         out[o + k] = (uint8_t)b;
@@ -341,15 +353,19 @@ FG_INF int inflate_blocks(Bits& br, const Tabs& t, uint8_t* out, uint32_t lim, b
         }
     }
     *produced = o;
+    if (MODE == STAGED) *live = wr;
     return rc;
 }
 
 // One datagram that classify() sent to an inflater (kind = UDP_ZLIB / UDP_GZIP), into out[0 .. lim).  Returns R_*; *produced = the
-// bytes produced.  !WRITE: nothing is written, the trailer only has to be there.  WRITE: R_BAD_CHECK when the trailer disagrees with
-// the bytes (which stay).
-template <bool WRITE>
-FG_INF int inflate_datagram(const uint8_t* p, uint32_t len, uint32_t kind, const Tabs& t, uint8_t* out, uint32_t lim, uint32_t* produced) {
+// bytes produced.  COUNT: nothing is written, the trailer only has to be there.  WRITE_ALL: R_BAD_CHECK when the trailer disagrees with
+// the bytes (which stay).  STAGED (stage out[0 .. w), *live as inflate_blocks leaves it): the trailer is compared while *live, only
+// looked for otherwise.
+template <int MODE>
+FG_INF int inflate_datagram(const uint8_t* p, uint32_t len, uint32_t kind, const Tabs& t, uint8_t* out, uint32_t lim, uint32_t* produced,
+                            uint32_t w = 0u, bool* live = nullptr) {
     *produced = 0;
+    if (MODE == STAGED) *live = true;
     const bool gz = kind == UDP_GZIP;
     uint32_t pos;
     if (!gz) {
@@ -386,11 +402,11 @@ FG_INF int inflate_datagram(const uint8_t* p, uint32_t len, uint32_t kind, const
     }
     Bits br{p, pos, len, 0ull, 0u};
     Sums sums{1u, 0u, 0xFFFFFFFFu};
-    const int rc = inflate_blocks<WRITE>(br, t, out, lim, gz, &sums, produced);
+    const int rc = inflate_blocks<MODE>(br, t, out, lim, gz, &sums, produced, w, live);
     if (rc != R_OK) return rc;
     const uint32_t tail = gz ? 8u : 4u;
     if (br.end - br.pos < tail) return R_TRUNC;
-    if (WRITE) {
+    if (MODE == WRITE_ALL || (MODE == STAGED && *live)) {
         const uint8_t* q = p + br.pos;
         if (gz) {
             const uint32_t crc = q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
@@ -402,6 +418,24 @@ FG_INF int inflate_datagram(const uint8_t* p, uint32_t len, uint32_t kind, const
         }
     }
     return R_OK;
+}
+
+// what a walk with max_inflated + 1 bytes of room that ended with rc after `produced` bytes means for the datagram (rc is not
+// R_BAD_CHECK): its fg_udp_status so far, *size = the bytes its slot needs
+FG_INF uint32_t count_verdict(uint32_t kind, int rc, uint32_t produced, uint32_t max_inflated, uint32_t* size) {
+    *size = 0;
+    const uint32_t bad = kind == UDP_GZIP ? UDP_BAD_GZIP : UDP_BAD_ZLIB;
+    if (rc == R_BAD) return bad;
+    if (rc == R_OK && produced == max_inflated + 1u) {
+        // One byte too many AND complete: zlib had the room to reach the trailer, so a wrong checksum is still its error.  The row
+        // is dropped either way; it keeps a slot so that the write pass can tell which.
+        *size = produced;
+        return UDP_TOO_LARGE;
+    }
+    if (rc == R_TOO_LARGE || produced > max_inflated) return UDP_TOO_LARGE;
+    if (rc == R_TRUNC) return bad;
+    *size = produced;
+    return kind;
 }
 
 // The count pass's answer for one datagram: *size = the bytes its slot needs, returns the fg_udp_status so far (the write pass may
@@ -418,18 +452,7 @@ FG_INF uint32_t count_datagram(const uint8_t* p, uint64_t len, uint32_t max_infl
     // zlib with max_inflated + 1 bytes of room: a stream that wants more stops there, one that ends or breaks first does that
     uint32_t produced = 0;
     const int rc = inflate_datagram<false>(p, (uint32_t)len, kind, t, nullptr, max_inflated + 1u, &produced);
-    const uint32_t bad = kind == UDP_GZIP ? UDP_BAD_GZIP : UDP_BAD_ZLIB;
-    if (rc == R_BAD) return bad;
-    if (rc == R_OK && produced == max_inflated + 1u) {
-        // One byte too many AND complete: zlib had the room to reach the trailer, so a wrong checksum is still its error.  The row
-        // is dropped either way; it keeps a slot so that the write pass can tell which.
-        *size = produced;
-        return UDP_TOO_LARGE;
-    }
-    if (rc == R_TOO_LARGE || produced > max_inflated) return UDP_TOO_LARGE;
-    if (rc == R_TRUNC) return bad;
-    *size = produced;
-    return kind;
+    return count_verdict(kind, rc, produced, max_inflated, size);
 }
 
 // The write pass for one datagram the count pass gave `size` bytes at `out` (not for a bare record: the wave copies those):
@@ -440,6 +463,45 @@ FG_INF uint32_t write_datagram(const uint8_t* p, uint64_t len, uint32_t st, uint
     uint32_t produced = 0;
     const int rc = inflate_datagram<true>(p, (uint32_t)len, kind, t, out, size, &produced);
     if (rc != R_OK || produced != size) return kind == UDP_GZIP ? UDP_BAD_GZIP : UDP_BAD_ZLIB;
+    return st;
+}
+
+// ---- the one-walk form: count and write in one pass over the stream, into a stage whose size is guessed from the datagram's length
+// The stage of a datagram of `len` bytes: what a compressed record of that length usually inflates to, and never more than zlib is
+// given room for.  A bare record takes none (the wave copies it from the datagram).  K = 4, C = 64: one record per datagram
+// compresses about 1.3 times, so a stream that outgrows four times its length is a run-length case, and those pay the
+// second walk.  A multiple of 16 unless it is the cap itself.
+constexpr uint32_t kStageK = 4u, kStageC = 64u;
+FG_INF uint32_t stage_capacity(const uint8_t* p, uint64_t len, uint32_t max_inflated) {
+    if (classify(p, len) == UDP_RAW) return 0u;
+    const uint64_t guess = ((uint64_t)kStageK * len + kStageC + 15ull) & ~15ull, cap = (uint64_t)max_inflated + 1ull;
+    return (uint32_t)(guess < cap ? guess : cap);
+}
+
+// One datagram in one walk, with the stage out[0 .. w): returns the fg_udp_status, *size = the bytes of its slot, *spilled = whether
+// they did not fit the stage.  Not spilled: status and size are what count_datagram followed by write_datagram leave (the trailer's
+// verdict included) and out[0 .. size) holds the slot's bytes.  Spilled: they are count_datagram's, and write_datagram still has to
+// run on the slot.  A bare record is neither staged nor spilled: size = len.  max_inflated < 2^31.
+FG_INF uint32_t stage_datagram(const uint8_t* p, uint64_t len, uint32_t max_inflated, uint32_t w, const Tabs& t, uint8_t* out, uint32_t* size,
+                               uint32_t* spilled) {
+    *size = 0;
+    *spilled = 0;
+    const uint32_t kind = classify(p, len);
+    if (kind == UDP_RAW) {
+        if (len > 0x7FFFFFFFull) return UDP_TOO_LARGE;
+        *size = (uint32_t)len;
+        return UDP_RAW;
+    }
+    if (len > 0xFFFFFFF0ull) return UDP_TOO_LARGE;
+    uint32_t produced = 0;
+    bool live = true;
+    const int rc = inflate_datagram<STAGED>(p, (uint32_t)len, kind, t, out, max_inflated + 1u, &produced, w, &live);
+    if (rc == R_BAD_CHECK) {  // (live, so the bytes are in the stage: they keep their slot, as behind write_datagram)
+        *size = produced;
+        return kind == UDP_GZIP ? UDP_BAD_GZIP : UDP_BAD_ZLIB;
+    }
+    const uint32_t st = count_verdict(kind, rc, produced, max_inflated, size);
+    *spilled = *size != 0u && !live ? 1u : 0u;  // (a stream without a slot owes nothing)
     return st;
 }
 

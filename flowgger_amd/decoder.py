@@ -556,6 +556,39 @@ class UdpUnpacker:
         L.check(L.lib().fg_udp_unpack_device(*args, d_out.data_ptr(), cap, *tail), "fg_udp_unpack_device")
         return d_out[:cap], d_off, d_drop[:n], d_st[:n]
 
+    def unpack_once(self, d_bytes, d_offsets, stream=None, out_cap=None):
+        """The same results from ONE walk per stream (fg_udp_unpack_once_device).  There is no sizing call, so the output buffer is a
+        guess: out_cap bytes (None: twice the datagrams' bytes + 4 KiB).  When the batch needs more the call says how much and is
+        made again with a buffer of that size (a host that never wants the walk twice uses Pipeline.run_datagrams, which sizes its
+        buffer between the walk and the pack).  `.last_spilled()`: how many streams outgrew their stage and were written by a
+        second walk.  The stream is synchronised before the tensors are returned."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        n = d_offsets.numel() - 1
+        dev = d_bytes.device
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_drop = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        d_st = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        total = C.c_uint64()
+        args = (self.decoder._ctx, d_bytes.data_ptr(), d_bytes.numel(), d_offsets.data_ptr(), n, self.max_inflated)
+        tail = (d_off.data_ptr(), d_drop.data_ptr(), d_st.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
+        cap = int(2 * d_bytes.numel() + 4096 if out_cap is None else out_cap)
+        d_out = torch.zeros((cap + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+        rc = L.lib().fg_udp_unpack_once_device(*args, d_out.data_ptr(), cap, *tail)
+        if rc == L.FG_ERR_ENT_OVERFLOW:
+            cap = int(total.value)
+            d_out = torch.zeros((cap + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+            rc = L.lib().fg_udp_unpack_once_device(*args, d_out.data_ptr(), cap, *tail)
+        L.check(rc, "fg_udp_unpack_once_device")
+        stream.synchronize()
+        cap = int(total.value)
+        return d_out[:cap], d_off, d_drop[:n], d_st[:n]
+
+    def last_spilled(self) -> int:
+        return int(L.lib().fg_udp_last_spilled(self.decoder._ctx))
+
 
 class FlushPolicy:
     """When a batching framer hands what it holds to the GPU (the fields of the C++ fg::FlushPolicy that make sense before the lines

@@ -154,6 +154,28 @@ class TranscodedMulti(Transcoded):
         self.seg_first, self.seg_consumed, self.seg_stop = seg_first, seg_consumed, seg_stop
 
 
+class TranscodedUdp(Transcoded):
+    """Result of Pipeline.run_datagrams: Transcoded (one verdict per DATAGRAM, no frame_offsets) plus udp_status (FG_UDP_*: why a
+    datagram was dropped before the decoder saw it)."""
+
+    def __init__(self, out, out_offsets, meta, enc_status, consumed, udp_status, fmt):
+        super().__init__(out, out_offsets, meta, enc_status, None, consumed)
+        self.udp_status, self._fmt = udp_status, fmt
+
+    def stderr_lines(self):
+        """what the reference writes to stderr for the batch, in order: per datagram that produced nothing, the bare error
+        (input/udp_input.rs:84-86 prints `{e}` alone) -- of the gate / inflater / UTF-8 check, else of the decoder, else of the encoder"""
+        lib, out = L.lib(), []
+        for i in range(self.n):
+            if self.udp_status[i] > L.FG_UDP_GZIP:
+                out.append(lib.fg_udp_error_string(int(self.udp_status[i])).decode())
+            elif self.meta[i] & 0xFF:
+                out.append(lib.fg_error_string(self._fmt, int(self.meta[i] & 0xFF)).decode())
+            elif self.enc_status[i]:
+                out.append(lib.fg_encode_error_string(int(self.enc_status[i])).decode())
+        return out
+
+
 class Pipeline:
     """decoder -> encoder -> merger for whole batches with HOST buffers (fg_transcode_batch): what
     ``handle_line`` (splitter/line_splitter.rs:44-54) does per line.  Only the encoded bytes and the per-line
@@ -235,3 +257,35 @@ class Pipeline:
                                view(res.slot_offsets, m if syslen else m + 1, np.uint64), view(res.slot_kind, m, np.uint8),
                                view(res.seg_first, K + 1, np.uint64), view(res.seg_consumed, K, np.uint64),
                                view(res.seg_stop, K, np.uint8) if res.seg_stop else None)
+
+    def run_datagrams(self, datagrams, max_inflated=None, now_ts: float = 0.0) -> TranscodedUdp:
+        """fg_udp_transcode_batch: the body of the UDP input's receive loop (input/udp_input.rs:66-143) for a batch -- a list of
+        datagrams, or (data uint8, offsets uint64[n + 1]) with the datagrams back to back; each a zlib stream, a gzip member or a
+        bare record.  `.out` is what the reference sends for them, `.stderr_lines()` what it prints.  max_inflated: the most a
+        compressed datagram may inflate to (None = 65 527 * 5)."""
+        import numpy as np
+
+        from .decoder import pack_lines
+
+        if isinstance(datagrams, tuple):
+            data, offsets = datagrams
+        else:
+            data, offsets = pack_lines(list(datagrams))
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        nbytes = int(offsets[-1]) if n else 0
+        cfg, _keep = self.encoder._cfg_struct(now_ts)
+        res, ust = L.fg_transcoded(), C.c_void_p()
+        rc = L.lib().fg_udp_transcode_batch(self.decoder._ctx, self.decoder.fmt, C.byref(cfg), data.ctypes.data if nbytes else None, nbytes,
+                                            offsets.ctypes.data, n, int(max_inflated or 0), C.byref(res), C.byref(ust))
+        L.check(rc, "fg_udp_transcode_batch")
+
+        def view(ptr, count, dt):
+            if not count or not ptr:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        return TranscodedUdp(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, n + 1, np.uint64) if n else np.zeros(1, np.uint64),
+                             view(res.meta, n, np.uint32), view(res.enc_status, n, np.uint8), int(res.consumed), view(ust, n, np.uint8),
+                             self.decoder.fmt)

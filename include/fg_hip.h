@@ -564,6 +564,21 @@ const char* fg_udp_error_string(uint8_t st);
 int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n,
                          uint64_t max_inflated, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets,
                          uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, void* stream);
+/* THE SAME IN ONE WALK PER STREAM (additive under the same FG_ABI_VERSION).  fg_udp_unpack_device walks every compressed datagram
+ * twice (count, then write) and a caller that has no size to give walks it a third time for the sizing call.  This form guesses:
+ * every gated datagram of `len` bytes is inflated into a ctx-owned stage of min(max_inflated + 1, 4 * len + 64 rounded up to 16)
+ * bytes by a walk that also counts, so its size, its verdict and its bytes exist after one pass; a stream that outgrows its stage
+ * is only counted from there on ("spilled") and written by the write walk afterwards, into its slot.  Arguments and results are
+ * those of fg_udp_unpack_device, byte for byte (d_out[0 .. *total), d_out_offsets, d_drop, d_udp_status, *total), except:
+ *   d_out == NULL        FG_ERR_ARG: there is no sizing call -- give a buffer, and on FG_ERR_ENT_OVERFLOW one of *total bytes
+ *   *total > out_cap     FG_ERR_ENT_OVERFLOW, the need in *total, nothing written to d_out (d_out_offsets, d_drop and d_udp_status
+ *                        are as far as the front half takes them: checksums of spilled rows and UTF-8 are not settled)
+ * The stream is synchronised ONCE, for *total; what is written behind that is queued on it and not waited for.
+ * fg_udp_last_spilled: how many datagrams of the last one-walk unpack on this ctx (this entry or fg_udp_transcode_batch) spilled. */
+int fg_udp_unpack_once_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n,
+                              uint64_t max_inflated, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets,
+                              uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, void* stream);
+uint64_t fg_udp_last_spilled(const fg_ctx* ctx);
 
 /* HOST-BUFFER decode: the batch is decoded into ctx-owned pinned host memory (`out` is filled with host pointers valid until
  * the next call on this ctx or fg_destroy).  Synchronous.  Entry-table capacity grows automatically.
@@ -813,7 +828,7 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
  *   slot_kind[n]   fg_slot_kind
  *   seg_first[n_segs + 1], seg_consumed[n_segs], seg_stop[n_segs] (fg_syslen_stop / fg_capnp_stop; NULL for LINE / NUL)
  * fg_last_host_path says which framing form ran (FG_PATH_FRAME_MULTI .. FG_PATH_FRAME_CAPNP_MULTI_HOST); fg_last_syslen_stop and
- * fg_last_capnp_stop are not touched.  Out of scope here: slicing over streams, the fused launch, datagrams. */
+ * fg_last_capnp_stop are not touched.  Out of scope here: slicing over streams, the fused launch. */
 typedef struct fg_transcoded_multi {
     const uint8_t* out;
     uint64_t out_bytes;
@@ -830,6 +845,21 @@ typedef struct fg_transcoded_multi {
 int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_encode_cfg* cfg, const uint8_t* bytes,
                              uint64_t nbytes, const uint64_t* seg_starts, const uint8_t* seg_final, uint64_t n_segs,
                              fg_transcoded_multi* out);
+
+/* THE SAME FOR A BATCH OF UDP DATAGRAMS (additive under the same FG_ABI_VERSION): the body of the UDP input's receive loop
+ * (input/udp_input.rs:66-143: the gate, inflate, from_utf8, `decoder.decode`, `encoder.encode`, `tx.send`) plus the Merger::frame of
+ * the output.  Upload, the one-walk unpack (fg_udp_unpack_once_device) into ctx-owned HBM, then decode + encode + frame as
+ * fg_transcode_batch does for FG_FRAME_NONE: neither the inflated payloads nor the tables cross the link.
+ *   bytes, offsets, n, max_inflated   as fg_udp_decode_batch, with its argument checks; fmt a text format (FG_CAPNP: FG_ERR_ARG)
+ *   out          as fg_transcode_batch: frame_offsets = NULL, consumed = nbytes, n = n.  A dropped datagram is a skipped row:
+ *                meta & 0xFF == FG_ST_BAD_UTF8, enc_status == 1, an empty message
+ *   udp_status   out: n fg_udp_status bytes (pinned, ctx-owned) -- why a datagram was dropped (fg_udp_error_string)
+ * What the reference writes to stderr for datagram i is the bare error, without the line: fg_udp_error_string(udp_status[i]) for a
+ * drop, else fg_error_string(meta[i] & 0xFF) for a failed decode, else fg_encode_error_string(enc_status[i]) for a failed encode.
+ * Everything returned stays valid until the next host-buffer call on this ctx.  fg_last_host_path is not touched; fg_udp_last_spilled
+ * tells how many streams took the second walk. */
+int fg_udp_transcode_batch(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* cfg, const uint8_t* bytes, uint64_t nbytes,
+                           const uint64_t* offsets, uint64_t n, uint64_t max_inflated, fg_transcoded* out, const uint8_t** udp_status);
 
 /* Host memory for the framer's batch buffers (bytes, offsets): PAGE-LOCKED, through a process-wide pool -- a freed block is kept
  * (up to idle_bytes in total) and handed to the next request it fits, so a framer per connection does not pin and unpin megabytes per
