@@ -125,10 +125,13 @@ def test_ltsv_structural_mutation_fuzz(oracle):
 
 @pytest.mark.parametrize("opts", [dict(), dict(force_head=True), dict(no_head=True), dict(force_head=True, tile_cap=6144, lines_per_group=5)])
 def test_ltsv_long_lines_head_staging(oracle, opts):
-    """LTSV lines of 64 B .. 8 KiB: only the head of a long line is staged, what lies behind it is scanned for a TAB without being
+    """LTSV lines of 64 B .. 8 KiB: only the head of a long line is staged -- LtsvFormatT::kHeadBytes = 512 bytes, the alignment slack
+    o0 & 15 included, so the staged part ends at line index 497 .. 512 --, what lies behind it is scanned for a TAB without being
     stored (fg_ltsv.hip LtsvFormatT<true>).  Lines whose long part is the last one (the corpus), lines with MORE parts behind the
-    first KiB (typed ones, `time` / `host` / `level` back there, parts without ':'), a cut part that is typed, a cut name, TABs exactly
-    at the head's end -- all must give the oracle's Records, with head staging forced on, off, and left to the launcher."""
+    head (typed ones, `time` / `host` / `level` back there, parts without ':'), a cut part that is typed, a cut name, TABs exactly
+    at the head's end -- all must give the oracle's Records, with head staging forced on, off, and left to the launcher.  The
+    padding is drawn twice: around 1 KiB (well behind the head: the parts of interest are found by the scan alone) and so that the
+    part of interest straddles line index 497 .. 512 (tests/ltsv_hazards.py sweeps the same edge byte by byte)."""
     rng = np.random.default_rng(11)
     dec = LTSVDecoder(synth.LTSV_CONFIG)
     dec.set_launch_opts(**opts)
@@ -145,6 +148,20 @@ def test_ltsv_long_lines_head_staging(oracle, opts):
         extra.append(b"host:h\ttime:1\tpad:" + pad(k - 40) + b"\tcounter:" + b"7" * int(rng.integers(1, 19)))
         extra.append(b"host:h\tpad:" + pad(k - 30) + b"\ttime:" + b"1" * int(rng.integers(1, 15)) + b".5")
         extra.append(b"host:h\ttime:2\tpad:" + pad(k - 35) + b"\t" + b"n" * int(rng.integers(1, 60)) + b":v")
+    # the same four shapes around the head the kernel has: the TAB in front of the tail / the typed value / the timestamp / the name
+    # at or across line index 497 .. 512
+    rng2 = np.random.default_rng(12)
+    tails = [b"\tlevel:3", b"\tlevel:9", b"\tcounter:12", b"\tcounter:x", b"\tnovalue", b"\thost:late", b"\ttime:[2015-08-05T15:53:45Z]", b"\t", b"",
+             b"\tmean:1e3\tdone:true", b"\tk:" + pad(700), b"\tscore:-" + b"9" * 19]
+    for i in range(1500):
+        tail = tails[i % len(tails)] if i % 24 < 12 else b"\tk:" + pad(int(rng2.integers(1, 3000)))
+        extra.append(b"time:1.5\thost:h\tmessage:" + pad(int(rng2.integers(480, 516)) - 24) + tail)  # (the TAB at 480 .. 515)
+        nd = int(rng2.integers(1, 19))
+        extra.append(b"host:h\ttime:1\tpad:" + pad(int(rng2.integers(497 - nd, 514)) - 27) + b"\tcounter:" + b"7" * nd)
+        nd = int(rng2.integers(1, 15))
+        extra.append(b"host:h\tpad:" + pad(int(rng2.integers(495 - nd, 514)) - 17) + b"\ttime:" + b"1" * nd + b".5")
+        nn = int(rng2.integers(1, 60))
+        extra.append(b"host:h\ttime:2\tpad:" + pad(int(rng2.integers(496 - nn, 514)) - 19) + b"\t" + b"n" * nn + b":v")
     lines = base + mutate_py(base[:2000], rng, LTSV_ALPHABET) + extra
     order = rng.permutation(len(lines))
     both_paths(dec, oracle, [lines[i] for i in order], synth.LTSV_CONFIG, host=False)
