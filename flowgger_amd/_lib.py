@@ -115,6 +115,18 @@ class fg_transcoded_multi(C.Structure):
                 ("seg_consumed", C.c_void_p), ("seg_stop", C.c_void_p), ("n", C.c_uint64)]
 
 
+FG_COMP_NONE, FG_COMP_GZIP = 0, 1  # fg_compression
+
+
+class fg_compress_cfg(C.Structure):
+    _fields_ = [("codec", C.c_int), ("coalesce", C.c_uint32), ("member_bytes", C.c_uint32)]
+
+
+class fg_compressed(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("z_bytes", C.c_uint64), ("z_offsets", C.c_void_p), ("member_first", C.c_void_p),
+                ("n_members", C.c_uint64), ("raw_bytes", C.c_uint64)]
+
+
 class fg_tz_table(C.Structure):
     _fields_ = [("n_zones", C.c_uint32), ("names", C.POINTER(C.c_char_p)), ("zone_first", C.c_void_p), ("utc_start", C.c_void_p),
                 ("utc_offset", C.c_void_p)]
@@ -223,6 +235,12 @@ def lib() -> C.CDLL:
     L.fg_frame_decode_capnp_multi_batch.argtypes = [vp, vp, u64, vp, u64, C.POINTER(fg_tables), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.fg_transcode_multi_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(fg_encode_cfg), vp, u64, vp, vp, u64, C.POINTER(fg_transcoded_multi)]
+    L.fg_deflate_block_bytes.restype = u32
+    L.fg_deflate_bound.argtypes = [u64, u64]
+    L.fg_deflate_bound.restype = u64
+    L.fg_deflate_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), vp]
+    L.fg_set_output_compression.argtypes = [vp, C.POINTER(fg_compress_cfg)]
+    L.fg_last_compressed.argtypes = [vp, C.POINTER(fg_compressed)]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

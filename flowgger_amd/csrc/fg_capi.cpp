@@ -226,6 +226,7 @@ int fg_clone(const fg_ctx* src, fg_ctx** out) {
     if (!ctx) return FG_ERR_NOMEM;
     ctx->device = src->device;
     ctx->lo = src->lo;
+    ctx->compress = src->compress;
     ctx->schema_names = src->schema_names;
     ctx->schema_types = src->schema_types;
     for (int k = 0; k < 4; ++k) {
@@ -300,6 +301,12 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_tout) (void)hipFree(ctx->d_tout);
     if (ctx->d_tmeta) (void)hipFree(ctx->d_tmeta);
     if (ctx->h_tout) (void)hipHostFree(ctx->h_tout);
+    if (ctx->d_df) (void)hipFree(ctx->d_df);
+    if (ctx->d_df_blk) (void)hipFree(ctx->d_df_blk);
+    if (ctx->d_df_slots) (void)hipFree(ctx->d_df_slots);
+    if (ctx->d_df_cut) (void)hipFree(ctx->d_df_cut);
+    if (ctx->d_zout) (void)hipFree(ctx->d_zout);
+    if (ctx->h_zout) (void)hipHostFree(ctx->h_zout);
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     for (hipEvent_t e : ctx->ev_slice) (void)hipEventDestroy(e);
@@ -698,6 +705,116 @@ int fg_udp_unpack_once_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbyt
     return fg_udp_once_pack(ctx, d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_drop, d_udp_status, s);
 }
 uint64_t fg_udp_last_spilled(const fg_ctx* ctx) { return ctx ? ctx->udp_last_spilled : 0; }
+
+// ---- the output compressor (fg_deflate.hip).  ctx->d_df holds, for n members: block counts | sizes | CRCs | the sums of the two scans (one
+// after the other) | blk_first[n + 1] | the error word, the ticket word; ctx->d_df_blk, per block: size | CRC | offset in its member;
+// ctx->d_df_slots the slots.
+namespace {
+struct DfMembers {
+    uint32_t *d_nblk, *d_msize, *d_crc, *d_err, *d_ticket;
+    uint64_t *d_sums, *d_blk_first;
+    static uint64_t bytes(uint64_t n) { return 3 * up(n * 4, 16) + up((n + 63) / 64 * 8, 16) + (n + 2) * 8 + 16; }
+    DfMembers(uint8_t* b, uint64_t n) {
+        d_nblk = (uint32_t*)b;
+        d_msize = (uint32_t*)(b += up(n * 4, 16));
+        d_crc = (uint32_t*)(b += up(n * 4, 16));
+        d_sums = (uint64_t*)(b += up(n * 4, 16));
+        d_blk_first = (uint64_t*)(b += up((n + 63) / 64 * 8, 16));
+        d_err = (uint32_t*)(b += (n + 2) * 8);
+        d_ticket = d_err + 1;
+    }
+};
+struct DfBlocks {
+    uint32_t *d_size, *d_crc, *d_rel;
+    static uint64_t bytes(uint64_t nb) { return 3 * up(nb * 4, 16); }
+    DfBlocks(uint8_t* b, uint64_t nb) {
+        d_size = (uint32_t*)b;
+        d_crc = (uint32_t*)(b += up(nb * 4, 16));
+        d_rel = (uint32_t*)(b += up(nb * 4, 16));
+    }
+};
+}  // namespace
+
+int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint64_t* d_z_offsets,
+                     uint64_t* total, hipStream_t s) {
+    *total = 0;
+    ctx->df_blocks = 0;
+    if (!fg_launch_deflate_count || !fg_launch_deflate_blocks || !fg_launch_deflate_sizes || !fg_launch_deflate_pack || !fg_deflate_slot_bytes)
+        return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df, &ctx->d_df_cap, DfMembers::bytes(n_members))) != FG_OK) return rc;
+    const DfMembers m(ctx->d_df, n_members);
+    uint64_t nb = 0;
+    ctx->df_err = 0;
+    FG_LAUNCH(ctx, fg_launch_deflate_count(d_cuts, n_members, nbytes, m.d_nblk, m.d_sums, m.d_blk_first, m.d_err, s));
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_err, m.d_err, 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(&nb, m.d_blk_first + n_members, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->df_err) return FG_ERR_ARG;
+    if (nb == 0) {  // (nothing but empty members)
+        FG_HIP(ctx, hipMemsetAsync(d_z_offsets, 0, (n_members + 1) * 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_blk, &ctx->d_df_blk_cap, DfBlocks::bytes(nb))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_slots, &ctx->d_df_slots_cap, fg_deflate_slot_bytes(nbytes, nb))) != FG_OK) return rc;
+    const DfBlocks b(ctx->d_df_blk, nb);
+    FG_LAUNCH(ctx, fg_launch_deflate_blocks(d_bytes, d_cuts, m.d_blk_first, n_members, nb, ctx->d_df_slots, ctx->d_df_slots_cap, b.d_size, b.d_crc,
+                                            m.d_ticket, fg::device_cus(), s));
+    FG_LAUNCH(ctx, fg_launch_deflate_sizes(d_cuts, m.d_blk_first, n_members, b.d_size, b.d_crc, b.d_rel, m.d_crc, m.d_msize, m.d_sums, d_z_offsets, s));
+    FG_HIP(ctx, hipMemcpyAsync(total, d_z_offsets + n_members, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    ctx->df_blocks = nb;
+    return FG_OK;
+}
+int fg_deflate_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_cuts, uint64_t n_members, const uint64_t* d_z_offsets, uint8_t* d_z,
+                    uint64_t z_cap, hipStream_t s) {
+    if (ctx->df_blocks == 0) return FG_OK;
+    const DfMembers m(ctx->d_df, n_members);
+    const DfBlocks b(ctx->d_df_blk, ctx->df_blocks);
+    FG_LAUNCH(ctx, fg_launch_deflate_pack(d_bytes, d_cuts, m.d_blk_first, n_members, ctx->df_blocks, ctx->d_df_slots, b.d_size, b.d_rel, m.d_crc, d_z_offsets,
+                                          d_z, z_cap, s));
+    return FG_OK;
+}
+
+// output.kafka_compression = "gzip" for a resident stream (output/kafka_output.rs:163-182 compresses what it sends; here on the GPU)
+int fg_deflate_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint8_t* d_z, uint64_t z_cap,
+                      uint64_t* d_z_offsets, uint64_t* total, void* stream) {
+    if (!ctx || !d_cuts || !d_z_offsets || !total || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (n_members >= 0x7FFFFFFFull * 64u) return FG_ERR_ARG;
+    *total = 0;
+    if (!fg_launch_deflate_count) return FG_ERR_UNSUPPORTED;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (n_members == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_z_offsets, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = fg_deflate_front(ctx, d_bytes, nbytes, d_cuts, n_members, d_z_offsets, total, s)) != FG_OK) return rc;
+    if (!d_z) return FG_OK;  // the sizing call
+    if (*total > z_cap) return FG_ERR_ENT_OVERFLOW;
+    if ((rc = fg_deflate_pack(ctx, d_bytes, d_cuts, n_members, d_z_offsets, d_z, z_cap, s)) != FG_OK) return rc;
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+
+int fg_set_output_compression(fg_ctx* ctx, const fg_compress_cfg* cfg) {
+    if (!ctx) return FG_ERR_ARG;
+    if (!cfg || cfg->codec == FG_COMP_NONE) {
+        ctx->compress = fg_compress_cfg{FG_COMP_NONE, 1u, 0u};
+        return FG_OK;
+    }
+    if (cfg->codec != FG_COMP_GZIP) return FG_ERR_ARG;
+    ctx->compress = *cfg;
+    return FG_OK;
+}
+int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out) {
+    if (!ctx || !out) return FG_ERR_ARG;
+    *out = ctx->last_comp;
+    return FG_OK;
+}
 
 int fg_decode_frames_device(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes,
                             const uint64_t* d_offsets, uint64_t n, const uint8_t* d_bad_utf8, const fg_tables* tables,

@@ -129,6 +129,25 @@ extern "C" uint64_t fg_capnp_frame_multi_scratch_bytes(uint64_t nbytes, uint64_t
 extern "C" int fg_launch_capnp_frame_multi(const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_seg_starts, uint64_t n_segs, uint8_t* scratch,
                                            uint64_t* d_offsets, uint8_t* d_kind, uint64_t cap, uint64_t* d_seg_first, uint64_t* d_seg_consumed,
                                            uint8_t* d_seg_stop, uint32_t** d_hdr_out, hipStream_t stream) __attribute__((weak));
+// the output compressor (fg_deflate.hip): count (the members' blocks, their scan), blocks (every block into its slot), sizes (the
+// members' sizes, their scan), pack; and the member cuts over an encoder's offsets.  (WEAK references, as fg_launch_syslen above: without
+// the kernels fg_deflate_device answers FG_ERR_UNSUPPORTED, and so do the transcode entry points of a ctx with compression set.  The
+// product library always has them: build.py checks the link.)
+extern "C" uint64_t fg_deflate_slot_bytes(uint64_t nbytes, uint64_t n_blocks) __attribute__((weak));
+extern "C" int fg_launch_deflate_count(const uint64_t* d_cuts, uint64_t n_members, uint64_t nbytes, uint32_t* d_nblk, uint64_t* d_sums,
+                                       uint64_t* d_blk_first, uint32_t* d_err, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_deflate_blocks(const uint8_t* d_bytes, const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members,
+                                        uint64_t n_blocks, uint8_t* d_slots, uint64_t slots_cap, uint32_t* d_blk_size, uint32_t* d_blk_crc,
+                                        uint32_t* d_ticket, int cus, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_deflate_sizes(const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members, const uint32_t* d_blk_size,
+                                       const uint32_t* d_blk_crc, uint32_t* d_blk_rel, uint32_t* d_member_crc, uint32_t* d_msize, uint64_t* d_sums,
+                                       uint64_t* d_z_offsets, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_deflate_pack(const uint8_t* d_bytes, const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members, uint64_t n_blocks,
+                                      const uint8_t* d_slots, const uint32_t* d_blk_size, const uint32_t* d_blk_rel, const uint32_t* d_member_crc,
+                                      const uint64_t* d_z_offsets, uint8_t* d_z, uint64_t z_cap, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_deflate_cuts(const uint64_t* d_off, uint64_t n, uint64_t coalesce, uint64_t member_bytes, uint32_t* d_flags, uint64_t* d_sums,
+                                      uint64_t* d_idx, uint64_t* d_member_first, uint64_t* d_cuts, uint64_t* d_n_members, hipStream_t stream)
+    __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
@@ -274,6 +293,24 @@ struct fg_ctx {
     uint64_t d_tmeta_cap = 0;
     uint8_t* h_tout = nullptr;   // pinned: messages | out_offsets | meta | enc_status
     uint64_t h_tout_cap = 0;
+    // the output compressor (fg_deflate_device, and behind the encoder of the transcode entry points: fg_set_output_compression)
+    fg_compress_cfg compress{FG_COMP_NONE, 1u, 0u};
+    fg_compressed last_comp{};       // fg_last_compressed
+    uint8_t* d_df = nullptr;         // per member: block counts | sizes | CRCs | the scans' sums | blk_first[n + 1]; the error and ticket words
+    uint64_t d_df_cap = 0;
+    uint8_t* d_df_blk = nullptr;     // per block: size | CRC | offset in its member
+    uint64_t d_df_blk_cap = 0;
+    uint8_t* d_df_slots = nullptr;   // the slots the blocks are compressed into
+    uint64_t d_df_slots_cap = 0;
+    uint64_t df_blocks = 0;          // ... how many of them the last front half found (a word it downloads into)
+    uint32_t df_err = 0;             // ... and whether it refused the cuts
+    uint8_t* d_df_cut = nullptr;     // the transcode entry points: start flags | sums | ranks | member_first[n + 2] | cuts[n + 2] | z_offsets[n + 2] | the count
+    uint64_t d_df_cut_cap = 0;
+    uint64_t df_members = 0;         // ... the members of the last cut (a word it is downloaded into)
+    uint8_t* d_zout = nullptr;       // ... the compressed stream
+    uint64_t d_zout_cap = 0;
+    uint8_t* h_zout = nullptr;       // ... pinned: the members | z_offsets | member_first
+    uint64_t h_zout_cap = 0;
 };
 
 namespace {
@@ -502,6 +539,13 @@ extern "C" int fg_udp_once_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t n
                                  uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, hipStream_t s);
 extern "C" int fg_udp_once_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
                                 uint64_t out_cap, uint8_t* d_drop, uint8_t* d_udp_status, hipStream_t s);
+// the two halves of fg_deflate_device (fg_capi.cpp), for the transcode tail, which sizes its buffer between them: the front compresses
+// every block into ctx-owned slots, leaves d_z_offsets[n_members + 1] and synchronises for *total; the pack fills d_z[0 .. z_cap)
+// (z_cap >= *total) and is not waited for.  n_members > 0.
+extern "C" int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint64_t* d_z_offsets,
+                                uint64_t* total, hipStream_t s);
+extern "C" int fg_deflate_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_cuts, uint64_t n_members, const uint64_t* d_z_offsets, uint8_t* d_z,
+                               uint64_t z_cap, hipStream_t s);
 // one fused launch on `stream` (fg_capi.cpp): *d_total = its result words in ctx scratch.  FG_ERR_UNSUPPORTED: nothing was launched
 extern "C" int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                                     uint64_t* d_offsets, uint64_t cap, const fg_tables* tables, uint64_t avg_line, void* stream,

@@ -1592,6 +1592,46 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     return FG_OK;
 }
 
+// The compression of a transcode (fg_set_output_compression): the `total` bytes of ctx->d_tout, whose n messages d_out_offsets bounds, are
+// cut into members by the ctx's policy and compressed behind the encoder; the members, their bounds and their first messages go to
+// ctx->h_zout and ctx->last_comp names them.  Synchronises for the member count and the sizes (the buffers are sized by them); the
+// downloads are queued on the ctx's stream and NOT waited for.  ctx->d_df_cut: start flags | sums | ranks[n + 1] | member_first[n + 2] |
+// cuts[n + 2] | z_offsets[n + 2] | the member count.  n > 0.
+static int compress_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, uint64_t n, uint64_t total) {
+    hipStream_t s = ctx->stream;
+    if (!fg_launch_deflate_cuts) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    const uint64_t flags_bytes = up(n * 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16), list = (n + 2) * 8;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_cut, &ctx->d_df_cut_cap, flags_bytes + sums_bytes + 4 * list + 16)) != FG_OK) return rc;
+    uint8_t* b = ctx->d_df_cut;
+    uint32_t* d_flags = (uint32_t*)b;
+    uint64_t* d_sums = (uint64_t*)(b += flags_bytes);
+    uint64_t* d_idx = (uint64_t*)(b += sums_bytes);
+    uint64_t* d_first = (uint64_t*)(b += list);
+    uint64_t* d_cuts = (uint64_t*)(b += list);
+    uint64_t* d_zoff = (uint64_t*)(b += list);
+    uint64_t* d_count = (uint64_t*)(b += list);
+    FG_LAUNCH(ctx, fg_launch_deflate_cuts(d_out_offsets, n, ctx->compress.coalesce, ctx->compress.member_bytes, d_flags, d_sums, d_idx, d_first, d_cuts,
+                                          d_count, s));
+    ctx->df_members = 0;
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_members, d_count, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    const uint64_t nm = ctx->df_members;
+    if (nm == 0 || nm > n) return FG_ERR_ARG;  // (never: message 0 starts a member, and no member is without a first message)
+    uint64_t zt = 0;
+    if ((rc = fg_deflate_front(ctx, ctx->d_tout, total, d_cuts, nm, d_zoff, &zt, s)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_zout, &ctx->d_zout_cap, zt + 16)) != FG_OK) return rc;
+    if ((rc = fg_deflate_pack(ctx, ctx->d_tout, d_cuts, nm, d_zoff, ctx->d_zout, ctx->d_zout_cap, s)) != FG_OK) return rc;
+    const uint64_t zb = up(zt, 256), lb = up((nm + 1) * 8, 256);
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_zout, &ctx->h_zout_cap, zb + 2 * lb)) != FG_OK) return rc;
+    uint8_t* h = ctx->h_zout;
+    if (zt) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_zout, zt, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h + zb, d_zoff, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h + zb + lb, d_first, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
+    ctx->last_comp = fg_compressed{h, zt, reinterpret_cast<const uint64_t*>(h + zb), reinterpret_cast<const uint64_t*>(h + zb + lb), nm, total};
+    return FG_OK;
+}
+
 // Steps 2 - 4 of a one-piece transcode, shared by fg_transcode_batch and fg_transcode_multi_batch -- nothing here depends on where the
 // frames came from: the n frames ctx->d_offsets names in d_src[0 .. src_bytes) (d_bad nonzero: a skipped row) are decoded into tables
 // that stay in HBM, encoded + framed from them (the output buffer grows to the batch: steady state is one count + one write; sized from
@@ -1621,15 +1661,21 @@ static int transcode_tail(fg_ctx* ctx, fg_format fmt, fg_framing dec_framing, co
                               d_enc_status, &total, FG_STREAM_OWN);
     }
     if (rc != FG_OK) return rc;
-    // 4. the messages, the fixed arrays behind them
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, up(total, 256), n, frames, res))) != FG_OK) return rc;
+    // 4. the messages, the fixed arrays behind them -- or, with compression set, the members in the messages' place (ctx->h_zout)
+    const bool gz = ctx->compress.codec == FG_COMP_GZIP;
+    const uint64_t plain = gz ? 0 : up(total, 256);
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, plain, n, frames, res))) != FG_OK) return rc;
     uint8_t* h = ctx->h_tout;
-    transcoded_arrays(h, up(total, 256), n, frames, res);
-    if (total) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
+    transcoded_arrays(h, plain, n, frames, res);
+    if (gz) {
+        if ((rc = compress_stage(ctx, d_out_offsets, n, total)) != FG_OK) return rc;
+    } else if (total) {
+        FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
+    }
     FG_HIP(ctx, hipMemcpyAsync((void*)res->out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync((void*)res->meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync((void*)res->enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s));
-    res->out = h;
+    res->out = gz ? nullptr : h;
     res->out_bytes = total;
     return FG_OK;
 }
@@ -1649,17 +1695,24 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
         return FG_ERR_ARG;  // a raw stream chunk is framed here; it does not come with offsets
     }
     *out = fg_transcoded{};
+    ctx->last_comp = fg_compressed{};
     if (framing != FG_FRAME_NONE && nbytes == 0) return FG_OK;
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
     int rc;
     // (from 16 MiB: the slices start at 4 MiB, so a 25 MB batch already has its first download in flight while the rest uploads --
     //  100 000 lines 1.65 vs 1.81 ms in one piece, 250 000 lines 3.35 vs 4.2; at 13 MB the two forms are level)
-    if (framing == FG_FRAME_NONE && nbytes >= (16ull << 20) && n >= 4096 && !(ctx->lo.flags & FG_LO_TRANSCODE_ONE_PIECE)) {
+    // (with compression set: one piece -- members are not cut across slices)
+    if (framing == FG_FRAME_NONE && nbytes >= (16ull << 20) && n >= 4096 && !(ctx->lo.flags & FG_LO_TRANSCODE_ONE_PIECE) &&
+        ctx->compress.codec == FG_COMP_NONE) {
         rc = transcode_sliced(ctx, fmt, ecfg, bytes, nbytes, offsets, n, out);
         if (rc != FG_ERR_UNSUPPORTED) return rc;
         *out = fg_transcoded{};
     }
+    // (with compression set every exit from here on waits for what it queued: the compress stage reads counts and sizes between its
+    //  steps, so an error may leave with work queued behind them.  Without compression this path's calls are what they were.)
+    DrainGuard drained(ctx);
+    drained.armed = ctx->compress.codec != FG_COMP_NONE;
     // 1. the chunk (and, for framed input, its offsets) to HBM
     if (!syslen) {
         if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;
@@ -1704,6 +1757,7 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     if (syslen) memcpy((void*)res.frame_offsets, ctx->h_off, (n + 1) * 8);  // (the frame starts in the caller's chunk, prefix included)
     else if (frames) FG_HIP(ctx, hipMemcpyAsync((void*)res.frame_offsets, ctx->d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
+    drained.armed = false;
     *out = res;
     return FG_OK;
 }
@@ -1722,6 +1776,7 @@ int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, con
                : syslen ? syslen_multi_args(fmt, nbytes, seg_starts, n_segs) : capnp_multi_args(nbytes, seg_starts, n_segs)) != FG_OK)
         return FG_ERR_ARG;
     *out = fg_transcoded_multi{};
+    ctx->last_comp = fg_compressed{};
     fg_tables none{};  // (SegBatch::upload clears the decode entries' tables)
     SegBatch b{ctx, n_segs, &none, &out->n, &out->seg_first, &out->seg_consumed, lines ? nullptr : &out->seg_stop, &out->slot_offsets, &out->slot_kind};
     DeviceGuard g(ctx->device);
@@ -1758,6 +1813,7 @@ int fg_udp_transcode_batch(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecfg
     if (max_inflated == 0) max_inflated = FG_UDP_DEFAULT_MAX_INFLATED;
     if (max_inflated > FG_UDP_MAX_MAX_INFLATED) return FG_ERR_ARG;
     *out = fg_transcoded{};
+    ctx->last_comp = fg_compressed{};
     *udp_status = nullptr;
     ctx->udp_last_spilled = 0;
     out->consumed = nbytes;

@@ -71,6 +71,7 @@ FG_WV uint32_t mbcnt(uint64_t m) {
 FG_WV uint32_t lds_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
 FG_WV uint32_t lds_xor(uint32_t* p, uint32_t v) { return atomicXor(p, v); }
 FG_WV uint32_t lds_min(uint32_t* p, uint32_t v) { return atomicMin(p, v); }
+FG_WV uint32_t lds_max(uint32_t* p, uint32_t v) { return atomicMax(p, v); }
 FG_WV uint32_t lds_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
 FG_WV unsigned long long glb_add(unsigned long long* p, unsigned long long v) { return atomicAdd(p, v); }
 FG_WV uint32_t ctz32(uint32_t x) { return (uint32_t)__builtin_ctz(x); }
@@ -106,6 +107,7 @@ FG_WV uint32_t mbcnt(uint64_t m) { return (uint32_t)__builtin_popcountll(m & ((1
 FG_WV uint32_t lds_or(uint32_t* p, uint32_t v) { uint32_t o = *p; *p = o | v; return o; }
 FG_WV uint32_t lds_xor(uint32_t* p, uint32_t v) { uint32_t o = *p; *p = o ^ v; return o; }
 FG_WV uint32_t lds_min(uint32_t* p, uint32_t v) { uint32_t o = *p; if (v < o) *p = v; return o; }
+FG_WV uint32_t lds_max(uint32_t* p, uint32_t v) { uint32_t o = *p; if (v > o) *p = v; return o; }
 FG_WV uint32_t lds_add(uint32_t* p, uint32_t v) { uint32_t o = *p; *p = o + v; return o; }
 FG_WV unsigned long long glb_add(unsigned long long* p, unsigned long long v) { unsigned long long o = *p; *p = o + v; return o; }
 FG_WV uint32_t ctz32(uint32_t x) { return (uint32_t)__builtin_ctz(x); }

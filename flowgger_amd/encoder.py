@@ -22,6 +22,18 @@ MERGERS = {None: L.FG_MERGE_NONE, "none": L.FG_MERGE_NONE, "noop": L.FG_MERGE_NO
            "line": L.FG_MERGE_LINE, "nul": L.FG_MERGE_NUL, "syslen": L.FG_MERGE_SYSLEN}
 
 
+def _compression(name: Optional[str]) -> int:
+    """output.kafka_compression (kafka_output.rs:163-182: lowercased; "none" / "gzip" / "snappy", anything else panics)"""
+    v = "none" if name is None else str(name).lower()
+    if v == "none":
+        return L.FG_COMP_NONE
+    if v == "gzip":
+        return L.FG_COMP_GZIP
+    if v == "snappy":
+        raise NotImplementedError("output.kafka_compression = \"snappy\" is not built")
+    raise ValueError("Unsupported compression method")
+
+
 class Encoder:
     """Base class; subclasses fix ``enc`` (fg_encoder)."""
     enc = -1
@@ -95,6 +107,33 @@ class Encoder:
         return d_off, d_st[:n]
 
     @staticmethod
+    def deflate_device(decoder, d_bytes, d_cuts, stream=None, out=None):
+        """fg_deflate_device: the resident bytes of `d_bytes` (uint8), cut into members by `d_cuts` (int64 / uint64 [n_members + 1],
+        ascending byte bounds), as gzip members back to back -- what follows fg_encode_device when output.kafka_compression = "gzip".
+        Returns (d_z uint8, d_z_offsets int64[n_members + 1]); an empty member produces no byte.  `out` = an optional preallocated
+        uint8 device tensor: one call when it is large enough; otherwise a sizing call comes first.  (`decoder` lends its ctx.)"""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        n = d_cuts.numel() - 1
+        d_zoff = torch.empty(n + 1, dtype=torch.int64, device=d_bytes.device)
+        total = C.c_uint64()
+        args = (decoder._ctx, d_bytes.data_ptr() if d_bytes.numel() else None, d_bytes.numel(), d_cuts.data_ptr(), n)
+        tail = (d_zoff.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
+        rc = L.FG_ERR_ENT_OVERFLOW
+        if out is not None:
+            rc = L.lib().fg_deflate_device(*args, out.data_ptr(), out.numel(), *tail)
+            if rc not in (L.FG_OK, L.FG_ERR_ENT_OVERFLOW):
+                L.check(rc, "fg_deflate_device")
+        if rc == L.FG_ERR_ENT_OVERFLOW:
+            if out is None:
+                L.check(L.lib().fg_deflate_device(*args, None, 0, *tail), "fg_deflate_device (size)")
+            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=d_bytes.device)
+            L.check(L.lib().fg_deflate_device(*args, out.data_ptr(), out.numel(), *tail), "fg_deflate_device")
+        return out[:int(total.value)], d_zoff
+
+    @staticmethod
     def error_string(status: int) -> Optional[str]:
         s = L.lib().fg_encode_error_string(status)
         return None if s is None else s.decode()
@@ -142,6 +181,23 @@ class Transcoded:
     def message(self, i: int) -> bytes:
         return self.out[int(self.out_offsets[i]):int(self.out_offsets[i + 1])].tobytes()
 
+    # With compression set on the Pipeline `out` is None and the stream comes as gzip members: z (uint8), z_offsets[n_members + 1],
+    # member_first[n_members + 1] (each member's first message index; the last entry = n), raw_bytes (the uncompressed total).
+    z = z_offsets = member_first = None
+    raw_bytes = 0
+
+    def members(self):
+        """the gzip members, one `bytes` each (every one inflates on its own)"""
+        z = self.z.tobytes()
+        return [z[int(self.z_offsets[k]):int(self.z_offsets[k + 1])] for k in range(len(self.z_offsets) - 1)]
+
+    def messages(self):
+        """the messages of a compressed result, inflated with Python's zlib and split by out_offsets (for callers and tests, not for speed)"""
+        import zlib
+
+        raw = b"".join(zlib.decompress(m, 31) for m in self.members() if m)
+        return [raw[int(self.out_offsets[i]):int(self.out_offsets[i + 1])] for i in range(self.n)]
+
 
 class TranscodedMulti(Transcoded):
     """Result of Pipeline.run_multi: Transcoded (one verdict per SLOT, no frame_offsets / consumed) plus the lists of the segmented
@@ -181,13 +237,55 @@ class Pipeline:
     ``handle_line`` (splitter/line_splitter.rs:44-54) does per line.  Only the encoded bytes and the per-line
     verdicts come back over PCIe; the decode tables stay in HBM."""
 
-    def __init__(self, decoder, encoder: Encoder):
+    def __init__(self, decoder, encoder: Encoder, compression: Optional[str] = None, coalesce: int = 1, member_bytes: int = 0):
+        """compression: None / "none", or "gzip" -- the encoded stream is deflated on the GPU and comes back as gzip members instead of
+        `.out` (fg_set_output_compression): one member per `coalesce` messages (the reference's output.kafka_coalesce), or, with
+        coalesce = 0, members of about `member_bytes` bytes cut at message boundaries (0 = one block of the compressor)."""
         self.decoder, self.encoder = decoder, encoder
+        self.compression = _compression(compression)
+        self.coalesce, self.member_bytes = int(coalesce), int(member_bytes)
+        if self.coalesce < 0 or self.member_bytes < 0:
+            raise ValueError("coalesce and member_bytes must not be negative")
+
+    @classmethod
+    def from_config(cls, decoder, encoder: Encoder, config: Optional[dict]):
+        """output.kafka_compression ("none" / "gzip", any case; "snappy" is not built) and output.kafka_coalesce (default 1), as
+        output/kafka_output.rs:163-182 reads them"""
+        out = (config or {}).get("output", {})
+        return cls(decoder, encoder, compression=str(out.get("kafka_compression", "none")), coalesce=int(out.get("kafka_coalesce", 1)))
+
+    def _set_compression(self):
+        # (the setting lives on the decoder's ctx, which Pipelines may share: set for every call)
+        cfg = L.fg_compress_cfg(self.compression, self.coalesce, self.member_bytes)
+        L.check(L.lib().fg_set_output_compression(self.decoder._ctx, C.byref(cfg)), "fg_set_output_compression")
+
+    def _compressed(self, t: Transcoded) -> Transcoded:
+        """with compression set: the members of the call that produced `t` in place of its `out`"""
+        import numpy as np
+
+        if self.compression == L.FG_COMP_NONE:
+            return t
+        c = L.fg_compressed()
+        L.check(L.lib().fg_last_compressed(self.decoder._ctx, C.byref(c)), "fg_last_compressed")
+        nm = int(c.n_members)
+
+        def view(ptr, count, dt):
+            if not count or not ptr:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        t.out = None
+        t.z = view(c.z, int(c.z_bytes), np.uint8)
+        t.z_offsets = view(c.z_offsets, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
+        t.member_first = view(c.member_first, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
+        t.raw_bytes = int(c.raw_bytes)
+        return t
 
     def _call(self, framing: int, data, nbytes: int, offsets, n: int, final: bool, now_ts: float) -> Transcoded:
         import numpy as np
 
         cfg, _keep = self.encoder._cfg_struct(now_ts)
+        self._set_compression()
         res = L.fg_transcoded()
         rc = L.lib().fg_transcode_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data, nbytes,
                                         None if offsets is None else offsets.ctypes.data, n, int(final), C.byref(res))
@@ -199,10 +297,10 @@ class Pipeline:
                 return np.zeros(0, dt)
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
 
-        return Transcoded(view(res.out, int(res.out_bytes), np.uint8),
-                          view(res.out_offsets, m + 1 if m else 0, np.uint64) if m else np.zeros(1, np.uint64),
-                          view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
-                          view(res.frame_offsets, m + 1, np.uint64) if (m and res.frame_offsets) else None, int(res.consumed))
+        return self._compressed(Transcoded(view(res.out, int(res.out_bytes), np.uint8),
+                                           view(res.out_offsets, m + 1 if m else 0, np.uint64) if m else np.zeros(1, np.uint64),
+                                           view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
+                                           view(res.frame_offsets, m + 1, np.uint64) if (m and res.frame_offsets) else None, int(res.consumed)))
 
     def run_packed(self, data, offsets, now_ts: float = 0.0) -> Transcoded:
         """framed lines (packed bytes + offsets[n + 1], as produced by pack_lines)"""
@@ -239,6 +337,7 @@ class Pipeline:
         K = len(starts) - 1
         final = None if seg_final is None else np.ascontiguousarray(seg_final, dtype=np.uint8)
         cfg, _keep = self.encoder._cfg_struct(now_ts)
+        self._set_compression()
         res = L.fg_transcoded_multi()
         rc = L.lib().fg_transcode_multi_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data if data.size else None,
                                               data.size, starts.ctypes.data, final.ctypes.data if final is not None and K else None, K,
@@ -252,11 +351,11 @@ class Pipeline:
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
 
         syslen = framing == L.FG_FRAME_SYSLEN
-        return TranscodedMulti(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, m + 1, np.uint64),
-                               view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
-                               view(res.slot_offsets, m if syslen else m + 1, np.uint64), view(res.slot_kind, m, np.uint8),
-                               view(res.seg_first, K + 1, np.uint64), view(res.seg_consumed, K, np.uint64),
-                               view(res.seg_stop, K, np.uint8) if res.seg_stop else None)
+        return self._compressed(TranscodedMulti(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, m + 1, np.uint64),
+                                                view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
+                                                view(res.slot_offsets, m if syslen else m + 1, np.uint64), view(res.slot_kind, m, np.uint8),
+                                                view(res.seg_first, K + 1, np.uint64), view(res.seg_consumed, K, np.uint64),
+                                                view(res.seg_stop, K, np.uint8) if res.seg_stop else None))
 
     def run_datagrams(self, datagrams, max_inflated=None, now_ts: float = 0.0) -> TranscodedUdp:
         """fg_udp_transcode_batch: the body of the UDP input's receive loop (input/udp_input.rs:66-143) for a batch -- a list of
@@ -276,6 +375,7 @@ class Pipeline:
         n = len(offsets) - 1
         nbytes = int(offsets[-1]) if n else 0
         cfg, _keep = self.encoder._cfg_struct(now_ts)
+        self._set_compression()
         res, ust = L.fg_transcoded(), C.c_void_p()
         rc = L.lib().fg_udp_transcode_batch(self.decoder._ctx, self.decoder.fmt, C.byref(cfg), data.ctypes.data if nbytes else None, nbytes,
                                             offsets.ctypes.data, n, int(max_inflated or 0), C.byref(res), C.byref(ust))
@@ -286,6 +386,7 @@ class Pipeline:
                 return np.zeros(0, dt)
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
 
-        return TranscodedUdp(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, n + 1, np.uint64) if n else np.zeros(1, np.uint64),
-                             view(res.meta, n, np.uint32), view(res.enc_status, n, np.uint8), int(res.consumed), view(ust, n, np.uint8),
-                             self.decoder.fmt)
+        return self._compressed(TranscodedUdp(view(res.out, int(res.out_bytes), np.uint8),
+                                              view(res.out_offsets, n + 1, np.uint64) if n else np.zeros(1, np.uint64),
+                                              view(res.meta, n, np.uint32), view(res.enc_status, n, np.uint8), int(res.consumed), view(ust, n, np.uint8),
+                                              self.decoder.fmt))

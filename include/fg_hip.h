@@ -861,6 +861,54 @@ int fg_transcode_multi_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, con
 int fg_udp_transcode_batch(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* cfg, const uint8_t* bytes, uint64_t nbytes,
                            const uint64_t* offsets, uint64_t n, uint64_t max_inflated, fg_transcoded* out, const uint8_t** udp_status);
 
+/* THE ENCODED STREAM DEFLATED ON THE GPU (additive under the same FG_ABI_VERSION): output.kafka_compression = "gzip" with
+ * output.kafka_coalesce (output/kafka_output.rs:163-182: every group of N messages is compressed), so that compressed bytes cross the
+ * link on the way out as they already may on the way in (fg_udp_unpack_device).
+ * The compressor takes a resident byte buffer and cuts[n_members + 1], ascending byte bounds: member m = bytes[cuts[m] .. cuts[m + 1]).
+ * Every non-empty member comes out as ONE complete gzip member (RFC 1952: the fixed header 1f 8b 08 00 00 00 00 00 00 ff, a raw deflate
+ * stream, CRC-32, ISIZE) that inflates on its own; an empty member produces no byte.  Members lie back to back, z_offsets[n_members + 1]
+ * their bounds.  Inside, a member is cut into independent blocks of fg_deflate_block_bytes() input bytes, each the cheaper of a
+ * fixed-Huffman block (greedy LZ77, matches of 4 .. 258 bytes inside the block) and a stored block; the output is a pure function
+ * of the input.  Dynamic Huffman codes are not produced.
+ *   fg_deflate_bound    bytes that always suffice for nbytes of input in n_members members
+ *   fg_deflate_device   d_z == NULL: a sizing call (*total and d_z_offsets are set).  *total > z_cap: FG_ERR_ENT_OVERFLOW and d_z is
+ *                       not written (the contract of fg_encode_device).  FG_ERR_ARG: cuts that do not ascend or go past nbytes, and a
+ *                       member of 0x7FE00000 bytes or more (which covers 4 GiB and more: a member's compressed size goes through a
+ *                       31-bit scan).  d_z_offsets: n_members + 1 entries.  Synchronises the stream.  FG_ERR_UNSUPPORTED: a build without the kernels. */
+typedef enum fg_compression { FG_COMP_NONE = 0, FG_COMP_GZIP = 1 } fg_compression;
+/* coalesce = C >= 1 (the reference's kafka_coalesce): member k = messages [k C, min((k + 1) C, n)) by index, dropped lines (empty messages)
+ * included.  coalesce = 0: members of about member_bytes bytes cut at message boundaries -- message i starts a member iff i == 0 or
+ * floor(out_offsets[i] / B) > floor(out_offsets[i - 1] / B), B = member_bytes (0: fg_deflate_block_bytes()); a message larger than B is a
+ * member of its own. */
+typedef struct fg_compress_cfg {
+    int codec; /* an fg_compression */
+    uint32_t coalesce;
+    uint32_t member_bytes;
+} fg_compress_cfg;
+uint32_t fg_deflate_block_bytes(void);
+uint64_t fg_deflate_bound(uint64_t nbytes, uint64_t n_members);
+int fg_deflate_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint8_t* d_z,
+                      uint64_t z_cap, uint64_t* d_z_offsets, uint64_t* total, void* stream);
+/* Compression of what fg_transcode_batch, fg_transcode_multi_batch and fg_udp_transcode_batch return (NULL or FG_COMP_NONE: off, the
+ * default, and then nothing changes by a byte).  With FG_COMP_GZIP those calls cut the encoded stream into members by cfg, compress it
+ * behind the encoder and do NOT copy the plain stream over the link: their `out` is NULL, out_bytes is the uncompressed total, and
+ * out_offsets, meta, enc_status and everything else are as without compression.  fg_last_compressed hands out what the last such call
+ * left (pinned host memory owned by ctx, valid until the next host-buffer call on it): z[0 .. z_bytes) the members back to back,
+ * z_offsets[n_members + 1] their bounds, member_first[n_members + 1] each member's first message index (the last entry = n),
+ * raw_bytes = out_bytes; all zero after a call without compression.  A member is the concatenation of its messages' encoded and framed
+ * bytes (the Kafka message-set wire format is not built here).  With compression set fg_transcode_batch runs in one piece: members are
+ * not cut across the slices of its pipelined form. */
+int fg_set_output_compression(fg_ctx* ctx, const fg_compress_cfg* cfg);
+typedef struct fg_compressed {
+    const uint8_t* z;
+    uint64_t z_bytes;
+    const uint64_t* z_offsets;
+    const uint64_t* member_first;
+    uint64_t n_members;
+    uint64_t raw_bytes;
+} fg_compressed;
+int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out);
+
 /* Host memory for the framer's batch buffers (bytes, offsets): PAGE-LOCKED, through a process-wide pool -- a freed block is kept
  * (up to idle_bytes in total) and handed to the next request it fits, so a framer per connection does not pin and unpin megabytes per
  * connect; the bytes pinned through this allocator are capped at total_bytes, beyond which a request gets PAGEABLE memory (every
