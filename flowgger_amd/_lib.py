@@ -116,6 +116,7 @@ class fg_transcoded_multi(C.Structure):
 
 
 FG_COMP_NONE, FG_COMP_GZIP = 0, 1  # fg_compression
+FG_DEFLATE_FIXED, FG_DEFLATE_DYNAMIC = 0, 1  # fg_deflate_mode
 
 
 class fg_compress_cfg(C.Structure):
@@ -241,6 +242,7 @@ def lib() -> C.CDLL:
     L.fg_deflate_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), vp]
     L.fg_set_output_compression.argtypes = [vp, C.POINTER(fg_compress_cfg)]
     L.fg_last_compressed.argtypes = [vp, C.POINTER(fg_compressed)]
+    L.fg_set_deflate_mode.argtypes = [vp, C.c_int]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

@@ -263,7 +263,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
                                                   "fg_launch_udp_pack", "fg_udp_stage_bytes")):
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without the launchers of fg_udp.hip")
-        if any(f" {f}\n" not in syms for f in ("fg_launch_deflate_count", "fg_launch_deflate_blocks", "fg_launch_deflate_sizes", "fg_launch_deflate_pack",
+        if any(f" {f}\n" not in syms for f in ("fg_launch_deflate_count", "fg_launch_deflate_blocks", "fg_launch_deflate_blocks_dyn", "fg_launch_deflate_sizes", "fg_launch_deflate_pack",
                                                  "fg_launch_deflate_cuts", "fg_deflate_slot_bytes", "fg_deflate_block_bytes", "fg_deflate_bound")):
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without the launchers of fg_deflate.hip")

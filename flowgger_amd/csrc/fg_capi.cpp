@@ -227,6 +227,7 @@ int fg_clone(const fg_ctx* src, fg_ctx** out) {
     ctx->device = src->device;
     ctx->lo = src->lo;
     ctx->compress = src->compress;
+    ctx->deflate_mode = src->deflate_mode;
     ctx->schema_names = src->schema_names;
     ctx->schema_types = src->schema_types;
     for (int k = 0; k < 4; ++k) {
@@ -741,6 +742,8 @@ int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const
     ctx->df_blocks = 0;
     if (!fg_launch_deflate_count || !fg_launch_deflate_blocks || !fg_launch_deflate_sizes || !fg_launch_deflate_pack || !fg_deflate_slot_bytes)
         return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    const bool dyn = ctx->deflate_mode == FG_DEFLATE_DYNAMIC;
+    if (dyn && !fg_launch_deflate_blocks_dyn) return FG_ERR_UNSUPPORTED;
     int rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_df, &ctx->d_df_cap, DfMembers::bytes(n_members))) != FG_OK) return rc;
     const DfMembers m(ctx->d_df, n_members);
@@ -759,8 +762,8 @@ int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const
     if ((rc = grow_dev(ctx, (void**)&ctx->d_df_blk, &ctx->d_df_blk_cap, DfBlocks::bytes(nb))) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_df_slots, &ctx->d_df_slots_cap, fg_deflate_slot_bytes(nbytes, nb))) != FG_OK) return rc;
     const DfBlocks b(ctx->d_df_blk, nb);
-    FG_LAUNCH(ctx, fg_launch_deflate_blocks(d_bytes, d_cuts, m.d_blk_first, n_members, nb, ctx->d_df_slots, ctx->d_df_slots_cap, b.d_size, b.d_crc,
-                                            m.d_ticket, fg::device_cus(), s));
+    FG_LAUNCH(ctx, (dyn ? fg_launch_deflate_blocks_dyn : fg_launch_deflate_blocks)(d_bytes, d_cuts, m.d_blk_first, n_members, nb, ctx->d_df_slots,
+                                                                                   ctx->d_df_slots_cap, b.d_size, b.d_crc, m.d_ticket, fg::device_cus(), s));
     FG_LAUNCH(ctx, fg_launch_deflate_sizes(d_cuts, m.d_blk_first, n_members, b.d_size, b.d_crc, b.d_rel, m.d_crc, m.d_msize, m.d_sums, d_z_offsets, s));
     FG_HIP(ctx, hipMemcpyAsync(total, d_z_offsets + n_members, 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
@@ -808,6 +811,11 @@ int fg_set_output_compression(fg_ctx* ctx, const fg_compress_cfg* cfg) {
     }
     if (cfg->codec != FG_COMP_GZIP) return FG_ERR_ARG;
     ctx->compress = *cfg;
+    return FG_OK;
+}
+int fg_set_deflate_mode(fg_ctx* ctx, int mode) {
+    if (!ctx || (mode != FG_DEFLATE_FIXED && mode != FG_DEFLATE_DYNAMIC)) return FG_ERR_ARG;
+    ctx->deflate_mode = mode;
     return FG_OK;
 }
 int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out) {

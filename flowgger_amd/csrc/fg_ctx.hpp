@@ -139,6 +139,9 @@ extern "C" int fg_launch_deflate_count(const uint64_t* d_cuts, uint64_t n_member
 extern "C" int fg_launch_deflate_blocks(const uint8_t* d_bytes, const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members,
                                         uint64_t n_blocks, uint8_t* d_slots, uint64_t slots_cap, uint32_t* d_blk_size, uint32_t* d_blk_crc,
                                         uint32_t* d_ticket, int cus, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_deflate_blocks_dyn(const uint8_t* d_bytes, const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members,
+                                            uint64_t n_blocks, uint8_t* d_slots, uint64_t slots_cap, uint32_t* d_blk_size, uint32_t* d_blk_crc,
+                                            uint32_t* d_ticket, int cus, hipStream_t stream) __attribute__((weak));  // FG_DEFLATE_DYNAMIC
 extern "C" int fg_launch_deflate_sizes(const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members, const uint32_t* d_blk_size,
                                        const uint32_t* d_blk_crc, uint32_t* d_blk_rel, uint32_t* d_member_crc, uint32_t* d_msize, uint64_t* d_sums,
                                        uint64_t* d_z_offsets, hipStream_t stream) __attribute__((weak));
@@ -295,6 +298,7 @@ struct fg_ctx {
     uint64_t h_tout_cap = 0;
     // the output compressor (fg_deflate_device, and behind the encoder of the transcode entry points: fg_set_output_compression)
     fg_compress_cfg compress{FG_COMP_NONE, 1u, 0u};
+    int deflate_mode = FG_DEFLATE_FIXED;  // fg_set_deflate_mode
     fg_compressed last_comp{};       // fg_last_compressed
     uint8_t* d_df = nullptr;         // per member: block counts | sizes | CRCs | the scans' sums | blk_first[n + 1]; the error and ticket words
     uint64_t d_df_cap = 0;

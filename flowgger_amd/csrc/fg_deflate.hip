@@ -6,6 +6,7 @@
 //   k_df_count    one lane per member: its cuts judged, its block count; per-64 sums          -> (scan) blk_first[n_members + 1]
 //   k_df_blocks   one wave per block, dealt by ticket (a wave's first block is its workgroup index, every further one is drawn from
 //                 one counter: blocks differ in cost by what they hold): fg::deflate::compress_block into the block's slot
+//   k_df_blocks_dyn   the same shell around compress_block_dyn (FG_DEFLATE_DYNAMIC): the block's histogram, its codes, the cheapest form
 //   k_df_finish   one lane per member: its blocks' offsets, its CRC-32, its size; per-64 sums  -> (scan) z_offsets[n_members + 1]
 //   k_df_pack     one wave per block: the slot (or, stored, the input) behind the member's header, the trailer behind the last
 // One 64-lane wave per workgroup with 16.3 KiB of LDS (the hash table, the bit buffer): nine workgroups share a CU's 160 KiB.  No loop
@@ -54,6 +55,35 @@ __global__ __launch_bounds__(64) void k_df_blocks(const uint8_t* __restrict__ by
         uint32_t size = (len + 5u) | kStored, crc = 0u;
         if (start < end && so + len + kSlotPad <= slots_cap)  // (always: blk_first is the scan of these cuts, the slots were sized by them)
             size = compress_block(bytes + start, len, last, (uint32_t*)(slots + so), s, &crc);
+        if (threadIdx.x == 0) {
+            blk_size[g] = size;
+            blk_crc[g] = crc;
+            s_ticket = atomicAdd(ticket, 1u);
+        }
+        __syncthreads();
+        g = (uint64_t)gridDim.x + s_ticket;
+        __syncthreads();
+    }
+}
+
+// k_df_blocks for FG_DEFLATE_DYNAMIC: the same shell around compress_block_dyn (17.6 KiB of LDS: nine workgroups still share a CU)
+__global__ __launch_bounds__(64) void k_df_blocks_dyn(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ cuts,
+                                                      const uint64_t* __restrict__ blk_first, uint64_t n_members, uint64_t n_blocks, uint8_t* slots,
+                                                      uint64_t slots_cap, uint32_t* __restrict__ blk_size, uint32_t* __restrict__ blk_crc,
+                                                      uint32_t* __restrict__ ticket) {
+    __shared__ uint32_t s_lds[kDynLdsWords];
+    __shared__ uint32_t s_ticket;
+    const DynLds s = dyn_lds_of(s_lds);
+    uint64_t g = blockIdx.x;
+    while (g < n_blocks) {  // (wave-uniform)
+        const uint64_t m = member_of(blk_first, n_members, g), j = g - blk_first[m];
+        const uint64_t start = cuts[m] + j * kBlock, end = cuts[m + 1];
+        const uint32_t len = (uint32_t)(end - start < kBlock ? end - start : kBlock);
+        const bool last = g + 1u == blk_first[m + 1];
+        const uint64_t so = slot_offset(start, g);
+        uint32_t size = (len + 5u) | kStored, crc = 0u, info;
+        if (start < end && so + len + kSlotPad <= slots_cap)  // (always, as in k_df_blocks)
+            size = compress_block_dyn(bytes + start, len, last, (uint32_t*)(slots + so), s, &crc, &info);
         if (threadIdx.x == 0) {
             blk_size[g] = size;
             blk_crc[g] = crc;
@@ -162,6 +192,19 @@ extern "C" int fg_launch_deflate_blocks(const uint8_t* d_bytes, const uint64_t* 
     if (rc != 0) return rc;
     hipLaunchKernelGGL(df::k_df_blocks, dim3(grid), dim3(64), 0, stream, d_bytes, d_cuts, d_blk_first, n_members, n_blocks, d_slots, slots_cap, d_blk_size,
                        d_blk_crc, d_ticket);
+    return (int)hipGetLastError();
+}
+// fg_launch_deflate_blocks for FG_DEFLATE_DYNAMIC (fg_set_deflate_mode): the same arguments, the same slots
+extern "C" int fg_launch_deflate_blocks_dyn(const uint8_t* d_bytes, const uint64_t* d_cuts, const uint64_t* d_blk_first, uint64_t n_members,
+                                            uint64_t n_blocks, uint8_t* d_slots, uint64_t slots_cap, uint32_t* d_blk_size, uint32_t* d_blk_crc,
+                                            uint32_t* d_ticket, int cus, hipStream_t stream) {
+    if (n_blocks > 0x7FFFFFFFull || ((uintptr_t)d_slots & 3u) != 0) return -1;
+    const uint64_t resident = (uint64_t)(cus > 0 ? cus : 1) * df::kWavesPerCu;
+    const uint32_t grid = (uint32_t)(n_blocks < resident ? n_blocks : resident);
+    int rc = (int)hipMemsetAsync(d_ticket, 0, 4, stream);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(df::k_df_blocks_dyn, dim3(grid), dim3(64), 0, stream, d_bytes, d_cuts, d_blk_first, n_members, n_blocks, d_slots, slots_cap,
+                       d_blk_size, d_blk_crc, d_ticket);
     return (int)hipGetLastError();
 }
 // the members' sizes: d_blk_rel n_blocks u32, d_member_crc / d_msize n_members u32, d_sums ceil(n_members / 64) u64 -> d_z_offsets[n_members + 1]

@@ -34,6 +34,15 @@ def _compression(name: Optional[str]) -> int:
     raise ValueError("Unsupported compression method")
 
 
+def _huffman(name: str) -> int:
+    """how the compressor codes a block (fg_set_deflate_mode): "fixed", the default, or "dynamic" (see Pipeline)"""
+    if name == "fixed":
+        return L.FG_DEFLATE_FIXED
+    if name == "dynamic":
+        return L.FG_DEFLATE_DYNAMIC
+    raise ValueError("huffman must be \"fixed\" or \"dynamic\"")
+
+
 class Encoder:
     """Base class; subclasses fix ``enc`` (fg_encoder)."""
     enc = -1
@@ -107,13 +116,16 @@ class Encoder:
         return d_off, d_st[:n]
 
     @staticmethod
-    def deflate_device(decoder, d_bytes, d_cuts, stream=None, out=None):
+    def deflate_device(decoder, d_bytes, d_cuts, stream=None, out=None, huffman="fixed"):
         """fg_deflate_device: the resident bytes of `d_bytes` (uint8), cut into members by `d_cuts` (int64 / uint64 [n_members + 1],
         ascending byte bounds), as gzip members back to back -- what follows fg_encode_device when output.kafka_compression = "gzip".
         Returns (d_z uint8, d_z_offsets int64[n_members + 1]); an empty member produces no byte.  `out` = an optional preallocated
-        uint8 device tensor: one call when it is large enough; otherwise a sizing call comes first.  (`decoder` lends its ctx.)"""
+        uint8 device tensor: one call when it is large enough; otherwise a sizing call comes first.  huffman = "fixed" or "dynamic":
+        fg_set_deflate_mode for this call (dynamic: every block the cheapest of stored, fixed and dynamic Huffman).  (`decoder` lends its
+        ctx, which keeps the mode: every call sets it.)"""
         import torch
 
+        L.check(L.lib().fg_set_deflate_mode(decoder._ctx, _huffman(huffman)), "fg_set_deflate_mode")
         if stream is None:
             stream = torch.cuda.current_stream(d_bytes.device)
         n = d_cuts.numel() - 1
@@ -237,11 +249,15 @@ class Pipeline:
     ``handle_line`` (splitter/line_splitter.rs:44-54) does per line.  Only the encoded bytes and the per-line
     verdicts come back over PCIe; the decode tables stay in HBM."""
 
-    def __init__(self, decoder, encoder: Encoder, compression: Optional[str] = None, coalesce: int = 1, member_bytes: int = 0):
+    def __init__(self, decoder, encoder: Encoder, compression: Optional[str] = None, coalesce: int = 1, member_bytes: int = 0,
+                 huffman: str = "fixed"):
         """compression: None / "none", or "gzip" -- the encoded stream is deflated on the GPU and comes back as gzip members instead of
         `.out` (fg_set_output_compression): one member per `coalesce` messages (the reference's output.kafka_coalesce), or, with
-        coalesce = 0, members of about `member_bytes` bytes cut at message boundaries (0 = one block of the compressor)."""
+        coalesce = 0, members of about `member_bytes` bytes cut at message boundaries (0 = one block of the compressor).  huffman:
+        "fixed" (the default) or "dynamic" -- dynamic Huffman blocks where they are smaller (fg_set_deflate_mode): fewer bytes, more
+        compressor time."""
         self.decoder, self.encoder = decoder, encoder
+        self.huffman = _huffman(huffman)
         self.compression = _compression(compression)
         self.coalesce, self.member_bytes = int(coalesce), int(member_bytes)
         if self.coalesce < 0 or self.member_bytes < 0:
@@ -258,6 +274,7 @@ class Pipeline:
         # (the setting lives on the decoder's ctx, which Pipelines may share: set for every call)
         cfg = L.fg_compress_cfg(self.compression, self.coalesce, self.member_bytes)
         L.check(L.lib().fg_set_output_compression(self.decoder._ctx, C.byref(cfg)), "fg_set_output_compression")
+        L.check(L.lib().fg_set_deflate_mode(self.decoder._ctx, self.huffman), "fg_set_deflate_mode")
 
     def _compressed(self, t: Transcoded) -> Transcoded:
         """with compression set: the members of the call that produced `t` in place of its `out`"""

@@ -6,7 +6,10 @@
   (b) fg_transcode_batch on --lines RFC5424 lines -> GELF from pinned host buffers: compression off in its pipelined (sliced) form, off in
       one piece (the path compression takes), gzip with member_bytes 65536; lines/s, and the bytes each form sends down the link
   (c) fg_measure_link's rates in the same process
-Usage: deflate_rate.py [--mib 256] [--lines 4000000] [--unique 100000]   -- prints one JSON line."""
+--huffman fixed | dynamic | both (the default): fg_set_deflate_mode for (a) and for the gzip leg of (b); with both, every figure of the
+compressor is taken in either mode in the same process, the fixed mode first (its keys are the ones this tool always had, the dynamic
+mode's carry "_dynamic").
+Usage: deflate_rate.py [--mib 256] [--lines 4000000] [--unique 100000] [--huffman both]   -- prints one JSON line."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +54,7 @@ def main():
     ap.add_argument("--unique", type=int, default=100_000)
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--huffman", choices=("fixed", "dynamic", "both"), default="both")
     a = ap.parse_args()
     import torch
 
@@ -64,6 +68,8 @@ def main():
     lines = synth.rfc5424_lines(a.unique, cfg=2)
     data, offsets = synth.pack(lines)
     res = {"block_bytes": int(lib.fg_deflate_block_bytes())}
+    modes = ("fixed", "dynamic") if a.huffman == "both" else (a.huffman,)
+    key = lambda name, mode: name + ("_dynamic" if mode == "dynamic" and a.huffman == "both" else "")
 
     # (a) the compressor alone
     t = Pipeline(dec, enc).run_packed(data, offsets)
@@ -77,18 +83,19 @@ def main():
     res["deflate_device"] = {"input_bytes": int(stream.size), "messages": len(off) - 1}
     for name, cuts in (("one_message", off), ("4KiB", cuts_by_bytes(off, 4096)), ("64KiB", cuts_by_bytes(off, 65536))):
         d_cuts = torch.from_numpy(cuts.astype(np.int64)).to(dev)
-        ms = []
-        for run in range(a.warmup + a.runs):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            d_z, d_zoff = Encoder.deflate_device(dec, d_bytes, d_cuts, out=d_out)
-            t1 = time.perf_counter()
-            if run >= a.warmup:
-                ms.append((t1 - t0) * 1e3)
-        s = spread(ms)
-        s.update({"members": len(cuts) - 1, "input_GBps": round(stream.size / (s["median_ms"] / 1e3) / 1e9, 3), "compressed_bytes": int(d_z.numel()),
-                  "ratio": round(int(d_z.numel()) / stream.size, 4)})
-        res["deflate_device"][name] = s
+        for mode in modes:
+            ms = []
+            for run in range(a.warmup + a.runs):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                d_z, d_zoff = Encoder.deflate_device(dec, d_bytes, d_cuts, out=d_out, huffman=mode)
+                t1 = time.perf_counter()
+                if run >= a.warmup:
+                    ms.append((t1 - t0) * 1e3)
+            s = spread(ms)
+            s.update({"members": len(cuts) - 1, "input_GBps": round(stream.size / (s["median_ms"] / 1e3) / 1e9, 3), "compressed_bytes": int(d_z.numel()),
+                      "ratio": round(int(d_z.numel()) / stream.size, 4)})
+            res["deflate_device"][key(name, mode)] = s
         del d_cuts
     del d_bytes, d_out, stream, off
 
@@ -111,8 +118,9 @@ def main():
         L.check(lib.fg_transcode_batch(dec._ctx, dec.fmt, L.FG_FRAME_NONE, C.byref(cfg), pb.ctypes.data, nbytes, po.ctypes.data, n, 1, C.byref(out)),
                 "fg_transcode_batch")
 
-    def leg(one_piece, gzip):
+    def leg(one_piece, gzip, mode="fixed"):
         dec.set_launch_opts(transcode_one_piece=one_piece)
+        L.check(lib.fg_set_deflate_mode(dec._ctx, L.FG_DEFLATE_DYNAMIC if mode == "dynamic" else L.FG_DEFLATE_FIXED), "fg_set_deflate_mode")
         cc = L.fg_compress_cfg(L.FG_COMP_GZIP if gzip else L.FG_COMP_NONE, 0, 65536)
         L.check(lib.fg_set_output_compression(dec._ctx, C.byref(cc)), "fg_set_output_compression")
         ms = []
@@ -134,7 +142,8 @@ def main():
     res["transcode_batch"] = {"lines": n, "input_bytes": nbytes}
     res["transcode_batch"]["off_sliced"] = leg(False, False)
     res["transcode_batch"]["off_one_piece"] = leg(True, False)
-    res["transcode_batch"]["gzip_64KiB_one_piece"] = leg(True, True)
+    for mode in modes:
+        res["transcode_batch"][key("gzip_64KiB_one_piece", mode)] = leg(True, True, mode)
     res["transcode_batch"]["off_sliced_again"] = leg(False, False)  # (the first leg once more: drift over the run)
     # (c) the link, same process
     g = (C.c_double * 3)()
