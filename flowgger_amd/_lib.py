@@ -117,6 +117,7 @@ class fg_transcoded_multi(C.Structure):
 
 FG_COMP_NONE, FG_COMP_GZIP = 0, 1  # fg_compression
 FG_DEFLATE_FIXED, FG_DEFLATE_DYNAMIC = 0, 1  # fg_deflate_mode
+FG_WIRE_RAW, FG_WIRE_KAFKA_V0 = 0, 1  # fg_output_wire
 
 
 class fg_compress_cfg(C.Structure):
@@ -243,6 +244,12 @@ def lib() -> C.CDLL:
     L.fg_set_output_compression.argtypes = [vp, C.POINTER(fg_compress_cfg)]
     L.fg_last_compressed.argtypes = [vp, C.POINTER(fg_compressed)]
     L.fg_set_deflate_mode.argtypes = [vp, C.c_int]
+    L.fg_set_output_wire.argtypes = [vp, C.c_int]
+    L.fg_kafka_message_overhead.restype = u32
+    L.fg_kafka_bound.argtypes = [u64, u64, u64]
+    L.fg_kafka_bound.restype = u64
+    L.fg_kafka_messageset_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, C.POINTER(u64), vp]
+    L.fg_kafka_wrap_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, C.POINTER(u64), vp]
     if L.fg_abi_version() != FG_ABI_VERSION:
         raise RuntimeError("libfg_hip.so ABI version mismatch")
     _lib = L

@@ -28,7 +28,7 @@ VARIANT_DEFS = os.environ.get("FG_BUILD_DEFS", "").split()
 LIB = ROOT / (f"libfg_hip_{VARIANT}.so" if VARIANT else "libfg_hip_prof.so" if PROF else "libfg_hip.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip", "fg_capnp.hip", "fg_syslen.hip", "fg_udp.hip", "fg_capnp_frame.hip", "fg_frame_multi.hip", "fg_syslen_multi.hip", "fg_capnp_frame_multi.hip", "fg_deflate.hip"]
+HIP_SOURCES = ["fg_rfc5424.hip", "fg_ltsv.hip", "fg_gelf.hip", "fg_frame.hip", "fg_encode.hip", "fg_rfc3164.hip", "fg_calib.hip", "fg_merge.hip", "fg_capnp.hip", "fg_syslen.hip", "fg_udp.hip", "fg_capnp_frame.hip", "fg_frame_multi.hip", "fg_syslen_multi.hip", "fg_capnp_frame_multi.hip", "fg_deflate.hip", "fg_kafka.hip"]
 HIP_HOST_SOURCES = ["fg_capi.cpp", "fg_host_pipeline.cpp"]  # host code that needs the HIP headers / launch syntax
 CXX_SOURCES = ["fg_materialize.cpp", "fg_gather.cpp"]
 
@@ -267,6 +267,10 @@ def build(force: bool = False, verbose: bool = False) -> Path:
                                                  "fg_launch_deflate_cuts", "fg_deflate_slot_bytes", "fg_deflate_block_bytes", "fg_deflate_bound")):
             LIB.unlink()
             raise RuntimeError("libfg_hip was linked without the launchers of fg_deflate.hip")
+        if any(f" {f}\n" not in syms for f in ("fg_launch_kafka_sizes", "fg_launch_kafka_write", "fg_launch_kafka_cuts", "fg_launch_kafka_wrap_sizes", "fg_launch_kafka_wrap",
+                                                 "fg_kafka_bound", "fg_kafka_message_overhead")):
+            LIB.unlink()
+            raise RuntimeError("libfg_hip was linked without the launchers of fg_kafka.hip")
     if not PROF and not VARIANT:
         _write_deps_manifest()
     return LIB

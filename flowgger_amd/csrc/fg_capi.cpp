@@ -228,6 +228,7 @@ int fg_clone(const fg_ctx* src, fg_ctx** out) {
     ctx->lo = src->lo;
     ctx->compress = src->compress;
     ctx->deflate_mode = src->deflate_mode;
+    ctx->wire = src->wire;
     ctx->schema_names = src->schema_names;
     ctx->schema_types = src->schema_types;
     for (int k = 0; k < 4; ++k) {
@@ -308,6 +309,8 @@ void fg_destroy(fg_ctx* ctx) {
     if (ctx->d_df_cut) (void)hipFree(ctx->d_df_cut);
     if (ctx->d_zout) (void)hipFree(ctx->d_zout);
     if (ctx->h_zout) (void)hipHostFree(ctx->h_zout);
+    for (uint8_t* p : {ctx->d_kf, ctx->d_kf_wrap, ctx->d_kf_crc, ctx->d_kf_set, ctx->d_kf_off, ctx->d_kf_w})
+        if (p) (void)hipFree(p);
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     for (hipEvent_t e : ctx->ev_slice) (void)hipEventDestroy(e);
@@ -805,11 +808,12 @@ int fg_deflate_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, cons
 
 int fg_set_output_compression(fg_ctx* ctx, const fg_compress_cfg* cfg) {
     if (!ctx) return FG_ERR_ARG;
-    if (!cfg || cfg->codec == FG_COMP_NONE) {
+    if (!cfg) {
         ctx->compress = fg_compress_cfg{FG_COMP_NONE, 1u, 0u};
         return FG_OK;
     }
-    if (cfg->codec != FG_COMP_GZIP) return FG_ERR_ARG;
+    // (FG_COMP_NONE keeps the member policy: nothing reads it but the message sets of FG_WIRE_KAFKA_V0, which are cut by it)
+    if (cfg->codec != FG_COMP_GZIP && cfg->codec != FG_COMP_NONE) return FG_ERR_ARG;
     ctx->compress = *cfg;
     return FG_OK;
 }
@@ -821,6 +825,132 @@ int fg_set_deflate_mode(fg_ctx* ctx, int mode) {
 int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out) {
     if (!ctx || !out) return FG_ERR_ARG;
     *out = ctx->last_comp;
+    return FG_OK;
+}
+
+// ---- Kafka v0 message sets (fg_kafka.hip).  ctx->d_kf holds, for n messages: sizes | the scan's sums | the error word; ctx->d_kf_wrap, for n
+// members: wrapper sizes | pieces | the sums of the two scans | piece_first[n + 1] | the error word; ctx->d_kf_crc a register per piece.
+namespace {
+struct KfWrap {
+    uint32_t *d_wsize, *d_npiece, *d_err;
+    uint64_t *d_sums, *d_piece_first;
+    static uint64_t bytes(uint64_t n) { return 2 * up(n * 4, 16) + up((n + 63) / 64 * 16, 16) + (n + 2) * 8 + 16; }
+    KfWrap(uint8_t* b, uint64_t n) {
+        d_wsize = (uint32_t*)b;
+        d_npiece = (uint32_t*)(b += up(n * 4, 16));
+        d_sums = (uint64_t*)(b += up(n * 4, 16));
+        d_piece_first = (uint64_t*)(b += up((n + 63) / 64 * 16, 16));
+        d_err = (uint32_t*)(b += (n + 2) * 8);
+    }
+};
+}  // namespace
+
+int fg_kafka_set_front(fg_ctx* ctx, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n, uint64_t nbytes, uint64_t* d_set_offsets, uint64_t* total,
+                       hipStream_t s) {
+    *total = 0;
+    if (!fg_launch_kafka_sizes || !fg_launch_kafka_write) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    const uint64_t sizes_bytes = up(n * 4 + 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16);
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf, &ctx->d_kf_cap, sizes_bytes + sums_bytes + 16)) != FG_OK) return rc;
+    uint32_t* d_sizes = (uint32_t*)ctx->d_kf;
+    uint64_t* d_sums = (uint64_t*)(ctx->d_kf + sizes_bytes);
+    uint32_t* d_err = (uint32_t*)(ctx->d_kf + sizes_bytes + sums_bytes);
+    ctx->kf_err = 0;
+    FG_LAUNCH(ctx, fg_launch_kafka_sizes(d_offsets, d_skip, n, nbytes, d_sizes, d_sums, d_set_offsets, d_err, s));
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->kf_err, d_err, 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(total, d_set_offsets + n, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->kf_err) {
+        *total = 0;
+        return FG_ERR_ARG;
+    }
+    return FG_OK;
+}
+int fg_kafka_set_write(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n, const uint64_t* d_set_offsets,
+                       uint8_t* d_set, uint64_t set_cap, hipStream_t s) {
+    FG_LAUNCH(ctx, fg_launch_kafka_write(d_bytes, d_offsets, d_skip, n, d_set_offsets, d_set, set_cap, fg::device_cus(), s));
+    return FG_OK;
+}
+int fg_kafka_messageset_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n,
+                               uint8_t* d_set, uint64_t set_cap, uint64_t* d_set_offsets, uint64_t* total, void* stream) {
+    if (!ctx || !d_offsets || !d_set_offsets || !total || (nbytes && !d_bytes)) return FG_ERR_ARG;
+    if (n >= 0x7FFFFFFFull * 64u) return FG_ERR_ARG;
+    *total = 0;
+    if (!fg_launch_kafka_sizes) return FG_ERR_UNSUPPORTED;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (n == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_set_offsets, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = fg_kafka_set_front(ctx, d_offsets, d_skip, n, nbytes, d_set_offsets, total, s)) != FG_OK) return rc;
+    if (!d_set) return FG_OK;  // the sizing call
+    if (*total > set_cap) return FG_ERR_ENT_OVERFLOW;
+    if (*total == 0) return FG_OK;  // (every row skipped)
+    if ((rc = fg_kafka_set_write(ctx, d_bytes, d_offsets, d_skip, n, d_set_offsets, d_set, set_cap, s)) != FG_OK) return rc;
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+
+int fg_kafka_wrap_front(fg_ctx* ctx, const uint64_t* d_z_offsets, uint64_t n_members, uint64_t* d_w_offsets, uint64_t* total, hipStream_t s) {
+    *total = 0;
+    ctx->kf_pieces = 0;
+    if (!fg_launch_kafka_wrap_sizes || !fg_launch_kafka_wrap) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_wrap, &ctx->d_kf_wrap_cap, KfWrap::bytes(n_members))) != FG_OK) return rc;
+    const KfWrap m(ctx->d_kf_wrap, n_members);
+    uint64_t np = 0;
+    ctx->kf_err = 0;
+    FG_LAUNCH(ctx, fg_launch_kafka_wrap_sizes(d_z_offsets, n_members, m.d_wsize, m.d_npiece, m.d_sums, d_w_offsets, m.d_piece_first, m.d_err, s));
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->kf_err, m.d_err, 4, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(&np, m.d_piece_first + n_members, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(total, d_w_offsets + n_members, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->kf_err) {
+        *total = 0;
+        return FG_ERR_ARG;
+    }
+    ctx->kf_pieces = np;
+    return FG_OK;
+}
+int fg_kafka_wrap_write(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_offsets, uint64_t n_members, const uint64_t* d_w_offsets, uint8_t* d_w,
+                        uint64_t w_cap, hipStream_t s) {
+    if (ctx->kf_pieces == 0) return FG_OK;  // (nothing but empty members)
+    int rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_crc, &ctx->d_kf_crc_cap, ctx->kf_pieces * 4)) != FG_OK) return rc;
+    const KfWrap m(ctx->d_kf_wrap, n_members);
+    FG_LAUNCH(ctx, fg_launch_kafka_wrap(d_z, d_z_offsets, m.d_piece_first, n_members, ctx->kf_pieces, d_w_offsets, d_w, w_cap, (uint32_t*)ctx->d_kf_crc,
+                                        fg::device_cus(), s));
+    return FG_OK;
+}
+int fg_kafka_wrap_device(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_offsets, uint64_t n_members, uint8_t* d_w, uint64_t w_cap,
+                         uint64_t* d_w_offsets, uint64_t* total, void* stream) {
+    if (!ctx || !d_z_offsets || !d_w_offsets || !total) return FG_ERR_ARG;
+    if (n_members >= 0x7FFFFFFFull * 64u) return FG_ERR_ARG;
+    *total = 0;
+    if (!fg_launch_kafka_wrap_sizes) return FG_ERR_UNSUPPORTED;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = stream_of(ctx, stream);
+    if (n_members == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_w_offsets, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    int rc;
+    if ((rc = fg_kafka_wrap_front(ctx, d_z_offsets, n_members, d_w_offsets, total, s)) != FG_OK) return rc;
+    if (!d_w) return FG_OK;  // the sizing call
+    if (*total > w_cap) return FG_ERR_ENT_OVERFLOW;
+    if (*total && !d_z) return FG_ERR_ARG;
+    if ((rc = fg_kafka_wrap_write(ctx, d_z, d_z_offsets, n_members, d_w_offsets, d_w, w_cap, s)) != FG_OK) return rc;
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return FG_OK;
+}
+
+int fg_set_output_wire(fg_ctx* ctx, int wire) {
+    if (!ctx || (wire != FG_WIRE_RAW && wire != FG_WIRE_KAFKA_V0)) return FG_ERR_ARG;
+    ctx->wire = wire;
     return FG_OK;
 }
 

@@ -151,6 +151,21 @@ extern "C" int fg_launch_deflate_pack(const uint8_t* d_bytes, const uint64_t* d_
 extern "C" int fg_launch_deflate_cuts(const uint64_t* d_off, uint64_t n, uint64_t coalesce, uint64_t member_bytes, uint32_t* d_flags, uint64_t* d_sums,
                                       uint64_t* d_idx, uint64_t* d_member_first, uint64_t* d_cuts, uint64_t* d_n_members, hipStream_t stream)
     __attribute__((weak));
+// Kafka v0 message sets (fg_kafka.hip): sizes (the messages' wire sizes, their scan), write (header, CRC-32 and value per message), cuts
+// (the members' bounds in the set); wrap_sizes (the wrappers' sizes and pieces, their scans), wrap (the members into their wrapper
+// messages).  (WEAK references, as the compressor's above: without the kernels fg_kafka_messageset_device and fg_kafka_wrap_device answer
+// FG_ERR_UNSUPPORTED, and so do the transcode entry points of a ctx with FG_WIRE_KAFKA_V0 set.  build.py checks the link.)
+extern "C" int fg_launch_kafka_sizes(const uint64_t* d_off, const uint8_t* d_skip, uint64_t n, uint64_t nbytes, uint32_t* d_sizes, uint64_t* d_sums,
+                                     uint64_t* d_set_offsets, uint32_t* d_err, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_kafka_write(const uint8_t* d_bytes, const uint64_t* d_off, const uint8_t* d_skip, uint64_t n, const uint64_t* d_set_offsets,
+                                     uint8_t* d_set, uint64_t set_cap, int cus, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_kafka_cuts(const uint64_t* d_set_offsets, const uint64_t* d_member_first, uint64_t n, uint64_t n_members, uint64_t* d_set_cuts,
+                                    hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_kafka_wrap_sizes(const uint64_t* d_z_offsets, uint64_t n_members, uint32_t* d_wsize, uint32_t* d_npiece, uint64_t* d_sums,
+                                          uint64_t* d_w_offsets, uint64_t* d_piece_first, uint32_t* d_err, hipStream_t stream) __attribute__((weak));
+extern "C" int fg_launch_kafka_wrap(const uint8_t* d_z, const uint64_t* d_z_offsets, const uint64_t* d_piece_first, uint64_t n_members, uint64_t n_pieces,
+                                    const uint64_t* d_w_offsets, uint8_t* d_w, uint64_t w_cap, uint32_t* d_piece_crc, int cus, hipStream_t stream)
+    __attribute__((weak));
 extern "C" uint64_t fg_frame_block_bytes(void);
 extern "C" uint64_t fg_frame_slice_align(void);
 extern "C" int fg_launch_frame_slice(const uint8_t* d_bytes, uint64_t nbytes, uint32_t delim, uint8_t* scratch, uint64_t* d_offsets,
@@ -315,6 +330,23 @@ struct fg_ctx {
     uint64_t d_zout_cap = 0;
     uint8_t* h_zout = nullptr;       // ... pinned: the members | z_offsets | member_first
     uint64_t h_zout_cap = 0;
+    // Kafka v0 message sets (fg_kafka_messageset_device, fg_kafka_wrap_device, and behind the encoder of the transcode entry points:
+    // fg_set_output_wire)
+    int wire = FG_WIRE_RAW;
+    uint8_t* d_kf = nullptr;         // per message: sizes | the scan's sums | the error word
+    uint64_t d_kf_cap = 0;
+    uint8_t* d_kf_wrap = nullptr;    // per member: wrapper sizes | pieces | the two scans' sums | piece_first[n + 1] | the error word
+    uint64_t d_kf_wrap_cap = 0;
+    uint8_t* d_kf_crc = nullptr;     // per piece: its CRC register
+    uint64_t d_kf_crc_cap = 0;
+    uint32_t kf_err = 0;             // whether the last front half refused its offsets (a word it downloads into)
+    uint64_t kf_pieces = 0;          // ... and the pieces the last wrap front found
+    uint8_t* d_kf_set = nullptr;     // the transcode entry points: the message set
+    uint64_t d_kf_set_cap = 0;
+    uint8_t* d_kf_off = nullptr;     // ... set_offsets[n + 1] | set_cuts[n + 2] | w_offsets[n + 2]
+    uint64_t d_kf_off_cap = 0;
+    uint8_t* d_kf_w = nullptr;       // ... the wrapper messages
+    uint64_t d_kf_w_cap = 0;
 };
 
 namespace {
@@ -550,6 +582,15 @@ extern "C" int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nb
                                 uint64_t* total, hipStream_t s);
 extern "C" int fg_deflate_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_cuts, uint64_t n_members, const uint64_t* d_z_offsets, uint8_t* d_z,
                                uint64_t z_cap, hipStream_t s);
+// ... and of fg_kafka_messageset_device / fg_kafka_wrap_device, in the same way: a front leaves the offsets and synchronises for *total,
+// the write / wrap fills the buffer (its capacity >= *total) and is not waited for.  n > 0, n_members > 0.
+extern "C" int fg_kafka_set_front(fg_ctx* ctx, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n, uint64_t nbytes, uint64_t* d_set_offsets,
+                                  uint64_t* total, hipStream_t s);
+extern "C" int fg_kafka_set_write(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n,
+                                  const uint64_t* d_set_offsets, uint8_t* d_set, uint64_t set_cap, hipStream_t s);
+extern "C" int fg_kafka_wrap_front(fg_ctx* ctx, const uint64_t* d_z_offsets, uint64_t n_members, uint64_t* d_w_offsets, uint64_t* total, hipStream_t s);
+extern "C" int fg_kafka_wrap_write(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_offsets, uint64_t n_members, const uint64_t* d_w_offsets, uint8_t* d_w,
+                                   uint64_t w_cap, hipStream_t s);
 // one fused launch on `stream` (fg_capi.cpp): *d_total = its result words in ctx scratch.  FG_ERR_UNSUPPORTED: nothing was launched
 extern "C" int fg_frame_decode_impl(fg_ctx* ctx, fg_format fmt, fg_framing framing, const uint8_t* d_bytes, uint64_t nbytes, int final,
                                     uint64_t* d_offsets, uint64_t cap, const fg_tables* tables, uint64_t avg_line, void* stream,

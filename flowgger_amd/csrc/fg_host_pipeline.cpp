@@ -1632,6 +1632,66 @@ static int compress_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, uint64_t n
     return FG_OK;
 }
 
+// The same stage with FG_WIRE_KAFKA_V0 set (fg_set_output_wire): the members are cut by the same rule over the same offsets, the message
+// set is built from ctx->d_tout with d_enc_status as the skipped rows, and the members' byte cuts are set_offsets[member_first[k]].
+// FG_COMP_GZIP: the set is deflated member by member and every non-empty member wrapped; FG_COMP_NONE: the set itself goes to ctx->h_zout,
+// the cuts as its z_offsets.  ctx->d_df_cut as above (its cuts[] are the plain stream's and unused); ctx->d_kf_off: set_offsets[n + 1] |
+// set_cuts[n + 2] | w_offsets[n + 2].  Synchronises where compress_stage does and for the set's and the wrappers' sizes.  n > 0.
+static int kafka_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, const uint8_t* d_enc_status, uint64_t n, uint64_t total) {
+    hipStream_t s = ctx->stream;
+    if (!fg_launch_deflate_cuts || !fg_launch_kafka_cuts) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    int rc;
+    const uint64_t flags_bytes = up(n * 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16), list = (n + 2) * 8;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_cut, &ctx->d_df_cut_cap, flags_bytes + sums_bytes + 4 * list + 16)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_off, &ctx->d_kf_off_cap, 3 * list)) != FG_OK) return rc;
+    uint8_t* b = ctx->d_df_cut;
+    uint32_t* d_flags = (uint32_t*)b;
+    uint64_t* d_sums = (uint64_t*)(b += flags_bytes);
+    uint64_t* d_idx = (uint64_t*)(b += sums_bytes);
+    uint64_t* d_first = (uint64_t*)(b += list);
+    uint64_t* d_cuts = (uint64_t*)(b += list);
+    uint64_t* d_zoff = (uint64_t*)(b += list);
+    uint64_t* d_count = (uint64_t*)(b += list);
+    uint64_t* d_set_off = (uint64_t*)ctx->d_kf_off;
+    uint64_t* d_set_cuts = (uint64_t*)(ctx->d_kf_off + list);
+    uint64_t* d_woff = (uint64_t*)(ctx->d_kf_off + 2 * list);
+    FG_LAUNCH(ctx, fg_launch_deflate_cuts(d_out_offsets, n, ctx->compress.coalesce, ctx->compress.member_bytes, d_flags, d_sums, d_idx, d_first, d_cuts,
+                                          d_count, s));
+    ctx->df_members = 0;
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_members, d_count, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    const uint64_t nm = ctx->df_members;
+    if (nm == 0 || nm > n) return FG_ERR_ARG;  // (never, as in compress_stage)
+    // the set, and the members' bounds in it
+    uint64_t st = 0;
+    if ((rc = fg_kafka_set_front(ctx, d_out_offsets, d_enc_status, n, total, d_set_off, &st, s)) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_set, &ctx->d_kf_set_cap, st + 16)) != FG_OK) return rc;
+    if (st && (rc = fg_kafka_set_write(ctx, ctx->d_tout, d_out_offsets, d_enc_status, n, d_set_off, ctx->d_kf_set, ctx->d_kf_set_cap, s)) != FG_OK) return rc;
+    FG_LAUNCH(ctx, fg_launch_kafka_cuts(d_set_off, d_first, n, nm, d_set_cuts, s));
+    const uint8_t* d_wire = ctx->d_kf_set;
+    const uint64_t* d_wire_off = d_set_cuts;
+    uint64_t wt = st;
+    if (ctx->compress.codec == FG_COMP_GZIP) {
+        uint64_t zt = 0;
+        if ((rc = fg_deflate_front(ctx, ctx->d_kf_set, st, d_set_cuts, nm, d_zoff, &zt, s)) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_zout, &ctx->d_zout_cap, zt + 16)) != FG_OK) return rc;
+        if ((rc = fg_deflate_pack(ctx, ctx->d_kf_set, d_set_cuts, nm, d_zoff, ctx->d_zout, ctx->d_zout_cap, s)) != FG_OK) return rc;
+        if ((rc = fg_kafka_wrap_front(ctx, d_zoff, nm, d_woff, &wt, s)) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_w, &ctx->d_kf_w_cap, wt + 16)) != FG_OK) return rc;
+        if ((rc = fg_kafka_wrap_write(ctx, ctx->d_zout, d_zoff, nm, d_woff, ctx->d_kf_w, ctx->d_kf_w_cap, s)) != FG_OK) return rc;
+        d_wire = ctx->d_kf_w;
+        d_wire_off = d_woff;
+    }
+    const uint64_t zb = up(wt, 256), lb = up((nm + 1) * 8, 256);
+    if ((rc = grow_pinned(ctx, (void**)&ctx->h_zout, &ctx->h_zout_cap, zb + 2 * lb)) != FG_OK) return rc;
+    uint8_t* h = ctx->h_zout;
+    if (wt) FG_HIP(ctx, hipMemcpyAsync(h, d_wire, wt, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h + zb, d_wire_off, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h + zb + lb, d_first, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
+    ctx->last_comp = fg_compressed{h, wt, reinterpret_cast<const uint64_t*>(h + zb), reinterpret_cast<const uint64_t*>(h + zb + lb), nm, total};
+    return FG_OK;
+}
+
 // Steps 2 - 4 of a one-piece transcode, shared by fg_transcode_batch and fg_transcode_multi_batch -- nothing here depends on where the
 // frames came from: the n frames ctx->d_offsets names in d_src[0 .. src_bytes) (d_bad nonzero: a skipped row) are decoded into tables
 // that stay in HBM, encoded + framed from them (the output buffer grows to the batch: steady state is one count + one write; sized from
@@ -1662,12 +1722,16 @@ static int transcode_tail(fg_ctx* ctx, fg_format fmt, fg_framing dec_framing, co
     }
     if (rc != FG_OK) return rc;
     // 4. the messages, the fixed arrays behind them -- or, with compression set, the members in the messages' place (ctx->h_zout)
-    const bool gz = ctx->compress.codec == FG_COMP_GZIP;
+    //    (with FG_WIRE_KAFKA_V0: the message set or its wrapped members there, whatever the codec)
+    const bool kafka = ctx->wire == FG_WIRE_KAFKA_V0;
+    const bool gz = ctx->compress.codec == FG_COMP_GZIP || kafka;
     const uint64_t plain = gz ? 0 : up(total, 256);
     if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, plain, n, frames, res))) != FG_OK) return rc;
     uint8_t* h = ctx->h_tout;
     transcoded_arrays(h, plain, n, frames, res);
-    if (gz) {
+    if (kafka) {
+        if ((rc = kafka_stage(ctx, d_out_offsets, d_enc_status, n, total)) != FG_OK) return rc;
+    } else if (gz) {
         if ((rc = compress_stage(ctx, d_out_offsets, n, total)) != FG_OK) return rc;
     } else if (total) {
         FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
@@ -1704,7 +1768,7 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     //  100 000 lines 1.65 vs 1.81 ms in one piece, 250 000 lines 3.35 vs 4.2; at 13 MB the two forms are level)
     // (with compression set: one piece -- members are not cut across slices)
     if (framing == FG_FRAME_NONE && nbytes >= (16ull << 20) && n >= 4096 && !(ctx->lo.flags & FG_LO_TRANSCODE_ONE_PIECE) &&
-        ctx->compress.codec == FG_COMP_NONE) {
+        ctx->compress.codec == FG_COMP_NONE && ctx->wire == FG_WIRE_RAW) {
         rc = transcode_sliced(ctx, fmt, ecfg, bytes, nbytes, offsets, n, out);
         if (rc != FG_ERR_UNSUPPORTED) return rc;
         *out = fg_transcoded{};
@@ -1712,7 +1776,7 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
     // (with compression set every exit from here on waits for what it queued: the compress stage reads counts and sizes between its
     //  steps, so an error may leave with work queued behind them.  Without compression this path's calls are what they were.)
     DrainGuard drained(ctx);
-    drained.armed = ctx->compress.codec != FG_COMP_NONE;
+    drained.armed = ctx->compress.codec != FG_COMP_NONE || ctx->wire != FG_WIRE_RAW;
     // 1. the chunk (and, for framed input, its offsets) to HBM
     if (!syslen) {
         if ((rc = grow_dev(ctx, (void**)&ctx->d_bytes, &ctx->d_bytes_cap, up(nbytes, 16) + 16)) != FG_OK) return rc;

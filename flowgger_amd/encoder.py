@@ -34,6 +34,35 @@ def _compression(name: Optional[str]) -> int:
     raise ValueError("Unsupported compression method")
 
 
+def _wire(name: Optional[str]) -> int:
+    """what the transcode calls hand out (fg_set_output_wire): "raw", the default, or "kafka" -- v0 message sets (see Pipeline)"""
+    if name is None or name == "raw":
+        return L.FG_WIRE_RAW
+    if name == "kafka":
+        return L.FG_WIRE_KAFKA_V0
+    raise ValueError("wire must be \"raw\" or \"kafka\"")
+
+
+def kafka_parse(buf: bytes):
+    """a Kafka v0 message set -> [(crc_ok, attributes, value)] (null keys; for callers and tests, not for speed).  The offset field is
+    not judged: a v0 producer may send anything there, the broker assigns it."""
+    import struct
+    import zlib
+
+    out, at, over = [], 0, int(L.lib().fg_kafka_message_overhead())
+    while at < len(buf):
+        if len(buf) - at < over:
+            raise ValueError("a message set ends inside a header")
+        size, crc = struct.unpack_from(">iI", buf, at + 8)
+        magic, attributes, keylen, vlen = struct.unpack_from(">bbii", buf, at + 16)
+        end = at + over + vlen
+        if magic != 0 or keylen != -1 or vlen < 0 or size != 14 + vlen or end > len(buf):
+            raise ValueError(f"not a v0 message with a null key at byte {at}")
+        out.append((zlib.crc32(buf[at + 16:end]) == crc, attributes, buf[at + over:end]))
+        at = end
+    return out
+
+
 def _huffman(name: str) -> int:
     """how the compressor codes a block (fg_set_deflate_mode): "fixed", the default, or "dynamic" (see Pipeline)"""
     if name == "fixed":
@@ -146,6 +175,57 @@ class Encoder:
         return out[:int(total.value)], d_zoff
 
     @staticmethod
+    def _sized_call(fn, what, args, tail, total, out, device):
+        """the contract of the resident calls: `out` when it is large enough, else a sizing call and a buffer of exactly the total"""
+        import torch
+
+        rc = L.FG_ERR_ENT_OVERFLOW
+        if out is not None:
+            rc = fn(*args, out.data_ptr(), out.numel(), *tail)
+            if rc not in (L.FG_OK, L.FG_ERR_ENT_OVERFLOW):
+                L.check(rc, what)
+        if rc == L.FG_ERR_ENT_OVERFLOW:
+            if out is None:
+                L.check(fn(*args, None, 0, *tail), what + " (size)")
+            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=device)
+            L.check(fn(*args, out.data_ptr(), out.numel(), *tail), what)
+        return out[:int(total.value)]
+
+    @staticmethod
+    def kafka_messageset_device(decoder, d_bytes, d_offsets, d_skip=None, stream=None, out=None):
+        """fg_kafka_messageset_device: the resident values d_bytes[d_offsets[i] : d_offsets[i + 1]] (what encode_device returned) as a Kafka
+        v0 message set -- every value behind its 26-byte header with its CRC-32, null keys.  d_skip: None, or uint8[n], nonzero = the row
+        is not in the set (encode_device's status).  Returns (d_set uint8, d_set_offsets int64[n + 1]: where each row's message lies,
+        an empty range for a skipped row).  `out` as in deflate_device.  (`decoder` lends its ctx.)"""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_bytes.device)
+        n = d_offsets.numel() - 1
+        d_soff = torch.empty(n + 1, dtype=torch.int64, device=d_bytes.device)
+        total = C.c_uint64()
+        args = (decoder._ctx, d_bytes.data_ptr() if d_bytes.numel() else None, d_bytes.numel(), d_offsets.data_ptr(),
+                None if d_skip is None else d_skip.data_ptr(), n)
+        tail = (d_soff.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
+        return Encoder._sized_call(L.lib().fg_kafka_messageset_device, "fg_kafka_messageset_device", args, tail, total, out, d_bytes.device), d_soff
+
+    @staticmethod
+    def kafka_wrap_device(decoder, d_z, d_z_offsets, stream=None, out=None):
+        """fg_kafka_wrap_device: the gzip members d_z[d_z_offsets[m] : d_z_offsets[m + 1]] (what deflate_device made of a message set)
+        each inside its wrapper message (attributes = 1, a CRC-32 over the compressed bytes); an empty member produces no byte.  Returns
+        (d_w uint8, d_w_offsets int64[n_members + 1])."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(d_z.device)
+        nm = d_z_offsets.numel() - 1
+        d_woff = torch.empty(nm + 1, dtype=torch.int64, device=d_z.device)
+        total = C.c_uint64()
+        args = (decoder._ctx, d_z.data_ptr() if d_z.numel() else None, d_z_offsets.data_ptr(), nm)
+        tail = (d_woff.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
+        return Encoder._sized_call(L.lib().fg_kafka_wrap_device, "fg_kafka_wrap_device", args, tail, total, out, d_z.device), d_woff
+
+    @staticmethod
     def error_string(status: int) -> Optional[str]:
         s = L.lib().fg_encode_error_string(status)
         return None if s is None else s.decode()
@@ -195,18 +275,42 @@ class Transcoded:
 
     # With compression set on the Pipeline `out` is None and the stream comes as gzip members: z (uint8), z_offsets[n_members + 1],
     # member_first[n_members + 1] (each member's first message index; the last entry = n), raw_bytes (the uncompressed total).
+    # With wire = "kafka" on the Pipeline (.wire says so) a member is Kafka v0 wire bytes: a plain message set without compression, one
+    # gzip wrapper message around the inner set with it; rows with enc_status != 0 are in no set.
     z = z_offsets = member_first = None
     raw_bytes = 0
+    wire = "raw"
 
     def members(self):
-        """the gzip members, one `bytes` each (every one inflates on its own)"""
+        """the members, one `bytes` each: gzip members (every one inflates on its own), or, with wire = "kafka", the wire bytes of each"""
         z = self.z.tobytes()
         return [z[int(self.z_offsets[k]):int(self.z_offsets[k + 1])] for k in range(len(self.z_offsets) - 1)]
 
-    def messages(self):
-        """the messages of a compressed result, inflated with Python's zlib and split by out_offsets (for callers and tests, not for speed)"""
+    def kafka_records(self):
+        """wire = "kafka": per member, the list of (crc_ok, value) of its inner messages -- the plain set parsed, or the wrapper parsed,
+        its value inflated with Python's zlib and the inner set parsed (crc_ok then covers both CRCs).  For callers and tests."""
         import zlib
 
+        if self.wire != "kafka":
+            raise ValueError("not a wire = \"kafka\" result")
+        out = []
+        for m in self.members():
+            msgs = kafka_parse(m)
+            if len(msgs) == 1 and msgs[0][1] == 1:
+                ok = msgs[0][0]
+                out.append([(ok and iok, v) for iok, _, v in kafka_parse(zlib.decompress(msgs[0][2], 31))])
+            else:
+                out.append([(iok, v) for iok, _, v in msgs])
+        return out
+
+    def messages(self):
+        """the messages of a compressed or wire result, inflated with Python's zlib (for callers and tests, not for speed): split by
+        out_offsets, or, with wire = "kafka", the values of the sets' messages in row order, b"" for a row that is in no set"""
+        import zlib
+
+        if self.wire == "kafka":
+            vals = iter(v for member in self.kafka_records() for _, v in member)
+            return [b"" if self.enc_status[i] else next(vals) for i in range(self.n)]
         raw = b"".join(zlib.decompress(m, 31) for m in self.members() if m)
         return [raw[int(self.out_offsets[i]):int(self.out_offsets[i + 1])] for i in range(self.n)]
 
@@ -250,13 +354,17 @@ class Pipeline:
     verdicts come back over PCIe; the decode tables stay in HBM."""
 
     def __init__(self, decoder, encoder: Encoder, compression: Optional[str] = None, coalesce: int = 1, member_bytes: int = 0,
-                 huffman: str = "fixed"):
+                 huffman: str = "fixed", wire: str = "raw"):
         """compression: None / "none", or "gzip" -- the encoded stream is deflated on the GPU and comes back as gzip members instead of
         `.out` (fg_set_output_compression): one member per `coalesce` messages (the reference's output.kafka_coalesce), or, with
         coalesce = 0, members of about `member_bytes` bytes cut at message boundaries (0 = one block of the compressor).  huffman:
         "fixed" (the default) or "dynamic" -- dynamic Huffman blocks where they are smaller (fg_set_deflate_mode): fewer bytes, more
-        compressor time."""
+        compressor time.  wire: "raw" (the default) or "kafka" -- the messages come back as Kafka v0 message sets (fg_set_output_wire)
+        instead of `.out`, one set per member of the policy above: plain, or with compression each deflated and inside its wrapper
+        message, which is what a broker takes."""
         self.decoder, self.encoder = decoder, encoder
+        self.wire = _wire(wire)
+        self._merger = None  # from_config with the Kafka output: the FG_MERGE_* to encode with in place of the encoder's own
         self.huffman = _huffman(huffman)
         self.compression = _compression(compression)
         self.coalesce, self.member_bytes = int(coalesce), int(member_bytes)
@@ -268,20 +376,40 @@ class Pipeline:
         """output.kafka_compression ("none" / "gzip", any case; "snappy" is not built) and output.kafka_coalesce (default 1), as
         output/kafka_output.rs:163-182 reads them"""
         out = (config or {}).get("output", {})
-        return cls(decoder, encoder, compression=str(out.get("kafka_compression", "none")), coalesce=int(out.get("kafka_coalesce", 1)))
+        kw = dict(compression=str(out.get("kafka_compression", "none")), coalesce=int(out.get("kafka_coalesce", 1)))
+        if out.get("type") == "kafka":
+            # output.type = "kafka": v0 message sets, and the encoder's merger is left out of the values -- on the pipeline's own copy of
+            # the cfg, the caller's Encoder stays as it is (kafka_output.rs:199-202 ignores output.framing and says so)
+            import sys
+
+            if encoder.merger != L.FG_MERGE_NONE:
+                print("Output framing is ignored with the Kafka output", file=sys.stderr)
+            kw.update(wire="kafka")
+        p = cls(decoder, encoder, **kw)
+        if p.wire == L.FG_WIRE_KAFKA_V0:
+            p._merger = L.FG_MERGE_NONE
+        return p
+
+    def _encode_cfg(self, now_ts: float):
+        cfg, keep = self.encoder._cfg_struct(now_ts)
+        if self._merger is not None:
+            cfg.merger = self._merger
+        return cfg, keep
 
     def _set_compression(self):
         # (the setting lives on the decoder's ctx, which Pipelines may share: set for every call)
         cfg = L.fg_compress_cfg(self.compression, self.coalesce, self.member_bytes)
         L.check(L.lib().fg_set_output_compression(self.decoder._ctx, C.byref(cfg)), "fg_set_output_compression")
         L.check(L.lib().fg_set_deflate_mode(self.decoder._ctx, self.huffman), "fg_set_deflate_mode")
+        L.check(L.lib().fg_set_output_wire(self.decoder._ctx, self.wire), "fg_set_output_wire")
 
     def _compressed(self, t: Transcoded) -> Transcoded:
         """with compression set: the members of the call that produced `t` in place of its `out`"""
         import numpy as np
 
-        if self.compression == L.FG_COMP_NONE:
+        if self.compression == L.FG_COMP_NONE and self.wire == L.FG_WIRE_RAW:
             return t
+        t.wire = "kafka" if self.wire == L.FG_WIRE_KAFKA_V0 else "raw"
         c = L.fg_compressed()
         L.check(L.lib().fg_last_compressed(self.decoder._ctx, C.byref(c)), "fg_last_compressed")
         nm = int(c.n_members)
@@ -301,7 +429,7 @@ class Pipeline:
     def _call(self, framing: int, data, nbytes: int, offsets, n: int, final: bool, now_ts: float) -> Transcoded:
         import numpy as np
 
-        cfg, _keep = self.encoder._cfg_struct(now_ts)
+        cfg, _keep = self._encode_cfg(now_ts)
         self._set_compression()
         res = L.fg_transcoded()
         rc = L.lib().fg_transcode_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data, nbytes,
@@ -353,7 +481,7 @@ class Pipeline:
         starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
         K = len(starts) - 1
         final = None if seg_final is None else np.ascontiguousarray(seg_final, dtype=np.uint8)
-        cfg, _keep = self.encoder._cfg_struct(now_ts)
+        cfg, _keep = self._encode_cfg(now_ts)
         self._set_compression()
         res = L.fg_transcoded_multi()
         rc = L.lib().fg_transcode_multi_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data if data.size else None,
@@ -391,7 +519,7 @@ class Pipeline:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = len(offsets) - 1
         nbytes = int(offsets[-1]) if n else 0
-        cfg, _keep = self.encoder._cfg_struct(now_ts)
+        cfg, _keep = self._encode_cfg(now_ts)
         self._set_compression()
         res, ust = L.fg_transcoded(), C.c_void_p()
         rc = L.lib().fg_udp_transcode_batch(self.decoder._ctx, self.decoder.fmt, C.byref(cfg), data.ctypes.data if nbytes else None, nbytes,

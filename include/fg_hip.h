@@ -893,13 +893,15 @@ uint64_t fg_deflate_bound(uint64_t nbytes, uint64_t n_members);
 int fg_deflate_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint8_t* d_z,
                       uint64_t z_cap, uint64_t* d_z_offsets, uint64_t* total, void* stream);
 /* Compression of what fg_transcode_batch, fg_transcode_multi_batch and fg_udp_transcode_batch return (NULL or FG_COMP_NONE: off, the
- * default, and then nothing changes by a byte).  With FG_COMP_GZIP those calls cut the encoded stream into members by cfg, compress it
+ * default, and then nothing changes by a byte).  A cfg with FG_COMP_NONE is stored as it is given (NULL: {FG_COMP_NONE, 1, 0}): its
+ * coalesce / member_bytes compress nothing, and the one thing that reads them is the message-set stage of FG_WIRE_KAFKA_V0
+ * (fg_set_output_wire, below), which cuts its uncompressed sets by them; with FG_WIRE_RAW they have no effect.  With FG_COMP_GZIP those calls cut the encoded stream into members by cfg, compress it
  * behind the encoder and do NOT copy the plain stream over the link: their `out` is NULL, out_bytes is the uncompressed total, and
  * out_offsets, meta, enc_status and everything else are as without compression.  fg_last_compressed hands out what the last such call
  * left (pinned host memory owned by ctx, valid until the next host-buffer call on it): z[0 .. z_bytes) the members back to back,
  * z_offsets[n_members + 1] their bounds, member_first[n_members + 1] each member's first message index (the last entry = n),
  * raw_bytes = out_bytes; all zero after a call without compression.  A member is the concatenation of its messages' encoded and framed
- * bytes (the Kafka message-set wire format is not built here).  With compression set fg_transcode_batch runs in one piece: members are
+ * bytes, not a Kafka message set (fg_set_output_wire below builds that).  With compression set fg_transcode_batch runs in one piece: members are
  * not cut across the slices of its pipelined form. */
 int fg_set_output_compression(fg_ctx* ctx, const fg_compress_cfg* cfg);
 /* How the compressor codes a block, for fg_deflate_device and for the compress stage of the three transcode calls: a ctx setting like the
@@ -917,6 +919,49 @@ typedef struct fg_compressed {
     uint64_t raw_bytes;
 } fg_compressed;
 int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out);
+
+/* KAFKA v0 MESSAGE SETS ON THE GPU (additive under the same FG_ABI_VERSION).  The reference's Kafka output hands every encoded line to
+ * the producer as a record with a null key (output/kafka_output.rs:68-112); the producer renders a request's records as a v0 MessageSet
+ * and, with compression on, compresses THAT set and sends it as the value of one wrapper message.  This builds both in HBM, between the
+ * encoder and the compressor.  All integers big-endian; a message is
+ *     offset 8 (0: the broker assigns) | message_size 4 (14 + value length) | crc 4 | magic 1 (0) | attributes 1 | key length 4 (-1:
+ *     a null key, no key bytes) | value length 4 | value
+ * 26 bytes (fg_kafka_message_overhead()) around the value; crc = CRC-32 (IEEE, zlib's) of magic .. the value's end.  A message set is
+ * messages back to back.  A gzip wrapper is one message with attributes = 1 whose value is a complete gzip member (what fg_deflate_device
+ * makes of the inner set).  The format is the Kafka protocol guide's MessageSet v0; the producer crate's source was not compared against.
+ *   fg_kafka_messageset_device   message i's value = d_bytes[d_offsets[i] .. d_offsets[i + 1]) (an encoder's out / out_offsets, merger
+ *                       bytes included); d_skip: NULL, or n bytes, nonzero = the row is NOT in the set (an encoder's enc_status: the reference
+ *                       never sends a line that failed); a row that is not skipped and has an empty value is a message with value length 0.
+ *                       d_set_offsets[n + 1]: where each message lies in the set (a skipped row: an empty range).  d_set == NULL: a sizing
+ *                       call (*total and d_set_offsets are set).  *total > set_cap: FG_ERR_ENT_OVERFLOW and d_set is not written.
+ *                       FG_ERR_ARG: offsets that do not ascend or go past nbytes, a message whose wire size does not fit int32.
+ *                       Synchronises the stream.  FG_ERR_UNSUPPORTED: a build without the kernels.
+ *   fg_kafka_wrap_device   member m = d_z[d_z_offsets[m] .. d_z_offsets[m + 1]) (fg_deflate_device's z / z_offsets) -> one wrapper message
+ *                       per NON-EMPTY member in d_w, d_w_offsets[n_members + 1] their bounds; an empty member produces no byte.  The same
+ *                       contract: the sizing call, FG_ERR_ENT_OVERFLOW, FG_ERR_ARG for offsets that do not ascend or a member that does
+ *                       not fit int32, the stream synchronised.
+ *   fg_kafka_bound      bytes that always suffice for the plain set of n messages over nbytes AND for its n_members compressed members
+ *                       in their wrappers
+ * A caller with resident data composes fg_encode_device -> fg_kafka_messageset_device -> fg_deflate_device (cuts =
+ * d_set_offsets[member_first[k]]) -> fg_kafka_wrap_device.  The output is a pure function of the input. */
+uint32_t fg_kafka_message_overhead(void);
+uint64_t fg_kafka_bound(uint64_t nbytes, uint64_t n, uint64_t n_members);
+int fg_kafka_messageset_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n,
+                               uint8_t* d_set, uint64_t set_cap, uint64_t* d_set_offsets, uint64_t* total, void* stream);
+int fg_kafka_wrap_device(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_offsets, uint64_t n_members, uint8_t* d_w, uint64_t w_cap,
+                         uint64_t* d_w_offsets, uint64_t* total, void* stream);
+/* What the three transcode calls hand out: a ctx setting like fg_set_deflate_mode (fg_clone copies it), FG_WIRE_RAW by default, and then
+ * nothing changes by a byte.  With FG_WIRE_KAFKA_V0 the calls run in one piece and build the message set behind the encoder: members are
+ * cut by the ctx's fg_compress_cfg policy (coalesce / member_bytes over out_offsets, counted over ALL rows, skipped ones included; a cfg
+ * with codec FG_COMP_NONE carries its policy too; no cfg or NULL: coalesce = 1), rows with enc_status != 0 are not in the set, and
+ * fg_last_compressed hands out
+ *     FG_COMP_GZIP   z = one wrapper message per non-empty member (the set deflated member by member, byte cuts
+ *                    set_offsets[member_first[k]]), z_offsets their bounds
+ *     FG_COMP_NONE   z = the plain message set, z_offsets[n_members + 1] the members' bounds in it
+ * `out` is NULL, out_bytes and raw_bytes stay the encoder's total, out_offsets, meta and enc_status are unchanged.  A member whose rows
+ * are all skipped is an empty set: no byte, no wrapper.  FG_ERR_ARG: a NULL ctx, any other value. */
+typedef enum fg_output_wire { FG_WIRE_RAW = 0, FG_WIRE_KAFKA_V0 = 1 } fg_output_wire;
+int fg_set_output_wire(fg_ctx* ctx, int wire);
 
 /* Host memory for the framer's batch buffers (bytes, offsets): PAGE-LOCKED, through a process-wide pool -- a freed block is kept
  * (up to idle_bytes in total) and handed to the next request it fits, so a framer per connection does not pin and unpin megabytes per
