@@ -599,6 +599,79 @@ const char* fg_udp_error_string(uint8_t st) {
     }
 }
 
+// ---- the sized resident calls (fg_udp_unpack_device, fg_udp_unpack_once_device, fg_deflate_device, fg_kafka_messageset_device,
+// fg_kafka_wrap_device): a front half leaves the offsets and *total, a write half fills the caller's buffer.
+extern "C++" {
+namespace {
+// What such an entry does between its argument checks and its write half, on s: n == 0 clears offsets[0] and waits; else front(),
+// which leaves d_offsets_out[0 .. n] and synchronises for *total.  FG_SIZED_WRITE: the caller's buffer holds *total bytes -- the entry
+// goes on to its write half (and waits for it or not, as it documents); anything else is the entry's answer: FG_OK for the sizing call
+// (no buffer) and for n == 0, FG_ERR_ENT_OVERFLOW for a buffer that is too small, front()'s error.
+constexpr int FG_SIZED_WRITE = 1;
+template <class Front>
+int sized_front(fg_ctx* ctx, hipStream_t s, uint64_t n, uint64_t* d_offsets_out, bool has_buffer, uint64_t cap, const uint64_t* total, Front&& front) {
+    if (n == 0) {
+        FG_HIP(ctx, hipMemsetAsync(d_offsets_out, 0, 8, s));
+        FG_HIP(ctx, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    const int rc = front();
+    if (rc != FG_OK) return rc;
+    if (!has_buffer) return FG_OK;  // the sizing call
+    return *total > cap ? FG_ERR_ENT_OVERFLOW : FG_SIZED_WRITE;
+}
+
+// What a front half does around its sizing launch: the ctx's error word cleared (h_err; nullptr: the launch has none), the launch, the
+// error word and the launch's other results (totals, counts) downloaded, one synchronisation of s.  FG_ERR_ARG: the kernel refused its
+// input (the error word is set).
+struct Download {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+template <class Launch>
+int front_results(fg_ctx* ctx, hipStream_t s, uint32_t* h_err, const uint32_t* d_err, std::initializer_list<Download> words, Launch&& launch) {
+    if (h_err) *h_err = 0;
+    FG_LAUNCH(ctx, launch());
+    if (h_err) FG_HIP(ctx, hipMemcpyAsync(h_err, d_err, 4, hipMemcpyDeviceToHost, s));
+    for (const Download& w : words) FG_HIP(ctx, hipMemcpyAsync(w.host, w.dev, w.bytes, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipStreamSynchronize(s));
+    return h_err && *h_err ? FG_ERR_ARG : FG_OK;
+}
+
+// ctx->d_udp as fg_udp_unpack_device lays it out for n datagrams: sizes | their per-64 sums
+struct UdpSizes {
+    uint32_t* d_sizes;
+    uint64_t *d_sums, bytes;
+    UdpSizes(uint8_t* b, uint64_t n) {
+        Carver c{b};
+        d_sizes = c.take<uint32_t>(n);
+        d_sums = c.take<uint64_t>((n + 63) / 64, 8);
+        bytes = c.off;
+    }
+};
+// ... and as the one-walk form does: sizes | their per-64 sums | stage capacities | their sums | stage offsets [n + 1] | spilled flags |
+// the spilled count (ctx->d_udp_stage holds the stages)
+struct UdpOnce {
+    uint32_t *d_sizes, *d_stage_sizes, *d_n_spilled;
+    uint64_t *d_sums, *d_stage_sums, *d_stage_off, bytes;
+    uint8_t* d_spilled;
+    UdpOnce(uint8_t* b, uint64_t n) {
+        Carver c{b};
+        const uint64_t nb = (n + 63) / 64;
+        d_sizes = c.take<uint32_t>(n);
+        d_sums = c.take<uint64_t>(nb, 8);
+        d_stage_sizes = c.take<uint32_t>(n);
+        d_stage_sums = c.take<uint64_t>(nb, 8);
+        d_stage_off = c.take<uint64_t>(n + 2, 8);
+        d_spilled = c.take<uint8_t>(n);
+        d_n_spilled = c.take<uint32_t>(1);
+        bytes = c.off;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
 // replaces handle_record_maybe_compressed (input/udp_input.rs:100-143) up to decoder.decode, for a batch of datagrams
 int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
                          uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total,
@@ -611,68 +684,40 @@ int fg_udp_unpack_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, c
     if (!fg_launch_udp_count || !fg_launch_udp_write || !fg_launch_udp_finish) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (n == 0) {
-        FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));
+    int rc = sized_front(ctx, s, n, d_out_offsets, d_out != nullptr, out_cap, total, [&]() -> int {
+        const int grc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, UdpSizes(nullptr, n).bytes);
+        if (grc != FG_OK) return grc;
+        const UdpSizes u(ctx->d_udp, n);
+        int lrc = fg_launch_udp_count(d_bytes, d_offsets, n, (uint32_t)max_inflated, u.d_sizes, u.d_sums, d_udp_status, d_drop, s);
+        if (lrc == 0) lrc = fg_launch_encode_scan(u.d_sizes, u.d_sums, n, d_out_offsets, 0ull, s);
+        FG_LAUNCH(ctx, lrc);
+        FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         return FG_OK;
-    }
-    int rc;
-    const uint64_t nb = (n + 63) / 64, sizes_bytes = up(n * 4, 16);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, sizes_bytes + nb * 8)) != FG_OK) return rc;
-    uint32_t* d_sizes = (uint32_t*)ctx->d_udp;
-    uint64_t* d_sums = (uint64_t*)(ctx->d_udp + sizes_bytes);
-    int lrc = fg_launch_udp_count(d_bytes, d_offsets, n, (uint32_t)max_inflated, d_sizes, d_sums, d_udp_status, d_drop, s);
-    if (lrc == 0) lrc = fg_launch_encode_scan(d_sizes, d_sums, n, d_out_offsets, 0ull, s);
-    FG_LAUNCH(ctx, lrc);
-    FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (!d_out) return FG_OK;  // the sizing call
-    if (*total > out_cap) return FG_ERR_ENT_OVERFLOW;
-    lrc = fg_launch_udp_write(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
-    if (lrc == 0) lrc = fg_launch_udp_finish(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
-    FG_LAUNCH(ctx, lrc);
+    });
+    if (rc != FG_SIZED_WRITE) return rc;
+    rc = fg_launch_udp_write(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
+    if (rc == 0) rc = fg_launch_udp_finish(d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_udp_status, d_drop, s);
+    FG_LAUNCH(ctx, rc);
     FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
 }
 
-// ---- the one-walk form.  ctx->d_udp holds, for n datagrams: sizes | their per-64 sums | stage capacities | their sums | stage offsets
-// [n + 1] | spilled flags | the spilled count; ctx->d_udp_stage the stages.
-namespace {
-struct UdpOnce {
-    uint32_t *d_sizes, *d_stage_sizes, *d_n_spilled;
-    uint64_t *d_sums, *d_stage_sums, *d_stage_off;
-    uint8_t* d_spilled;
-    static uint64_t bytes(uint64_t n) { return 2 * up(n * 4, 16) + 2 * ((n + 63) / 64) * 8 + (n + 2) * 8 + up(n, 16) + 16; }
-    UdpOnce(uint8_t* b, uint64_t n) {
-        const uint64_t nb = (n + 63) / 64;
-        d_sizes = (uint32_t*)b;
-        d_sums = (uint64_t*)(b += up(n * 4, 16));
-        d_stage_sizes = (uint32_t*)(b += nb * 8);
-        d_stage_sums = (uint64_t*)(b += up(n * 4, 16));
-        d_stage_off = (uint64_t*)(b += nb * 8);
-        d_spilled = (b += (n + 2) * 8);
-        d_n_spilled = (uint32_t*)(b += up(n, 16));
-    }
-};
-}  // namespace
-
-// The front half: every datagram walked once into its stage, d_out_offsets / d_drop / d_udp_status as fg_udp_unpack_device leaves them
-// except for what the back half settles (the checksums of spilled rows, UTF-8), *total = the packed bytes.  Synchronises s once.
-// n > 0, max_inflated checked by the caller.
+// The front half of the one-walk form: every datagram walked once into its stage, d_out_offsets / d_drop / d_udp_status as
+// fg_udp_unpack_device leaves them except for what the back half settles (the checksums of spilled rows, UTF-8), *total = the packed
+// bytes.  Synchronises s once.  n > 0, max_inflated checked by the caller.
 int fg_udp_once_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_offsets, uint64_t n, uint64_t max_inflated,
                       uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, hipStream_t s) {
     ctx->udp_last_spilled = 0;
     if (!fg_launch_udp_stage || !fg_launch_udp_write_spilled || !fg_launch_udp_pack || !fg_udp_stage_bytes) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     int rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, UdpOnce::bytes(n))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_udp, &ctx->d_udp_cap, UdpOnce(nullptr, n).bytes)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_udp_stage, &ctx->d_udp_stage_cap, fg_udp_stage_bytes(nbytes, n))) != FG_OK) return rc;
     const UdpOnce u(ctx->d_udp, n);
-    FG_LAUNCH(ctx, fg_launch_udp_stage(d_bytes, d_offsets, n, (uint32_t)max_inflated, u.d_stage_sizes, u.d_stage_sums, u.d_stage_off, ctx->d_udp_stage,
-                                       ctx->d_udp_stage_cap, u.d_sizes, u.d_sums, d_out_offsets, d_udp_status, d_drop, u.d_spilled, u.d_n_spilled, s));
-    FG_HIP(ctx, hipMemcpyAsync(total, d_out_offsets + n, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->udp_last_spilled, u.d_n_spilled, 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    return FG_OK;
+    return front_results(ctx, s, nullptr, nullptr, {{total, d_out_offsets + n, 8}, {&ctx->udp_last_spilled, u.d_n_spilled, 4}}, [&] {
+        return fg_launch_udp_stage(d_bytes, d_offsets, n, (uint32_t)max_inflated, u.d_stage_sizes, u.d_stage_sums, u.d_stage_off, ctx->d_udp_stage,
+                                   ctx->d_udp_stage_cap, u.d_sizes, u.d_sums, d_out_offsets, d_udp_status, d_drop, u.d_spilled, u.d_n_spilled, s);
+    });
 }
 // The back half, into d_out[0 .. out_cap) with out_cap >= the front half's total: the write walk for the spilled rows (when there are
 // any), every other row from its stage or its datagram, UTF-8.  Queued on s, not waited for.
@@ -698,43 +743,43 @@ int fg_udp_unpack_once_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbyt
     ctx->udp_last_spilled = 0;
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (n == 0) {
-        FG_HIP(ctx, hipMemsetAsync(d_out_offsets, 0, 8, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    int rc;
-    if ((rc = fg_udp_once_front(ctx, d_bytes, nbytes, d_offsets, n, max_inflated, d_out_offsets, d_drop, d_udp_status, total, s)) != FG_OK) return rc;
-    if (*total > out_cap) return FG_ERR_ENT_OVERFLOW;
-    return fg_udp_once_pack(ctx, d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_drop, d_udp_status, s);
+    const int rc = sized_front(ctx, s, n, d_out_offsets, true, out_cap, total, [&] {
+        return fg_udp_once_front(ctx, d_bytes, nbytes, d_offsets, n, max_inflated, d_out_offsets, d_drop, d_udp_status, total, s);
+    });
+    if (rc != FG_SIZED_WRITE) return rc;
+    return fg_udp_once_pack(ctx, d_bytes, d_offsets, n, d_out_offsets, d_out, out_cap, d_drop, d_udp_status, s);  // (queued, NOT waited for)
 }
 uint64_t fg_udp_last_spilled(const fg_ctx* ctx) { return ctx ? ctx->udp_last_spilled : 0; }
 
-// ---- the output compressor (fg_deflate.hip).  ctx->d_df holds, for n members: block counts | sizes | CRCs | the sums of the two scans (one
-// after the other) | blk_first[n + 1] | the error word, the ticket word; ctx->d_df_blk, per block: size | CRC | offset in its member;
-// ctx->d_df_slots the slots.
+// ---- the output compressor (fg_deflate.hip).  ctx->d_df_slots holds the slots the blocks are compressed into.
 namespace {
+// ctx->d_df, for n members: block counts | sizes | CRCs | the sums of the two scans (one after the other) | blk_first[n + 1] | the error
+// word, the ticket word
 struct DfMembers {
     uint32_t *d_nblk, *d_msize, *d_crc, *d_err, *d_ticket;
-    uint64_t *d_sums, *d_blk_first;
-    static uint64_t bytes(uint64_t n) { return 3 * up(n * 4, 16) + up((n + 63) / 64 * 8, 16) + (n + 2) * 8 + 16; }
+    uint64_t *d_sums, *d_blk_first, bytes;
     DfMembers(uint8_t* b, uint64_t n) {
-        d_nblk = (uint32_t*)b;
-        d_msize = (uint32_t*)(b += up(n * 4, 16));
-        d_crc = (uint32_t*)(b += up(n * 4, 16));
-        d_sums = (uint64_t*)(b += up(n * 4, 16));
-        d_blk_first = (uint64_t*)(b += up((n + 63) / 64 * 8, 16));
-        d_err = (uint32_t*)(b += (n + 2) * 8);
-        d_ticket = d_err + 1;
+        Carver c{b};
+        d_nblk = c.take<uint32_t>(n);
+        d_msize = c.take<uint32_t>(n);
+        d_crc = c.take<uint32_t>(n);
+        d_sums = c.take<uint64_t>((n + 63) / 64);
+        d_blk_first = c.take<uint64_t>(n + 2, 8);
+        d_err = c.take<uint32_t>(2);
+        d_ticket = b ? d_err + 1 : nullptr;
+        bytes = c.off;
     }
 };
+// ctx->d_df_blk, per block: size | CRC | offset in its member
 struct DfBlocks {
     uint32_t *d_size, *d_crc, *d_rel;
-    static uint64_t bytes(uint64_t nb) { return 3 * up(nb * 4, 16); }
+    uint64_t bytes;
     DfBlocks(uint8_t* b, uint64_t nb) {
-        d_size = (uint32_t*)b;
-        d_crc = (uint32_t*)(b += up(nb * 4, 16));
-        d_rel = (uint32_t*)(b += up(nb * 4, 16));
+        Carver c{b};
+        d_size = c.take<uint32_t>(nb);
+        d_crc = c.take<uint32_t>(nb);
+        d_rel = c.take<uint32_t>(nb);
+        bytes = c.off;
     }
 };
 }  // namespace
@@ -748,21 +793,18 @@ int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const
     const bool dyn = ctx->deflate_mode == FG_DEFLATE_DYNAMIC;
     if (dyn && !fg_launch_deflate_blocks_dyn) return FG_ERR_UNSUPPORTED;
     int rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_df, &ctx->d_df_cap, DfMembers::bytes(n_members))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df, &ctx->d_df_cap, DfMembers(nullptr, n_members).bytes)) != FG_OK) return rc;
     const DfMembers m(ctx->d_df, n_members);
     uint64_t nb = 0;
-    ctx->df_err = 0;
-    FG_LAUNCH(ctx, fg_launch_deflate_count(d_cuts, n_members, nbytes, m.d_nblk, m.d_sums, m.d_blk_first, m.d_err, s));
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_err, m.d_err, 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(&nb, m.d_blk_first + n_members, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->df_err) return FG_ERR_ARG;
-    if (nb == 0) {  // (nothing but empty members)
+    rc = front_results(ctx, s, &ctx->df_err, m.d_err, {{&nb, m.d_blk_first + n_members, 8}},
+                       [&] { return fg_launch_deflate_count(d_cuts, n_members, nbytes, m.d_nblk, m.d_sums, m.d_blk_first, m.d_err, s); });
+    if (rc != FG_OK) return rc;
+    if (nb == 0) {  // (nothing but empty members: the cleared offsets are waited for, as the scan's are below)
         FG_HIP(ctx, hipMemsetAsync(d_z_offsets, 0, (n_members + 1) * 8, s));
         FG_HIP(ctx, hipStreamSynchronize(s));
         return FG_OK;
     }
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_blk, &ctx->d_df_blk_cap, DfBlocks::bytes(nb))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_blk, &ctx->d_df_blk_cap, DfBlocks(nullptr, nb).bytes)) != FG_OK) return rc;
     if ((rc = grow_dev(ctx, (void**)&ctx->d_df_slots, &ctx->d_df_slots_cap, fg_deflate_slot_bytes(nbytes, nb))) != FG_OK) return rc;
     const DfBlocks b(ctx->d_df_blk, nb);
     FG_LAUNCH(ctx, (dyn ? fg_launch_deflate_blocks_dyn : fg_launch_deflate_blocks)(d_bytes, d_cuts, m.d_blk_first, n_members, nb, ctx->d_df_slots,
@@ -792,15 +834,9 @@ int fg_deflate_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, cons
     if (!fg_launch_deflate_count) return FG_ERR_UNSUPPORTED;
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (n_members == 0) {
-        FG_HIP(ctx, hipMemsetAsync(d_z_offsets, 0, 8, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    int rc;
-    if ((rc = fg_deflate_front(ctx, d_bytes, nbytes, d_cuts, n_members, d_z_offsets, total, s)) != FG_OK) return rc;
-    if (!d_z) return FG_OK;  // the sizing call
-    if (*total > z_cap) return FG_ERR_ENT_OVERFLOW;
+    int rc = sized_front(ctx, s, n_members, d_z_offsets, d_z != nullptr, z_cap, total,
+                         [&] { return fg_deflate_front(ctx, d_bytes, nbytes, d_cuts, n_members, d_z_offsets, total, s); });
+    if (rc != FG_SIZED_WRITE) return rc;
     if ((rc = fg_deflate_pack(ctx, d_bytes, d_cuts, n_members, d_z_offsets, d_z, z_cap, s)) != FG_OK) return rc;
     FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
@@ -828,19 +864,32 @@ int fg_last_compressed(const fg_ctx* ctx, fg_compressed* out) {
     return FG_OK;
 }
 
-// ---- Kafka v0 message sets (fg_kafka.hip).  ctx->d_kf holds, for n messages: sizes | the scan's sums | the error word; ctx->d_kf_wrap, for n
-// members: wrapper sizes | pieces | the sums of the two scans | piece_first[n + 1] | the error word; ctx->d_kf_crc a register per piece.
+// ---- Kafka v0 message sets (fg_kafka.hip).  ctx->d_kf_crc holds a CRC register per piece.
 namespace {
+// ctx->d_kf, for n messages: sizes [n + 1] | the scan's sums | the error word
+struct KfSet {
+    uint32_t *d_sizes, *d_err;
+    uint64_t *d_sums, bytes;
+    KfSet(uint8_t* b, uint64_t n) {
+        Carver c{b};
+        d_sizes = c.take<uint32_t>(n + 1);
+        d_sums = c.take<uint64_t>((n + 63) / 64);
+        d_err = c.take<uint32_t>(1);
+        bytes = c.off;
+    }
+};
+// ctx->d_kf_wrap, for n members: wrapper sizes | pieces | the sums of the two scans | piece_first[n + 1] | the error word
 struct KfWrap {
     uint32_t *d_wsize, *d_npiece, *d_err;
-    uint64_t *d_sums, *d_piece_first;
-    static uint64_t bytes(uint64_t n) { return 2 * up(n * 4, 16) + up((n + 63) / 64 * 16, 16) + (n + 2) * 8 + 16; }
+    uint64_t *d_sums, *d_piece_first, bytes;
     KfWrap(uint8_t* b, uint64_t n) {
-        d_wsize = (uint32_t*)b;
-        d_npiece = (uint32_t*)(b += up(n * 4, 16));
-        d_sums = (uint64_t*)(b += up(n * 4, 16));
-        d_piece_first = (uint64_t*)(b += up((n + 63) / 64 * 16, 16));
-        d_err = (uint32_t*)(b += (n + 2) * 8);
+        Carver c{b};
+        d_wsize = c.take<uint32_t>(n);
+        d_npiece = c.take<uint32_t>(n);
+        d_sums = c.take<uint64_t>((n + 63) / 64 * 2);
+        d_piece_first = c.take<uint64_t>(n + 2, 8);
+        d_err = c.take<uint32_t>(1);
+        bytes = c.off;
     }
 };
 }  // namespace
@@ -850,21 +899,12 @@ int fg_kafka_set_front(fg_ctx* ctx, const uint64_t* d_offsets, const uint8_t* d_
     *total = 0;
     if (!fg_launch_kafka_sizes || !fg_launch_kafka_write) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     int rc;
-    const uint64_t sizes_bytes = up(n * 4 + 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16);
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf, &ctx->d_kf_cap, sizes_bytes + sums_bytes + 16)) != FG_OK) return rc;
-    uint32_t* d_sizes = (uint32_t*)ctx->d_kf;
-    uint64_t* d_sums = (uint64_t*)(ctx->d_kf + sizes_bytes);
-    uint32_t* d_err = (uint32_t*)(ctx->d_kf + sizes_bytes + sums_bytes);
-    ctx->kf_err = 0;
-    FG_LAUNCH(ctx, fg_launch_kafka_sizes(d_offsets, d_skip, n, nbytes, d_sizes, d_sums, d_set_offsets, d_err, s));
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->kf_err, d_err, 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(total, d_set_offsets + n, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->kf_err) {
-        *total = 0;
-        return FG_ERR_ARG;
-    }
-    return FG_OK;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf, &ctx->d_kf_cap, KfSet(nullptr, n).bytes)) != FG_OK) return rc;
+    const KfSet m(ctx->d_kf, n);
+    rc = front_results(ctx, s, &ctx->kf_err, m.d_err, {{total, d_set_offsets + n, 8}},
+                       [&] { return fg_launch_kafka_sizes(d_offsets, d_skip, n, nbytes, m.d_sizes, m.d_sums, d_set_offsets, m.d_err, s); });
+    if (rc == FG_ERR_ARG) *total = 0;  // (refused offsets: whatever the scan left is no size)
+    return rc;
 }
 int fg_kafka_set_write(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, const uint8_t* d_skip, uint64_t n, const uint64_t* d_set_offsets,
                        uint8_t* d_set, uint64_t set_cap, hipStream_t s) {
@@ -879,16 +919,10 @@ int fg_kafka_messageset_device(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nby
     if (!fg_launch_kafka_sizes) return FG_ERR_UNSUPPORTED;
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (n == 0) {
-        FG_HIP(ctx, hipMemsetAsync(d_set_offsets, 0, 8, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    int rc;
-    if ((rc = fg_kafka_set_front(ctx, d_offsets, d_skip, n, nbytes, d_set_offsets, total, s)) != FG_OK) return rc;
-    if (!d_set) return FG_OK;  // the sizing call
-    if (*total > set_cap) return FG_ERR_ENT_OVERFLOW;
-    if (*total == 0) return FG_OK;  // (every row skipped)
+    int rc = sized_front(ctx, s, n, d_set_offsets, d_set != nullptr, set_cap, total,
+                         [&] { return fg_kafka_set_front(ctx, d_offsets, d_skip, n, nbytes, d_set_offsets, total, s); });
+    if (rc != FG_SIZED_WRITE) return rc;
+    if (*total == 0) return FG_OK;  // (every row skipped: nothing to write or to wait for)
     if ((rc = fg_kafka_set_write(ctx, d_bytes, d_offsets, d_skip, n, d_set_offsets, d_set, set_cap, s)) != FG_OK) return rc;
     FG_HIP(ctx, hipStreamSynchronize(s));
     return FG_OK;
@@ -899,21 +933,15 @@ int fg_kafka_wrap_front(fg_ctx* ctx, const uint64_t* d_z_offsets, uint64_t n_mem
     ctx->kf_pieces = 0;
     if (!fg_launch_kafka_wrap_sizes || !fg_launch_kafka_wrap) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     int rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_wrap, &ctx->d_kf_wrap_cap, KfWrap::bytes(n_members))) != FG_OK) return rc;
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_wrap, &ctx->d_kf_wrap_cap, KfWrap(nullptr, n_members).bytes)) != FG_OK) return rc;
     const KfWrap m(ctx->d_kf_wrap, n_members);
     uint64_t np = 0;
-    ctx->kf_err = 0;
-    FG_LAUNCH(ctx, fg_launch_kafka_wrap_sizes(d_z_offsets, n_members, m.d_wsize, m.d_npiece, m.d_sums, d_w_offsets, m.d_piece_first, m.d_err, s));
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->kf_err, m.d_err, 4, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(&np, m.d_piece_first + n_members, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(total, d_w_offsets + n_members, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->kf_err) {
-        *total = 0;
-        return FG_ERR_ARG;
-    }
-    ctx->kf_pieces = np;
-    return FG_OK;
+    rc = front_results(ctx, s, &ctx->kf_err, m.d_err, {{&np, m.d_piece_first + n_members, 8}, {total, d_w_offsets + n_members, 8}}, [&] {
+        return fg_launch_kafka_wrap_sizes(d_z_offsets, n_members, m.d_wsize, m.d_npiece, m.d_sums, d_w_offsets, m.d_piece_first, m.d_err, s);
+    });
+    if (rc == FG_ERR_ARG) *total = 0;  // (refused offsets, as in fg_kafka_set_front)
+    if (rc == FG_OK) ctx->kf_pieces = np;
+    return rc;
 }
 int fg_kafka_wrap_write(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_offsets, uint64_t n_members, const uint64_t* d_w_offsets, uint8_t* d_w,
                         uint64_t w_cap, hipStream_t s) {
@@ -933,15 +961,9 @@ int fg_kafka_wrap_device(fg_ctx* ctx, const uint8_t* d_z, const uint64_t* d_z_of
     if (!fg_launch_kafka_wrap_sizes) return FG_ERR_UNSUPPORTED;
     DeviceGuard g(ctx->device);
     hipStream_t s = stream_of(ctx, stream);
-    if (n_members == 0) {
-        FG_HIP(ctx, hipMemsetAsync(d_w_offsets, 0, 8, s));
-        FG_HIP(ctx, hipStreamSynchronize(s));
-        return FG_OK;
-    }
-    int rc;
-    if ((rc = fg_kafka_wrap_front(ctx, d_z_offsets, n_members, d_w_offsets, total, s)) != FG_OK) return rc;
-    if (!d_w) return FG_OK;  // the sizing call
-    if (*total > w_cap) return FG_ERR_ENT_OVERFLOW;
+    int rc = sized_front(ctx, s, n_members, d_w_offsets, d_w != nullptr, w_cap, total,
+                         [&] { return fg_kafka_wrap_front(ctx, d_z_offsets, n_members, d_w_offsets, total, s); });
+    if (rc != FG_SIZED_WRITE) return rc;
     if (*total && !d_z) return FG_ERR_ARG;
     if ((rc = fg_kafka_wrap_write(ctx, d_z, d_z_offsets, n_members, d_w_offsets, d_w, w_cap, s)) != FG_OK) return rc;
     FG_HIP(ctx, hipStreamSynchronize(s));

@@ -255,7 +255,7 @@ struct fg_ctx {
     // fg_udp_decode_batch also BORROWS d_bytes (the datagrams), d_sl_packed (the payloads), d_offsets (their offsets), d_bad (the drop
     // flags) and d_tab / h_tab from the frame / syslen / decode paths: every host-buffer call on a ctx synchronises before it returns,
     // so no two of them have these buffers in use at once.
-    uint8_t* d_udp = nullptr;        // fg_udp_unpack_device: per-datagram sizes, then the per-64 sums of the scan
+    uint8_t* d_udp = nullptr;        // the unpackers' per-datagram scratch: UdpSizes (fg_udp_unpack_device) or UdpOnce (the one-walk form), fg_capi.cpp
     uint64_t d_udp_cap = 0;
     uint8_t* d_udp_stage = nullptr;  // fg_udp_unpack_once_device: the stages the one walk inflates into
     uint64_t d_udp_stage_cap = 0;
@@ -315,15 +315,15 @@ struct fg_ctx {
     fg_compress_cfg compress{FG_COMP_NONE, 1u, 0u};
     int deflate_mode = FG_DEFLATE_FIXED;  // fg_set_deflate_mode
     fg_compressed last_comp{};       // fg_last_compressed
-    uint8_t* d_df = nullptr;         // per member: block counts | sizes | CRCs | the scans' sums | blk_first[n + 1]; the error and ticket words
+    uint8_t* d_df = nullptr;         // per member: DfMembers (fg_capi.cpp)
     uint64_t d_df_cap = 0;
-    uint8_t* d_df_blk = nullptr;     // per block: size | CRC | offset in its member
+    uint8_t* d_df_blk = nullptr;     // per block: DfBlocks (fg_capi.cpp)
     uint64_t d_df_blk_cap = 0;
     uint8_t* d_df_slots = nullptr;   // the slots the blocks are compressed into
     uint64_t d_df_slots_cap = 0;
     uint64_t df_blocks = 0;          // ... how many of them the last front half found (a word it downloads into)
     uint32_t df_err = 0;             // ... and whether it refused the cuts
-    uint8_t* d_df_cut = nullptr;     // the transcode entry points: start flags | sums | ranks | member_first[n + 2] | cuts[n + 2] | z_offsets[n + 2] | the count
+    uint8_t* d_df_cut = nullptr;     // the transcode entry points' member stage: MemberCuts (fg_host_pipeline.cpp)
     uint64_t d_df_cut_cap = 0;
     uint64_t df_members = 0;         // ... the members of the last cut (a word it is downloaded into)
     uint8_t* d_zout = nullptr;       // ... the compressed stream
@@ -333,9 +333,9 @@ struct fg_ctx {
     // Kafka v0 message sets (fg_kafka_messageset_device, fg_kafka_wrap_device, and behind the encoder of the transcode entry points:
     // fg_set_output_wire)
     int wire = FG_WIRE_RAW;
-    uint8_t* d_kf = nullptr;         // per message: sizes | the scan's sums | the error word
+    uint8_t* d_kf = nullptr;         // per message: KfSet (fg_capi.cpp)
     uint64_t d_kf_cap = 0;
-    uint8_t* d_kf_wrap = nullptr;    // per member: wrapper sizes | pieces | the two scans' sums | piece_first[n + 1] | the error word
+    uint8_t* d_kf_wrap = nullptr;    // per member: KfWrap (fg_capi.cpp)
     uint64_t d_kf_wrap_cap = 0;
     uint8_t* d_kf_crc = nullptr;     // per piece: its CRC register
     uint64_t d_kf_crc_cap = 0;
@@ -343,7 +343,7 @@ struct fg_ctx {
     uint64_t kf_pieces = 0;          // ... and the pieces the last wrap front found
     uint8_t* d_kf_set = nullptr;     // the transcode entry points: the message set
     uint64_t d_kf_set_cap = 0;
-    uint8_t* d_kf_off = nullptr;     // ... set_offsets[n + 1] | set_cuts[n + 2] | w_offsets[n + 2]
+    uint8_t* d_kf_off = nullptr;     // ... the offset lists of the member stage: KfOffsets (fg_host_pipeline.cpp)
     uint64_t d_kf_off_cap = 0;
     uint8_t* d_kf_w = nullptr;       // ... the wrapper messages
     uint64_t d_kf_w_cap = 0;
@@ -467,6 +467,20 @@ int grow_pinned(fg_ctx* ctx, void** p, uint64_t* cap, uint64_t need) {
     return FG_OK;
 }
 
+// One scratch allocation handed out array by array.  A layout struct (UdpOnce, DfMembers, MemberCuts, ...) walks its arrays through one
+// of these in its constructor and nowhere else: over the buffer for the launchers' pointers, over a null base for the size to ask of
+// grow_dev (`Layout(nullptr, n).bytes`), so the two cannot disagree.  take: `count` elements of T, the next array `pad`-aligned behind them.
+struct Carver {
+    uint8_t* base;
+    uint64_t off = 0;
+    template <class T>
+    T* take(uint64_t count, uint64_t pad = 16) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += up(count * sizeof(T), pad);
+        return p;
+    }
+};
+
 // One framing scan of d_bytes[0 .. nbytes) on s, shared by fg_frame_device and the host paths' frame_stage: the one-pass scan, launched
 // again in its classic three-kernel form when its look-back gave up (FG_FRAME_ABORTED).  *total = the delimiters = the terminated
 // frames; more of them (and a possible tail) than `cap` holds -> FG_ERR_ENT_OVERFLOW, nothing else is read; else *last_end = where the
@@ -575,7 +589,7 @@ extern "C" int fg_udp_once_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t n
                                  uint64_t* d_out_offsets, uint8_t* d_drop, uint8_t* d_udp_status, uint64_t* total, hipStream_t s);
 extern "C" int fg_udp_once_pack(fg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_out_offsets, uint8_t* d_out,
                                 uint64_t out_cap, uint8_t* d_drop, uint8_t* d_udp_status, hipStream_t s);
-// the two halves of fg_deflate_device (fg_capi.cpp), for the transcode tail, which sizes its buffer between them: the front compresses
+// the two halves of fg_deflate_device (fg_capi.cpp), for member_stage (fg_host_pipeline.cpp), which sizes its buffer between them: the front compresses
 // every block into ctx-owned slots, leaves d_z_offsets[n_members + 1] and synchronises for *total; the pack fills d_z[0 .. z_cap)
 // (z_cap >= *total) and is not waited for.  n_members > 0.
 extern "C" int fg_deflate_front(fg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_cuts, uint64_t n_members, uint64_t* d_z_offsets,

@@ -1592,102 +1592,98 @@ static int transcode_sliced(fg_ctx* ctx, fg_format fmt, const fg_encode_cfg* ecf
     return FG_OK;
 }
 
-// The compression of a transcode (fg_set_output_compression): the `total` bytes of ctx->d_tout, whose n messages d_out_offsets bounds, are
-// cut into members by the ctx's policy and compressed behind the encoder; the members, their bounds and their first messages go to
-// ctx->h_zout and ctx->last_comp names them.  Synchronises for the member count and the sizes (the buffers are sized by them); the
-// downloads are queued on the ctx's stream and NOT waited for.  ctx->d_df_cut: start flags | sums | ranks[n + 1] | member_first[n + 2] |
-// cuts[n + 2] | z_offsets[n + 2] | the member count.  n > 0.
-static int compress_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, uint64_t n, uint64_t total) {
+namespace {
+// ctx->d_df_cut, for n messages: start flags | sums | ranks[n + 1] | member_first[n + 2] | cuts[n + 2] | z_offsets[n + 2] | the member count
+struct MemberCuts {
+    uint32_t* d_flags;
+    uint64_t *d_sums, *d_idx, *d_first, *d_cuts, *d_zoff, *d_count, bytes;
+    MemberCuts(uint8_t* b, uint64_t n) {
+        Carver c{b};
+        d_flags = c.take<uint32_t>(n);
+        d_sums = c.take<uint64_t>((n + 63) / 64);
+        d_idx = c.take<uint64_t>(n + 2, 8);
+        d_first = c.take<uint64_t>(n + 2, 8);
+        d_cuts = c.take<uint64_t>(n + 2, 8);
+        d_zoff = c.take<uint64_t>(n + 2, 8);
+        d_count = c.take<uint64_t>(1);
+        bytes = c.off;
+    }
+};
+// ctx->d_kf_off (FG_WIRE_KAFKA_V0), for n messages: three lists of n + 2 words each -- set_offsets (n + 1 of them written) | set_cuts |
+// w_offsets (n_members + 1 <= n + 1 written of either)
+struct KfOffsets {
+    uint64_t *d_set_off, *d_set_cuts, *d_woff, bytes;
+    KfOffsets(uint8_t* b, uint64_t n) {
+        Carver c{b};
+        d_set_off = c.take<uint64_t>(n + 2, 8);
+        d_set_cuts = c.take<uint64_t>(n + 2, 8);
+        d_woff = c.take<uint64_t>(n + 2, 8);
+        bytes = c.off;
+    }
+};
+}  // namespace
+
+// The member stage of a transcode, behind the encoder whenever the wire is not FG_WIRE_RAW or a codec is set (fg_set_output_wire,
+// fg_set_output_compression): members in the place of the messages.  The `total` bytes of ctx->d_tout, whose n messages d_out_offsets
+// bounds (d_enc_status nonzero: a row that is in no message set), become
+//   1. members, cut by the ctx's policy over the messages' offsets -- whatever follows, member_first is the same;
+//   2. FG_WIRE_KAFKA_V0: the message set built from ctx->d_tout, the members' byte cuts in it set_offsets[member_first[k]] (the cuts[]
+//      of step 1 are the plain stream's and unused then);
+//   3. FG_COMP_GZIP: what step 2 left -- the set, else the plain stream -- deflated member by member, and with Kafka every non-empty
+//      member wrapped in its message;
+//   4. the bytes, their bounds and member_first downloaded into ctx->h_zout, which ctx->last_comp names.
+// Synchronises for the member count and for every size a buffer is grown to (the set's, the members', the wrappers'); the downloads
+// are queued on the ctx's stream and NOT waited for.  n > 0.
+static int member_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, const uint8_t* d_enc_status, uint64_t n, uint64_t total) {
     hipStream_t s = ctx->stream;
-    if (!fg_launch_deflate_cuts) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
+    const bool kafka = ctx->wire == FG_WIRE_KAFKA_V0, gzip = ctx->compress.codec == FG_COMP_GZIP;
+    if (!fg_launch_deflate_cuts || (kafka && !fg_launch_kafka_cuts)) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
     int rc;
-    const uint64_t flags_bytes = up(n * 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16), list = (n + 2) * 8;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_cut, &ctx->d_df_cut_cap, flags_bytes + sums_bytes + 4 * list + 16)) != FG_OK) return rc;
-    uint8_t* b = ctx->d_df_cut;
-    uint32_t* d_flags = (uint32_t*)b;
-    uint64_t* d_sums = (uint64_t*)(b += flags_bytes);
-    uint64_t* d_idx = (uint64_t*)(b += sums_bytes);
-    uint64_t* d_first = (uint64_t*)(b += list);
-    uint64_t* d_cuts = (uint64_t*)(b += list);
-    uint64_t* d_zoff = (uint64_t*)(b += list);
-    uint64_t* d_count = (uint64_t*)(b += list);
-    FG_LAUNCH(ctx, fg_launch_deflate_cuts(d_out_offsets, n, ctx->compress.coalesce, ctx->compress.member_bytes, d_flags, d_sums, d_idx, d_first, d_cuts,
-                                          d_count, s));
+    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_cut, &ctx->d_df_cut_cap, MemberCuts(nullptr, n).bytes)) != FG_OK) return rc;
+    if (kafka && (rc = grow_dev(ctx, (void**)&ctx->d_kf_off, &ctx->d_kf_off_cap, KfOffsets(nullptr, n).bytes)) != FG_OK) return rc;
+    const MemberCuts m(ctx->d_df_cut, n);
+    const KfOffsets k(kafka ? ctx->d_kf_off : nullptr, n);
+    FG_LAUNCH(ctx, fg_launch_deflate_cuts(d_out_offsets, n, ctx->compress.coalesce, ctx->compress.member_bytes, m.d_flags, m.d_sums, m.d_idx, m.d_first,
+                                          m.d_cuts, m.d_count, s));
     ctx->df_members = 0;
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_members, d_count, 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_members, m.d_count, 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipStreamSynchronize(s));
     const uint64_t nm = ctx->df_members;
     if (nm == 0 || nm > n) return FG_ERR_ARG;  // (never: message 0 starts a member, and no member is without a first message)
-    uint64_t zt = 0;
-    if ((rc = fg_deflate_front(ctx, ctx->d_tout, total, d_cuts, nm, d_zoff, &zt, s)) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_zout, &ctx->d_zout_cap, zt + 16)) != FG_OK) return rc;
-    if ((rc = fg_deflate_pack(ctx, ctx->d_tout, d_cuts, nm, d_zoff, ctx->d_zout, ctx->d_zout_cap, s)) != FG_OK) return rc;
-    const uint64_t zb = up(zt, 256), lb = up((nm + 1) * 8, 256);
-    if ((rc = grow_pinned(ctx, (void**)&ctx->h_zout, &ctx->h_zout_cap, zb + 2 * lb)) != FG_OK) return rc;
-    uint8_t* h = ctx->h_zout;
-    if (zt) FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_zout, zt, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + zb, d_zoff, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + zb + lb, d_first, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
-    ctx->last_comp = fg_compressed{h, zt, reinterpret_cast<const uint64_t*>(h + zb), reinterpret_cast<const uint64_t*>(h + zb + lb), nm, total};
-    return FG_OK;
-}
-
-// The same stage with FG_WIRE_KAFKA_V0 set (fg_set_output_wire): the members are cut by the same rule over the same offsets, the message
-// set is built from ctx->d_tout with d_enc_status as the skipped rows, and the members' byte cuts are set_offsets[member_first[k]].
-// FG_COMP_GZIP: the set is deflated member by member and every non-empty member wrapped; FG_COMP_NONE: the set itself goes to ctx->h_zout,
-// the cuts as its z_offsets.  ctx->d_df_cut as above (its cuts[] are the plain stream's and unused); ctx->d_kf_off: set_offsets[n + 1] |
-// set_cuts[n + 2] | w_offsets[n + 2].  Synchronises where compress_stage does and for the set's and the wrappers' sizes.  n > 0.
-static int kafka_stage(fg_ctx* ctx, const uint64_t* d_out_offsets, const uint8_t* d_enc_status, uint64_t n, uint64_t total) {
-    hipStream_t s = ctx->stream;
-    if (!fg_launch_deflate_cuts || !fg_launch_kafka_cuts) return FG_ERR_UNSUPPORTED;  // (only in a build without the kernels: fg_ctx.hpp)
-    int rc;
-    const uint64_t flags_bytes = up(n * 4, 16), sums_bytes = up((n + 63) / 64 * 8, 16), list = (n + 2) * 8;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_df_cut, &ctx->d_df_cut_cap, flags_bytes + sums_bytes + 4 * list + 16)) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_off, &ctx->d_kf_off_cap, 3 * list)) != FG_OK) return rc;
-    uint8_t* b = ctx->d_df_cut;
-    uint32_t* d_flags = (uint32_t*)b;
-    uint64_t* d_sums = (uint64_t*)(b += flags_bytes);
-    uint64_t* d_idx = (uint64_t*)(b += sums_bytes);
-    uint64_t* d_first = (uint64_t*)(b += list);
-    uint64_t* d_cuts = (uint64_t*)(b += list);
-    uint64_t* d_zoff = (uint64_t*)(b += list);
-    uint64_t* d_count = (uint64_t*)(b += list);
-    uint64_t* d_set_off = (uint64_t*)ctx->d_kf_off;
-    uint64_t* d_set_cuts = (uint64_t*)(ctx->d_kf_off + list);
-    uint64_t* d_woff = (uint64_t*)(ctx->d_kf_off + 2 * list);
-    FG_LAUNCH(ctx, fg_launch_deflate_cuts(d_out_offsets, n, ctx->compress.coalesce, ctx->compress.member_bytes, d_flags, d_sums, d_idx, d_first, d_cuts,
-                                          d_count, s));
-    ctx->df_members = 0;
-    FG_HIP(ctx, hipMemcpyAsync(&ctx->df_members, d_count, 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipStreamSynchronize(s));
-    const uint64_t nm = ctx->df_members;
-    if (nm == 0 || nm > n) return FG_ERR_ARG;  // (never, as in compress_stage)
-    // the set, and the members' bounds in it
-    uint64_t st = 0;
-    if ((rc = fg_kafka_set_front(ctx, d_out_offsets, d_enc_status, n, total, d_set_off, &st, s)) != FG_OK) return rc;
-    if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_set, &ctx->d_kf_set_cap, st + 16)) != FG_OK) return rc;
-    if (st && (rc = fg_kafka_set_write(ctx, ctx->d_tout, d_out_offsets, d_enc_status, n, d_set_off, ctx->d_kf_set, ctx->d_kf_set_cap, s)) != FG_OK) return rc;
-    FG_LAUNCH(ctx, fg_launch_kafka_cuts(d_set_off, d_first, n, nm, d_set_cuts, s));
-    const uint8_t* d_wire = ctx->d_kf_set;
-    const uint64_t* d_wire_off = d_set_cuts;
-    uint64_t wt = st;
-    if (ctx->compress.codec == FG_COMP_GZIP) {
+    // what goes to the host: wt bytes at d_wire, the members' bounds in them d_wire_off[0 .. nm]
+    const uint8_t* d_wire = ctx->d_tout;
+    const uint64_t* d_wire_off = m.d_cuts;
+    uint64_t wt = total;
+    if (kafka) {
+        if ((rc = fg_kafka_set_front(ctx, d_out_offsets, d_enc_status, n, total, k.d_set_off, &wt, s)) != FG_OK) return rc;
+        if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_set, &ctx->d_kf_set_cap, wt + 16)) != FG_OK) return rc;
+        if (wt && (rc = fg_kafka_set_write(ctx, ctx->d_tout, d_out_offsets, d_enc_status, n, k.d_set_off, ctx->d_kf_set, ctx->d_kf_set_cap, s)) != FG_OK) return rc;
+        FG_LAUNCH(ctx, fg_launch_kafka_cuts(k.d_set_off, m.d_first, n, nm, k.d_set_cuts, s));
+        d_wire = ctx->d_kf_set;
+        d_wire_off = k.d_set_cuts;
+    }
+    if (gzip) {
         uint64_t zt = 0;
-        if ((rc = fg_deflate_front(ctx, ctx->d_kf_set, st, d_set_cuts, nm, d_zoff, &zt, s)) != FG_OK) return rc;
+        if ((rc = fg_deflate_front(ctx, d_wire, wt, d_wire_off, nm, m.d_zoff, &zt, s)) != FG_OK) return rc;
         if ((rc = grow_dev(ctx, (void**)&ctx->d_zout, &ctx->d_zout_cap, zt + 16)) != FG_OK) return rc;
-        if ((rc = fg_deflate_pack(ctx, ctx->d_kf_set, d_set_cuts, nm, d_zoff, ctx->d_zout, ctx->d_zout_cap, s)) != FG_OK) return rc;
-        if ((rc = fg_kafka_wrap_front(ctx, d_zoff, nm, d_woff, &wt, s)) != FG_OK) return rc;
-        if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_w, &ctx->d_kf_w_cap, wt + 16)) != FG_OK) return rc;
-        if ((rc = fg_kafka_wrap_write(ctx, ctx->d_zout, d_zoff, nm, d_woff, ctx->d_kf_w, ctx->d_kf_w_cap, s)) != FG_OK) return rc;
-        d_wire = ctx->d_kf_w;
-        d_wire_off = d_woff;
+        if ((rc = fg_deflate_pack(ctx, d_wire, d_wire_off, nm, m.d_zoff, ctx->d_zout, ctx->d_zout_cap, s)) != FG_OK) return rc;
+        d_wire = ctx->d_zout;
+        d_wire_off = m.d_zoff;
+        wt = zt;
+        if (kafka) {
+            if ((rc = fg_kafka_wrap_front(ctx, m.d_zoff, nm, k.d_woff, &wt, s)) != FG_OK) return rc;
+            if ((rc = grow_dev(ctx, (void**)&ctx->d_kf_w, &ctx->d_kf_w_cap, wt + 16)) != FG_OK) return rc;
+            if ((rc = fg_kafka_wrap_write(ctx, ctx->d_zout, m.d_zoff, nm, k.d_woff, ctx->d_kf_w, ctx->d_kf_w_cap, s)) != FG_OK) return rc;
+            d_wire = ctx->d_kf_w;
+            d_wire_off = k.d_woff;
+        }
     }
     const uint64_t zb = up(wt, 256), lb = up((nm + 1) * 8, 256);
     if ((rc = grow_pinned(ctx, (void**)&ctx->h_zout, &ctx->h_zout_cap, zb + 2 * lb)) != FG_OK) return rc;
     uint8_t* h = ctx->h_zout;
     if (wt) FG_HIP(ctx, hipMemcpyAsync(h, d_wire, wt, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync(h + zb, d_wire_off, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
-    FG_HIP(ctx, hipMemcpyAsync(h + zb + lb, d_first, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
+    FG_HIP(ctx, hipMemcpyAsync(h + zb + lb, m.d_first, (nm + 1) * 8, hipMemcpyDeviceToHost, s));
     ctx->last_comp = fg_compressed{h, wt, reinterpret_cast<const uint64_t*>(h + zb), reinterpret_cast<const uint64_t*>(h + zb + lb), nm, total};
     return FG_OK;
 }
@@ -1721,25 +1717,21 @@ static int transcode_tail(fg_ctx* ctx, fg_format fmt, fg_framing dec_framing, co
                               d_enc_status, &total, FG_STREAM_OWN);
     }
     if (rc != FG_OK) return rc;
-    // 4. the messages, the fixed arrays behind them -- or, with compression set, the members in the messages' place (ctx->h_zout)
-    //    (with FG_WIRE_KAFKA_V0: the message set or its wrapped members there, whatever the codec)
-    const bool kafka = ctx->wire == FG_WIRE_KAFKA_V0;
-    const bool gz = ctx->compress.codec == FG_COMP_GZIP || kafka;
-    const uint64_t plain = gz ? 0 : up(total, 256);
+    // 4. the messages, the fixed arrays behind them -- or, with a member stage, the members in the messages' place (ctx->h_zout)
+    const bool members = ctx->wire != FG_WIRE_RAW || ctx->compress.codec != FG_COMP_NONE;
+    const uint64_t plain = members ? 0 : up(total, 256);
     if ((rc = grow_pinned(ctx, (void**)&ctx->h_tout, &ctx->h_tout_cap, transcoded_arrays(nullptr, plain, n, frames, res))) != FG_OK) return rc;
     uint8_t* h = ctx->h_tout;
     transcoded_arrays(h, plain, n, frames, res);
-    if (kafka) {
-        if ((rc = kafka_stage(ctx, d_out_offsets, d_enc_status, n, total)) != FG_OK) return rc;
-    } else if (gz) {
-        if ((rc = compress_stage(ctx, d_out_offsets, n, total)) != FG_OK) return rc;
+    if (members) {
+        if ((rc = member_stage(ctx, d_out_offsets, d_enc_status, n, total)) != FG_OK) return rc;
     } else if (total) {
         FG_HIP(ctx, hipMemcpyAsync(h, ctx->d_tout, total, hipMemcpyDeviceToHost, s));
     }
     FG_HIP(ctx, hipMemcpyAsync((void*)res->out_offsets, d_out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync((void*)res->meta, dt.meta, n * 4, hipMemcpyDeviceToHost, s));
     FG_HIP(ctx, hipMemcpyAsync((void*)res->enc_status, d_enc_status, n, hipMemcpyDeviceToHost, s));
-    res->out = gz ? nullptr : h;
+    res->out = members ? nullptr : h;
     res->out_bytes = total;
     return FG_OK;
 }
@@ -1773,8 +1765,8 @@ int fg_transcode_batch(fg_ctx* ctx, fg_format fmt, fg_framing framing, const fg_
         if (rc != FG_ERR_UNSUPPORTED) return rc;
         *out = fg_transcoded{};
     }
-    // (with compression set every exit from here on waits for what it queued: the compress stage reads counts and sizes between its
-    //  steps, so an error may leave with work queued behind them.  Without compression this path's calls are what they were.)
+    // (with a member stage every exit from here on waits for what it queued: member_stage reads counts and sizes between its steps, so
+    //  an error may leave with work queued behind them.  Without one this path's calls are what they were.)
     DrainGuard drained(ctx);
     drained.armed = ctx->compress.codec != FG_COMP_NONE || ctx->wire != FG_WIRE_RAW;
     // 1. the chunk (and, for framed input, its offsets) to HBM

@@ -72,6 +72,15 @@ def _huffman(name: str) -> int:
     raise ValueError("huffman must be \"fixed\" or \"dynamic\"")
 
 
+def _view(ptr, count, dt):
+    """a copy of `count` elements of dtype `dt` at `ptr` (ctx-owned pinned memory a C call handed out); empty for none or NULL"""
+    import numpy as np
+
+    if not count or not ptr:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
+
+
 class Encoder:
     """Base class; subclasses fix ``enc`` (fg_encoder)."""
     enc = -1
@@ -162,17 +171,7 @@ class Encoder:
         total = C.c_uint64()
         args = (decoder._ctx, d_bytes.data_ptr() if d_bytes.numel() else None, d_bytes.numel(), d_cuts.data_ptr(), n)
         tail = (d_zoff.data_ptr(), C.byref(total), C.c_void_p(stream.cuda_stream))
-        rc = L.FG_ERR_ENT_OVERFLOW
-        if out is not None:
-            rc = L.lib().fg_deflate_device(*args, out.data_ptr(), out.numel(), *tail)
-            if rc not in (L.FG_OK, L.FG_ERR_ENT_OVERFLOW):
-                L.check(rc, "fg_deflate_device")
-        if rc == L.FG_ERR_ENT_OVERFLOW:
-            if out is None:
-                L.check(L.lib().fg_deflate_device(*args, None, 0, *tail), "fg_deflate_device (size)")
-            out = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=d_bytes.device)
-            L.check(L.lib().fg_deflate_device(*args, out.data_ptr(), out.numel(), *tail), "fg_deflate_device")
-        return out[:int(total.value)], d_zoff
+        return Encoder._sized_call(L.lib().fg_deflate_device, "fg_deflate_device", args, tail, total, out, d_bytes.device), d_zoff
 
     @staticmethod
     def _sized_call(fn, what, args, tail, total, out, device):
@@ -403,6 +402,13 @@ class Pipeline:
         L.check(L.lib().fg_set_deflate_mode(self.decoder._ctx, self.huffman), "fg_set_deflate_mode")
         L.check(L.lib().fg_set_output_wire(self.decoder._ctx, self.wire), "fg_set_output_wire")
 
+    def _transcode(self, what: str, now_ts: float, call):
+        """one transcode call: the encode cfg built, the ctx's output settings set, `call(ctx, fmt, cfg)` -- the C call itself, which the
+        caller spells out -- made and its return code checked"""
+        cfg, _keep = self._encode_cfg(now_ts)
+        self._set_compression()
+        L.check(call(self.decoder._ctx, self.decoder.fmt, C.byref(cfg)), what)
+
     def _compressed(self, t: Transcoded) -> Transcoded:
         """with compression set: the members of the call that produced `t` in place of its `out`"""
         import numpy as np
@@ -413,39 +419,24 @@ class Pipeline:
         c = L.fg_compressed()
         L.check(L.lib().fg_last_compressed(self.decoder._ctx, C.byref(c)), "fg_last_compressed")
         nm = int(c.n_members)
-
-        def view(ptr, count, dt):
-            if not count or not ptr:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
-
         t.out = None
-        t.z = view(c.z, int(c.z_bytes), np.uint8)
-        t.z_offsets = view(c.z_offsets, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
-        t.member_first = view(c.member_first, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
+        t.z = _view(c.z, int(c.z_bytes), np.uint8)
+        t.z_offsets = _view(c.z_offsets, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
+        t.member_first = _view(c.member_first, nm + 1, np.uint64) if nm else np.zeros(1, np.uint64)
         t.raw_bytes = int(c.raw_bytes)
         return t
 
     def _call(self, framing: int, data, nbytes: int, offsets, n: int, final: bool, now_ts: float) -> Transcoded:
         import numpy as np
 
-        cfg, _keep = self._encode_cfg(now_ts)
-        self._set_compression()
         res = L.fg_transcoded()
-        rc = L.lib().fg_transcode_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data, nbytes,
-                                        None if offsets is None else offsets.ctypes.data, n, int(final), C.byref(res))
-        L.check(rc, "fg_transcode_batch")
+        self._transcode("fg_transcode_batch", now_ts, lambda ctx, fmt, cfg: L.lib().fg_transcode_batch(
+            ctx, fmt, framing, cfg, data.ctypes.data, nbytes, None if offsets is None else offsets.ctypes.data, n, int(final), C.byref(res)))
         m = int(res.n)
-
-        def view(ptr, count, dt):
-            if not count or not ptr:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
-
-        return self._compressed(Transcoded(view(res.out, int(res.out_bytes), np.uint8),
-                                           view(res.out_offsets, m + 1 if m else 0, np.uint64) if m else np.zeros(1, np.uint64),
-                                           view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
-                                           view(res.frame_offsets, m + 1, np.uint64) if (m and res.frame_offsets) else None, int(res.consumed)))
+        return self._compressed(Transcoded(_view(res.out, int(res.out_bytes), np.uint8),
+                                           _view(res.out_offsets, m + 1 if m else 0, np.uint64) if m else np.zeros(1, np.uint64),
+                                           _view(res.meta, m, np.uint32), _view(res.enc_status, m, np.uint8),
+                                           _view(res.frame_offsets, m + 1, np.uint64) if (m and res.frame_offsets) else None, int(res.consumed)))
 
     def run_packed(self, data, offsets, now_ts: float = 0.0) -> Transcoded:
         """framed lines (packed bytes + offsets[n + 1], as produced by pack_lines)"""
@@ -481,26 +472,17 @@ class Pipeline:
         starts = np.ascontiguousarray(seg_starts, dtype=np.uint64)
         K = len(starts) - 1
         final = None if seg_final is None else np.ascontiguousarray(seg_final, dtype=np.uint8)
-        cfg, _keep = self._encode_cfg(now_ts)
-        self._set_compression()
         res = L.fg_transcoded_multi()
-        rc = L.lib().fg_transcode_multi_batch(self.decoder._ctx, self.decoder.fmt, framing, C.byref(cfg), data.ctypes.data if data.size else None,
-                                              data.size, starts.ctypes.data, final.ctypes.data if final is not None and K else None, K,
-                                              C.byref(res))
-        L.check(rc, "fg_transcode_multi_batch")
+        self._transcode("fg_transcode_multi_batch", now_ts, lambda ctx, fmt, cfg: L.lib().fg_transcode_multi_batch(
+            ctx, fmt, framing, cfg, data.ctypes.data if data.size else None, data.size, starts.ctypes.data,
+            final.ctypes.data if final is not None and K else None, K, C.byref(res)))
         m = int(res.n)
-
-        def view(ptr, count, dt):
-            if not count or not ptr:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
-
         syslen = framing == L.FG_FRAME_SYSLEN
-        return self._compressed(TranscodedMulti(view(res.out, int(res.out_bytes), np.uint8), view(res.out_offsets, m + 1, np.uint64),
-                                                view(res.meta, m, np.uint32), view(res.enc_status, m, np.uint8),
-                                                view(res.slot_offsets, m if syslen else m + 1, np.uint64), view(res.slot_kind, m, np.uint8),
-                                                view(res.seg_first, K + 1, np.uint64), view(res.seg_consumed, K, np.uint64),
-                                                view(res.seg_stop, K, np.uint8) if res.seg_stop else None))
+        return self._compressed(TranscodedMulti(_view(res.out, int(res.out_bytes), np.uint8), _view(res.out_offsets, m + 1, np.uint64),
+                                                _view(res.meta, m, np.uint32), _view(res.enc_status, m, np.uint8),
+                                                _view(res.slot_offsets, m if syslen else m + 1, np.uint64), _view(res.slot_kind, m, np.uint8),
+                                                _view(res.seg_first, K + 1, np.uint64), _view(res.seg_consumed, K, np.uint64),
+                                                _view(res.seg_stop, K, np.uint8) if res.seg_stop else None))
 
     def run_datagrams(self, datagrams, max_inflated=None, now_ts: float = 0.0) -> TranscodedUdp:
         """fg_udp_transcode_batch: the body of the UDP input's receive loop (input/udp_input.rs:66-143) for a batch -- a list of
@@ -519,19 +501,10 @@ class Pipeline:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = len(offsets) - 1
         nbytes = int(offsets[-1]) if n else 0
-        cfg, _keep = self._encode_cfg(now_ts)
-        self._set_compression()
         res, ust = L.fg_transcoded(), C.c_void_p()
-        rc = L.lib().fg_udp_transcode_batch(self.decoder._ctx, self.decoder.fmt, C.byref(cfg), data.ctypes.data if nbytes else None, nbytes,
-                                            offsets.ctypes.data, n, int(max_inflated or 0), C.byref(res), C.byref(ust))
-        L.check(rc, "fg_udp_transcode_batch")
-
-        def view(ptr, count, dt):
-            if not count or not ptr:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dt).itemsize,)).view(dt).copy()
-
-        return self._compressed(TranscodedUdp(view(res.out, int(res.out_bytes), np.uint8),
-                                              view(res.out_offsets, n + 1, np.uint64) if n else np.zeros(1, np.uint64),
-                                              view(res.meta, n, np.uint32), view(res.enc_status, n, np.uint8), int(res.consumed), view(ust, n, np.uint8),
+        self._transcode("fg_udp_transcode_batch", now_ts, lambda ctx, fmt, cfg: L.lib().fg_udp_transcode_batch(
+            ctx, fmt, cfg, data.ctypes.data if nbytes else None, nbytes, offsets.ctypes.data, n, int(max_inflated or 0), C.byref(res), C.byref(ust)))
+        return self._compressed(TranscodedUdp(_view(res.out, int(res.out_bytes), np.uint8),
+                                              _view(res.out_offsets, n + 1, np.uint64) if n else np.zeros(1, np.uint64),
+                                              _view(res.meta, n, np.uint32), _view(res.enc_status, n, np.uint8), int(res.consumed), _view(ust, n, np.uint8),
                                               self.decoder.fmt))

@@ -62,10 +62,9 @@ inline void trampoline() {
 // Run `body` once per lane, in lockstep at the cross-lane primitives.  Throws std::runtime_error on divergence.
 inline void run_wave(const std::function<void()>& body, size_t stack_bytes = 512u << 10) {
     static thread_local Wave* w = nullptr;
-    if (!w) {
-        w = new Wave();
-        w->stacks.resize((size_t)Wave::kLanes * stack_bytes);
-    }
+    if (!w) w = new Wave();
+    // (callers ask for different lane stacks -- deflate_driver.hpp's lane_stack() beside the default: never less than this call's)
+    if (w->stacks.size() < (size_t)Wave::kLanes * stack_bytes) w->stacks.resize((size_t)Wave::kLanes * stack_bytes);
     Wave* prev = current();
     current() = w;
     w->body = body;

@@ -1,6 +1,7 @@
 // kafka_driver.hpp -- the passes of fg_kafka.hip as host loops over fg_kafka.hpp on the wave emulation: what a kernel does per wave or per
 // lane, a loop does per iteration, with the kernels' arguments (test infrastructure, host only).
 #pragma once
+#include <functional>
 #include <vector>
 
 #include "fg_kafka.hpp"
@@ -9,6 +10,17 @@ namespace fgk {
 namespace kf = fg::kafka;
 
 constexpr uint64_t kBadArgs = ~0ull;
+
+// bytes of stack per emulated lane (0 = the emulation's default), as deflate_driver.hpp's: a sanitized stand-alone program asks for
+// small ones, AddressSanitizer's cost of a lane switch grows with them
+inline size_t& lane_stack() {
+    static size_t v = 0;
+    return v;
+}
+inline void run_wave(const std::function<void()>& body) {
+    if (lane_stack()) fg::emu::run_wave(body, lane_stack());
+    else fg::emu::run_wave(body);
+}
 
 // k_kf_sizes and its scan: set_off[n + 1]; false for offsets the set refuses
 inline bool sizes(const uint64_t* off, const uint8_t* skip, uint64_t n, uint64_t nbytes, uint64_t* set_off) {
@@ -28,7 +40,7 @@ inline void write(const uint8_t* bytes, const uint64_t* off, const uint8_t* skip
     const uint64_t steps = kf::write_steps(n);
     for (uint64_t w = 0; w < waves && w < steps; ++w) {
         std::vector<uint32_t> lds(kf::kLdsWords);
-        fg::emu::run_wave([&] {
+        run_wave([&] {
             kf::build_tables(lds.data());
             const kf::Lds s = kf::lds_of(lds.data());
             for (uint64_t k = w; k < steps; k += waves) kf::write_step(bytes, off, skip, n, k * kf::kRowsPerWave, set_off, set, set_cap, s);
@@ -63,7 +75,7 @@ inline void wrap(const uint8_t* z, const uint64_t* z_off, const uint64_t* piece_
     const uint64_t np = piece_first[n_members];
     std::vector<uint32_t> lds(kf::kLdsWords);
     if (np)
-        fg::emu::run_wave([&] {
+        run_wave([&] {
             kf::build_tables(lds.data());
             const kf::Lds s = kf::lds_of(lds.data());
             for (uint64_t g = 0; g < np; ++g) kf::wrap_piece(z, z_off, piece_first, n_members, g, w_off, w, w_cap, piece_crc, s);

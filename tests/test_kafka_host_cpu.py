@@ -5,6 +5,7 @@ real ones, so what comes out is held against tests/kafka_wire.py and zlib; the d
 host_pipeline_fake.cpp, as in test_deflate_host_cpu.py, whose batches and entry points these tests share."""
 import ctypes as C
 import subprocess
+import warnings
 
 import numpy as np
 import pytest
@@ -12,6 +13,7 @@ import pytest
 import deflate_model as dm
 import kafka_model as km
 import kafka_wire as kw
+import test_deflate_dynamic_host_cpu as Y
 import test_deflate_host_cpu as D
 import test_host_pipeline_cpu as H
 from flowgger_amd import _lib as L
@@ -222,6 +224,83 @@ def test_argument_errors_of_the_resident_calls(fake):
     c.close()
 
 
+def runtime_calls_and_caps(lib, entry, wire, codec, policy, dynamic=False):
+    """the counted runtime calls of the first and of the second (warm) call of one configuration over D.lines_of(300) on a ctx of its
+    own, and what fgf_deflate_caps reports behind them: d_df_slots, d_zout, h_zout, d_df_cut"""
+    c = Ctx(lib)
+    D.set_compression(lib, c, L.FG_COMP_GZIP if codec == "gzip" else L.FG_COMP_NONE, *policy)
+    set_wire(lib, c, KAFKA if wire == "kafka" else RAW)
+    if dynamic:
+        assert lib.fg_set_deflate_mode(c.h, L.FG_DEFLATE_DYNAMIC) == 0
+    lines, calls = D.lines_of(300), []
+    for _ in range(2):
+        c0 = lib.fgf_calls()
+        assert D.ENTRIES[entry](lib, c, lines)[0] == 0 and lib.fgf_in_flight() == 0
+        calls.append(int(lib.fgf_calls() - c0))
+    caps = (C.c_ulonglong * 4)()
+    lib.fgf_deflate_caps(c.h, caps)
+    c.close()
+    assert all(int(x) % (1 << 20) == 0 for x in caps)  # (grow_dev and grow_pinned round up to whole MiB)
+    return calls + [int(x) >> 20 for x in caps]
+
+
+# Recorded from the PARENT commit's fake build (compress_stage and kafka_stage as two functions, the resident entries written out one
+# by one), not from the code under test: [calls of the first call, calls of the warm call, then the four capacities in MiB].
+PARENT_CALLS_AND_CAPS = {
+    ('multi', 'raw', 'none', 'fixed', (1, 0)): [27, 27, 0, 0, 0, 0],
+    ('multi', 'raw', 'none', 'fixed', (0, 4096)): [27, 27, 0, 0, 0, 0],
+    ('multi', 'raw', 'gzip', 'fixed', (1, 0)): [41, 41, 1, 1, 1, 1],
+    ('multi', 'raw', 'gzip', 'fixed', (0, 4096)): [41, 41, 1, 1, 1, 1],
+    ('multi', 'kafka', 'none', 'fixed', (1, 0)): [38, 38, 0, 0, 1, 1],
+    ('multi', 'kafka', 'none', 'fixed', (0, 4096)): [38, 38, 0, 0, 1, 1],
+    ('multi', 'kafka', 'gzip', 'fixed', (1, 0)): [53, 53, 1, 1, 1, 1],
+    ('multi', 'kafka', 'gzip', 'fixed', (0, 4096)): [53, 53, 1, 1, 1, 1],
+    ('multi', 'raw', 'gzip', 'dynamic', (1, 0)): [41, 41, 1, 1, 1, 1],
+    ('multi', 'raw', 'gzip', 'dynamic', (0, 4096)): [41, 41, 1, 1, 1, 1],
+    ('packed', 'raw', 'none', 'fixed', (1, 0)): [19, 19, 0, 0, 0, 0],
+    ('packed', 'raw', 'none', 'fixed', (0, 4096)): [19, 19, 0, 0, 0, 0],
+    ('packed', 'raw', 'gzip', 'fixed', (1, 0)): [33, 33, 1, 1, 1, 1],
+    ('packed', 'raw', 'gzip', 'fixed', (0, 4096)): [33, 33, 1, 1, 1, 1],
+    ('packed', 'kafka', 'none', 'fixed', (1, 0)): [30, 30, 0, 0, 1, 1],
+    ('packed', 'kafka', 'none', 'fixed', (0, 4096)): [30, 30, 0, 0, 1, 1],
+    ('packed', 'kafka', 'gzip', 'fixed', (1, 0)): [45, 45, 1, 1, 1, 1],
+    ('packed', 'kafka', 'gzip', 'fixed', (0, 4096)): [45, 45, 1, 1, 1, 1],
+    ('packed', 'raw', 'gzip', 'dynamic', (1, 0)): [33, 33, 1, 1, 1, 1],
+    ('packed', 'raw', 'gzip', 'dynamic', (0, 4096)): [33, 33, 1, 1, 1, 1],
+    ('udp', 'raw', 'none', 'fixed', (1, 0)): [27, 27, 0, 0, 0, 0],
+    ('udp', 'raw', 'none', 'fixed', (0, 4096)): [27, 27, 0, 0, 0, 0],
+    ('udp', 'raw', 'gzip', 'fixed', (1, 0)): [41, 41, 1, 1, 1, 1],
+    ('udp', 'raw', 'gzip', 'fixed', (0, 4096)): [41, 41, 1, 1, 1, 1],
+    ('udp', 'kafka', 'none', 'fixed', (1, 0)): [38, 38, 0, 0, 1, 1],
+    ('udp', 'kafka', 'none', 'fixed', (0, 4096)): [38, 38, 0, 0, 1, 1],
+    ('udp', 'kafka', 'gzip', 'fixed', (1, 0)): [53, 53, 1, 1, 1, 1],
+    ('udp', 'kafka', 'gzip', 'fixed', (0, 4096)): [53, 53, 1, 1, 1, 1],
+    ('udp', 'raw', 'gzip', 'dynamic', (1, 0)): [41, 41, 1, 1, 1, 1],
+    ('udp', 'raw', 'gzip', 'dynamic', (0, 4096)): [41, 41, 1, 1, 1, 1],
+}
+
+
+@pytest.mark.parametrize("entry", sorted(D.ENTRIES))
+def test_runtime_calls_and_capacities_are_the_parents(fake, entry):
+    """every transcode entry, wire, codec and member policy (and FG_DEFLATE_DYNAMIC where a fake has its launcher: the library of
+    test_deflate_dynamic_host_cpu.py, which has no Kafka launchers) makes the runtime calls the parent made and grows the compressor's
+    buffers to the parent's sizes.  What this does not see: kafka with dynamic deflate (no fake library has both sets of launchers;
+    the stand-alone program of the test below defines the missing one and runs those cells), and a layout whose byte count moves by
+    less than the MiB the capacities are rounded to -- that is the stand-alone program's business too, under AddressSanitizer."""
+    got = {}
+    for wire in ("raw", "kafka"):
+        for codec in ("none", "gzip"):
+            for policy in ((1, 0), (0, 4096)):
+                got[(entry, wire, codec, "fixed", policy)] = runtime_calls_and_caps(fake, entry, wire, codec, policy)
+    dyn = Y.load(Y.LIB, Y.SRC)
+    dyn.fg_set_output_wire.argtypes = [vp, C.c_int]
+    dyn.fgf_deflate_caps.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    for policy in ((1, 0), (0, 4096)):
+        got[(entry, "raw", "gzip", "dynamic", policy)] = runtime_calls_and_caps(dyn, entry, "raw", "gzip", policy, dynamic=True)
+    want = {k: v for k, v in PARENT_CALLS_AND_CAPS.items() if k[0] == entry}
+    assert got == want
+
+
 @pytest.mark.parametrize("codec", ["none", "gzip"])
 @pytest.mark.parametrize("entry", sorted(D.ENTRIES))
 def test_a_failed_runtime_call_at_every_index_leaves_nothing_in_flight_and_the_ctx_usable(fake, entry, codec):
@@ -256,3 +335,24 @@ def test_a_failed_runtime_call_at_every_index_leaves_nothing_in_flight_and_the_c
             bad.append((i, why))
     c.close()
     assert not bad, f"{len(bad)} of {calls} call indices: {bad}"
+
+
+def test_sanitized_standalone_run_of_the_host_stages(tmp_path):
+    """the scratch layouts, the member stage and the sized resident calls in a stand-alone program under AddressSanitizer and UBSan
+    (tests/native/host_stages_san_main.cpp, on the fake runtime, whose device memory is malloc'd): the grid of the test above through the
+    three transcode entries, the five resident entries at n = 0, 1, 63, 64, 65, 130 as a sizing call, at exact capacity and a byte
+    short, a failed runtime call at every index of one kafka + gzip transcode.  Nothing loaded into Python is sanitized."""
+    exe = tmp_path / "host_stages_san"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-unused-variable", "-fno-omit-frame-pointer",
+           f"-I{H.HERE / 'fakehip'}", f"-I{H.ROOT / 'include'}", f"-I{D.CSRC}", f"-I{H.HERE}", str(H.HERE / "host_stages_san_main.cpp"), "-o", str(exe)]
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    b = subprocess.run(cmd[:1] + san + cmd[1:], capture_output=True, text=True)
+    if b.returncode != 0:
+        # only a linker that cannot find the sanitizers' runtime may fall back to the plain build, which still runs every case, and
+        # the run says so; anything else the sanitized build trips over is a failure
+        assert "cannot find" in b.stderr and ("asan" in b.stderr or "ubsan" in b.stderr), b.stderr[-4000:]
+        warnings.warn("no sanitizer runtime on this machine: host_stages_san_main.cpp ran WITHOUT AddressSanitizer / UBSan")
+        subprocess.run(cmd, check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    # (AddressSanitizer says once on stderr that it does not fully support swapcontext -- the fibers of the wave emulation; an error ends the run)
+    assert r.returncode == 0 and r.stdout.split() == ["ok", "48", "cells", "48", "resident", "45", "faults"] and "ERROR" not in r.stderr, r.stdout + r.stderr
